@@ -7,14 +7,17 @@
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --mode train [--gpus N]                 data-parallel TRAINING step (fwd + bwd + AdamW, grad-accum 4,
                                                              gradient all-reduce over RCCL): secondary figure
+    python bench.py --full                                  the line above plus everything that is not the headline figure
+    python bench.py --dump-outputs DIR                      also writes the last timed step's output as DIR/<name>.npy
 
 A step = one pass of the hot path over one synthetic batch that is already resident in HBM:
 wav (B x 40 s @ 16 kHz) -> Fbank -> global normalisation -> CNN front end -> src Linear -> 18 ConMamba
 layers -> final LayerNorm (reference train_CTC.py:285-298 + TransformerASR.encode), bf16 autocast, eval.
 Each rank processes its own utterance shard (weak scaling, no data-path collective: SURVEY.md §8e).
-Rank 0 prints ONE JSON line; `roofline` is for the dominant kernel (the selective scan) measured with HIP
-events on the launching stream; `cpu_baseline` is the CPU oracle (port of the reference path) on a bounded
-sample, rank 0 at N=1 only.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and prints the line; only --full measures
+more: `roofline` for the dominant kernel (the selective scan) with HIP events on the launching stream, `cpu_baseline`
+(the CPU oracle, a port of the reference path, on a bounded sample) and, in forward mode, the `survey_b16` and `train`
+keys (the last three at N=1 only).
 """
 import argparse
 import json
@@ -43,9 +46,15 @@ def parse():
                          "288 GB MI355X.  SURVEY §8d's 16 x 40 s: --batch 16")
     ap.add_argument("--frames", type=int, default=4000, help="10 ms audio frames per utterance (L)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure also measure the roofline, the CPU baseline and the extra keys (off: a plain run "
+                         "times the steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy (float32 or float64, at most 64 MB in "
+                         "all; a larger output as a fixed seeded sample): encoder_out in forward mode, loss in train mode")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="forward mode, 1 GPU: skip the extra keys of the line (\"train\": the training micro-batch of --mode train at 32 utterances; "
+                    help="--full, forward mode, 1 GPU: skip the extra keys of the line (\"train\": the training micro-batch of --mode train at 32 utterances; "
                          "\"survey_b16\": the forward at SURVEY §8d's 16 x 40 s)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured hipGraph")
     ap.add_argument("--graph-train", action="store_true",
@@ -53,8 +62,8 @@ def parse():
     ap.add_argument("--streams", type=int, default=None, help="parts / HIP streams of the fused encoder (default: CM_STREAMS or 2)")
     ap.add_argument("--stream-mode", choices=["join", "free", "pair"], default=None,
                     help="join (default): the scan runs once per layer on the whole batch; free: fully independent parts")
-    ap.add_argument("--cpu-frames", type=int, default=4000, help="frames per utterance of the CPU-baseline sample")
-    ap.add_argument("--cpu-batch", type=int, default=64, help="utterances in the CPU-baseline sample")
+    ap.add_argument("--cpu-frames", type=int, default=4000, help="--full: frames per utterance of the CPU-baseline sample")
+    ap.add_argument("--cpu-batch", type=int, default=64, help="--full: utterances in the CPU-baseline sample")
     ap.add_argument("--mode", choices=["forward", "train"], default="forward",
                     help="forward (default, the headline metric) or train: fwd + bwd + AdamW through the Brain loop with the "
                          "gradient exchange of mamba_asr_amd.ddp (reference train_CTC.py:1062 + conmamba_large.yaml:90)")
@@ -64,7 +73,10 @@ def parse():
     ap.add_argument("--accum", type=int, default=4, help="train mode: grad_accumulation_factor (conmamba_large.yaml:90)")
     ap.add_argument("--comm-dtype", choices=["f32", "bf16"], default="f32", help="train mode: gradient transport dtype")
     ap.add_argument("--ddp-algo", choices=["allreduce", "mesh"], default=None, help="train mode: see mamba_asr_amd/ddp.py")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def _free_port() -> int:
@@ -128,6 +140,29 @@ def pmc_traffic(batch, seqlen, dim, dtype):
         except (OSError, KeyError, ValueError):
             continue
     return None
+
+
+DUMP_BYTES = 32 * 2 ** 20        # cap per array written by --dump-outputs (one array per mode: under 64 MB in all)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor as <path>/<name>.npy, float32 (float64 stays float64).  A tensor over DUMP_BYTES is
+    cut into rows of its last dimension (one encoder frame: d_model values) and a fixed seeded sample of them is written,
+    in their original order, as a (rows, last dim) array: the same shape gives the same rows in every run.  The inputs are
+    seeded, but the bf16 forward is not bit-reproducible: two runs of one build differ by up to ~1 bf16 ulp (measured:
+    max |diff| 0.024 on the default workload's encoder output, mean |x| 0.79), so compare builds with a tolerance."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        t = t if t.dtype == torch.float64 else t.float()
+        if t.numel() * t.element_size() > DUMP_BYTES:
+            rows = t.reshape(-1, t.shape[-1])
+            keep = DUMP_BYTES // (rows.shape[1] * t.element_size())
+            idx = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = rows[idx]
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
 
 
 def make_batch(a, cfg, rank, dev):
@@ -236,31 +271,34 @@ def run_train(a, cfg, dev, rank, world, use_dist, emit_line=True):
     losses = [float(l) for l in losses]
     assert all(l == l for l in losses), "non-finite loss"
     value = world * a.batch * a.frames * a.steps / elapsed
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"loss": torch.tensor(losses[-1], dtype=torch.float64)})
     roof = None
-    # backward-scan roofline: one more micro-batch on EVERY rank (it may end in the exchange), HIP events on rank 0
-    ops.LAUNCH_LOG = [] if rank == 0 else None
-    brain.graph_steps = False                                  # the per-launch event pairs need eager launches
-    brain.fit_batch(batch)
-    torch.cuda.synchronize()
-    log, ops.LAUNCH_LOG = ops.LAUNCH_LOG, None
-    if rank == 0:
-        e_inner, n_state, s_ = cfg.expand * cfg.d_model, cfg.d_state, (2 if a.dtype == "bf16" else 4)
-        per_step = (9 * e_inner + 4 * n_state) * s_                                 # fwd reads + dout, du / ddelta / dz + dB / dC, per scan step and direction
-        for name, label, ndir in (("cm_scan_cl_bwd", "scan_rows_bwd_kernel + fixed-order reduce (cm_scan_cl_bwd: both BiMamba directions per launch)", 2),
-                                  ("cm_selective_scan_bwd", "scan_bwd_kernel (cm_selective_scan_bwd, one direction per launch)", 1)):
-            # encoder launches only (a decoder's scans have other sizes): the most frequent unit count
-            ts_all = [(e0.elapsed_time(e1), u) for nm, e0, e1, u in log if nm == name]
-            if not ts_all:
-                continue
-            u_enc = a.batch * (a.frames // 4) * ndir
-            ts = [t for t, u in ts_all if u == u_enc] or [t for t, _ in ts_all]
-            alg = u_enc * per_step
-            avg_ms = sum(ts) / len(ts)
-            roof = {"bound": "hbm", "achieved": round(alg / (avg_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(alg / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": None, "kernel": label,
-                    "avg_launch_us": round(avg_ms * 1e3, 1), "us_per_direction": round(avg_ms * 1e3 / ndir, 1),
-                    "launches_per_step": len(ts), "alg_bytes_per_launch": alg}
-            break
+    if a.full:
+        # backward-scan roofline: one more micro-batch on EVERY rank (it may end in the exchange), HIP events on rank 0
+        ops.LAUNCH_LOG = [] if rank == 0 else None
+        brain.graph_steps = False                                  # the per-launch event pairs need eager launches
+        brain.fit_batch(batch)
+        torch.cuda.synchronize()
+        log, ops.LAUNCH_LOG = ops.LAUNCH_LOG, None
+        if rank == 0:
+            e_inner, n_state, s_ = cfg.expand * cfg.d_model, cfg.d_state, (2 if a.dtype == "bf16" else 4)
+            per_step = (9 * e_inner + 4 * n_state) * s_                                 # fwd reads + dout, du / ddelta / dz + dB / dC, per scan step and direction
+            for name, label, ndir in (("cm_scan_cl_bwd", "scan_rows_bwd_kernel + fixed-order reduce (cm_scan_cl_bwd: both BiMamba directions per launch)", 2),
+                                      ("cm_selective_scan_bwd", "scan_bwd_kernel (cm_selective_scan_bwd, one direction per launch)", 1)):
+                # encoder launches only (a decoder's scans have other sizes): the most frequent unit count
+                ts_all = [(e0.elapsed_time(e1), u) for nm, e0, e1, u in log if nm == name]
+                if not ts_all:
+                    continue
+                u_enc = a.batch * (a.frames // 4) * ndir
+                ts = [t for t, u in ts_all if u == u_enc] or [t for t, _ in ts_all]
+                alg = u_enc * per_step
+                avg_ms = sum(ts) / len(ts)
+                roof = {"bound": "hbm", "achieved": round(alg / (avg_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(alg / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": None, "kernel": label,
+                        "avg_launch_us": round(avg_ms * 1e3, 1), "us_per_direction": round(avg_ms * 1e3 / ndir, 1),
+                        "launches_per_step": len(ts), "alg_bytes_per_launch": alg}
+                break
     if rank == 0:
         line = {"metric": f"training audio-frames/sec ({cfg.name}, L={a.frames}, fwd+bwd+AdamW" + (", encoder + Mamba decoder, 0.3 CTC + 0.7 KL)" if s2s else ")"),
                 "value": round(value, 1),
@@ -375,10 +413,12 @@ def main():
     assert torch.isfinite(out.float()).all()
     frames_total = world * a.batch * a.frames * a.steps
     value = frames_total / elapsed
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"encoder_out": out})
 
     # ---- roofline of the dominant kernel: selective-scan forward, HIP events on its launch stream
     roof = None
-    if rank == 0:
+    if a.full and rank == 0:
         # Eager pass, each native launch bracketed by HIP events on its stream.  An event's timestamp is taken when the stream
         # REACHES it: if the host is the slower side, the stream sits empty, the first event fires at once and the interval
         # includes the host's launch latency (measured: +11 us on a 250 us kernel).  So every pass starts behind a blocker --
@@ -432,7 +472,7 @@ def main():
 
     # ---- extra keys (1 GPU, the default configuration): SURVEY §8d's 16 x 40 s forward, and the training micro-batch
     extras = {}
-    if rank == 0 and world == 1 and not a.no_extras and a.config == "conmamba_large_ctc" and a.batch != 16 and not a.no_graph:
+    if a.full and rank == 0 and world == 1 and not a.no_extras and a.config == "conmamba_large_ctc" and a.batch != 16 and not a.no_graph:
         import copy
         a16 = copy.copy(a)
         a16.batch = 16
@@ -462,12 +502,13 @@ def main():
                                 "scan_roofline_frac_raw_interval": round(alg16 / (sum(sc) / len(sc) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if sc else None}
         del g16, w16, l16
     base = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         base = cpu_baseline(model, cfg, a.cpu_frames, a.cpu_batch)
-    if rank == 0 and world == 1 and not a.no_extras and a.config == "conmamba_large_ctc":
+    if a.full and rank == 0 and world == 1 and not a.no_extras and a.config == "conmamba_large_ctc":
         import copy
         at = copy.copy(a)
         at.batch, at.steps, at.warmup, at.accum, at.comm_dtype, at.ddp_algo = 32, 8, 4, 4, "f32", None
+        at.dump_outputs = None                                                       # the dump holds the timed forward only
         at.graph_train = not a.no_graph                                              # the micro-batch's fwd + loss + bwd as a hipGraph, as the forward line
         graphed = step = out = None                                                  # release the forward's graph and buffers
         del model

@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for v in 0 2 3 4 5; do
   CM_LIB_PATH=$R/mamba_asr_amd/lib/libconmamba_hip_ablate.so CM_DEBUG=$v rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/st$v -- \
-      python3 $R/bench.py --no-cpu-baseline --no-extras --streams 1 --steps 8 > $OUT/b$v.log 2>&1
+      python3 $R/bench.py --full --no-cpu-baseline --no-extras --streams 1 --steps 8 > $OUT/b$v.log 2>&1
   find $OUT/st$v -name "*kernel_stats.csv" -exec cp {} $OUT/stats$v.csv \;
   rm -rf $OUT/st$v
 done

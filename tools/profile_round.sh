@@ -9,8 +9,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof_$ROUND
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $OUT/bench.json.log 2> $OUT/bench.err || exit 1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --no-cpu-baseline > $OUT/bench_under_rocprof.json.log 2>&1 || exit 1
+python3 $R/bench.py --full > $OUT/bench.json.log 2> $OUT/bench.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --full --no-cpu-baseline > $OUT/bench_under_rocprof.json.log 2>&1 || exit 1
 for B in 64 32; do
   B=$B rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch_b$B -- python3 $R/tools/pmc_scan.py > $OUT/pmc_fetch_b$B.log 2>&1 || exit 1
   B=$B rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write_b$B -- python3 $R/tools/pmc_scan.py > $OUT/pmc_write_b$B.log 2>&1 || exit 1
