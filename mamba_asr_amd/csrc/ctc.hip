@@ -13,9 +13,11 @@ namespace {
 
 constexpr float NEG_INF = -__builtin_huge_valf();
 
+// NaN in, NaN out: fmaxf drops a NaN operand, so an all -inf maximum returns the plain sum (-inf, or NaN when one operand is
+// NaN); with a finite maximum a NaN operand makes its exponential NaN.  (+inf - +inf is NaN too, as in torch's recursion.)
 __device__ __forceinline__ float lse3(float a, float b, float c) {
     const float m = fmaxf(a, fmaxf(b, c));
-    if (m == NEG_INF) return NEG_INF;
+    if (m == NEG_INF) return a + b + c;
     return m + CM_LN2 * cm_log2(cm_exp2(CM_LOG2E * (a - m)) + cm_exp2(CM_LOG2E * (b - m)) + cm_exp2(CM_LOG2E * (c - m)));
 }
 
@@ -103,10 +105,13 @@ __global__ __launch_bounds__(256) void ctc_grad_classes_kernel(const cm_ctc_args
         const float aN = al[(int64_t)(T - 1) * p.Sx_max + Sx - 1], aM = Sx > 1 ? al[(int64_t)(T - 1) * p.Sx_max + Sx - 2] : NEG_INF;
         nll = -lse3(aN, aM, NEG_INF);
     }
-    const bool inf = !(nll < __builtin_huge_valf());                 // infeasible alignment (or NaN): zero_infinity
+    // zero_infinity: only an infeasible alignment (nll = +inf) gives loss 0 and gradient 0.  A NaN nll (NaN / +inf log-probs on
+    // the lattice) is written as NaN with a NaN gradient row at every step t < T, as torch.nn.functional.ctc_loss does
+    const bool inf = nll == __builtin_huge_valf(), nan = nll != nll;
     if (t == 0 && lane == 0) p.nll[b] = inf ? 0.f : nll;
-    if (t >= T || inf) {
-        for (int v = lane; v < p.V; v += 64) g[v] = 0.f;
+    if (t >= T || inf || nan) {
+        const float fill = (t < T && nan) ? __builtin_nanf("") : 0.f;
+        for (int v = lane; v < p.V; v += 64) g[v] = fill;
         return;
     }
     const int64_t *tg = p.targets + (int64_t)b * p.S;
@@ -161,10 +166,13 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const cm_ctc_args p) {
         const float aN = al[(int64_t)(T - 1) * p.Sx_max + Sx - 1], aM = Sx > 1 ? al[(int64_t)(T - 1) * p.Sx_max + Sx - 2] : NEG_INF;
         nll = -lse3(aN, aM, NEG_INF);
     }
-    const bool inf = !(nll < __builtin_huge_valf());                 // infeasible alignment (or NaN): zero_infinity
+    // zero_infinity: only an infeasible alignment (nll = +inf) gives loss 0 and gradient 0.  A NaN nll (NaN / +inf log-probs on
+    // the lattice) is written as NaN with a NaN gradient row at every step t < T, as torch.nn.functional.ctc_loss does
+    const bool inf = nll == __builtin_huge_valf(), nan = nll != nll;
     if (t == 0 && lane == 0) p.nll[b] = inf ? 0.f : nll;
-    if (t >= T || inf) {
-        for (int v = lane; v < p.V; v += 64) g[v] = 0.f;
+    if (t >= T || inf || nan) {
+        const float fill = (t < T && nan) ? __builtin_nanf("") : 0.f;
+        for (int v = lane; v < p.V; v += 64) g[v] = fill;
         return;
     }
     const int64_t *tg = p.targets + (int64_t)b * p.S;

@@ -348,13 +348,90 @@ def mamba_uni(p: Dict[str, torch.Tensor], hidden, scan=selective_scan, prefix=""
 # a10-a12. ConvolutionModule / ConmambaEncoderLayer / ConmambaEncoder
 # (reference: modules/Conmamba.py:439-449, :631-650, :716-727)
 # --------------------------------------------------------------------------
+# The product's dropout stream (mamba_asr_amd/csrc/cm_dropout.h), restated on
+# the host so that tests get masks that no kernel under test produced.
+# Element e of a row-major tensor belongs to group e // 8; a group draws four
+# 32-bit words, word j holding element 2j in its low and 2j+1 in its high 16
+# bits; the element is kept when its 16 bits are >= round(p * 65536) (capped
+# at 65535), and survivors are scaled by 1 / (1 - thresh / 65536).
+# --------------------------------------------------------------------------
+DROP_EPOCH_MUL = 0x9E3779B97F4A7C15
+
+
+def _mix32(x: np.ndarray) -> np.ndarray:
+    """murmur3's 32-bit finaliser on a uint32 array (wrapping arithmetic)."""
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x85EBCA6B)
+    x = x ^ (x >> np.uint32(13))
+    x = x * np.uint32(0xC2B2AE35)
+    return x ^ (x >> np.uint32(16))
+
+
+def drop_thresh(p: float) -> int:
+    """The 16-bit keep threshold, computed in fp32 as the kernels do."""
+    if p <= 0.0:
+        return 0
+    t = np.float32(p) * np.float32(65536.0) + np.float32(0.5)
+    return 65535 if t >= np.float32(65535.0) else int(t)
+
+
+def drop_scale(p: float) -> float:
+    """1 / (1 - thresh / 65536) in fp32: the factor survivors are multiplied by."""
+    return float(np.float32(1.0) / (np.float32(1.0) - np.float32(drop_thresh(p)) * np.float32(1.0 / 65536.0)))
+
+
+def drop_seed(seed: int, epoch: int = 0) -> int:
+    """The seed a launch uses when the graph-replay epoch word holds ``epoch``."""
+    return (int(seed) + int(epoch) * DROP_EPOCH_MUL) % (1 << 64)
+
+
+def drop_words(seed: int, groups: np.ndarray) -> np.ndarray:
+    """(len(groups), 4) uint32: the four words every group of 8 elements draws."""
+    g = np.asarray(groups, dtype=np.uint64)
+    s = np.uint64(int(seed) % (1 << 64))
+    lo = (g & np.uint64(0xFFFFFFFF)).astype(np.uint32) ^ np.uint32(int(s) & 0xFFFFFFFF)
+    base = (_mix32(lo) + (g >> np.uint64(32)).astype(np.uint32) * np.uint32(0x85EBCA6B)
+            + np.uint32(int(s) >> 32))
+    j = np.arange(4, dtype=np.uint32) * np.uint32(0x9E3779B9)
+    return _mix32(base[:, None] + j[None, :])
+
+
+def drop_keep(seed: int, shape, p: float, epoch: int = 0, offset: int = 0):
+    """-> (keep mask (bool ndarray of ``shape``), scale) of a row-major tensor of ``shape`` whose first element has index
+    ``offset`` in the stream, for a launch with host seed ``seed`` and epoch word ``epoch``."""
+    n = int(np.prod(shape))
+    if p <= 0.0:
+        return np.ones(shape, dtype=bool), 1.0
+    g0, g1 = offset // 8, (offset + n + 7) // 8
+    w = drop_words(drop_seed(seed, epoch), np.arange(g0, g1, dtype=np.uint64))
+    halves = np.stack([w & np.uint32(0xFFFF), w >> np.uint32(16)], axis=-1).reshape(-1)    # element order within a group
+    keep = halves[offset - 8 * g0: offset - 8 * g0 + n] >= drop_thresh(p)
+    return keep.reshape(shape), drop_scale(p)
+
+
+def drop_mask(seed: int, shape, p: float, epoch: int = 0, dtype=torch.float64) -> torch.Tensor:
+    """keep x scale as a CPU tensor: what a dropout site multiplies its input by."""
+    keep, sc = drop_keep(seed, shape, p, epoch)
+    return torch.from_numpy(keep).to(dtype) * sc
+
+
+# --------------------------------------------------------------------------
 def _ln(x, w, b, eps):
     return F.layer_norm(x, (x.shape[-1],), w.to(x.dtype), b.to(x.dtype), eps)
 
 
-def conv_module(p, x, prefix="", kernel_size=31):
+def _drop(x, masks, key):
+    """Dropout as a given multiplier (keep x 1 / keep-probability, broadcastable to x): ``masks`` None = eval mode (identity);
+    otherwise every site must have its entry, so that a test cannot silently leave one out."""
+    if masks is None:
+        return x
+    return x * masks[key].to(x.dtype)
+
+
+def conv_module(p, x, prefix="", kernel_size=31, masks=None):
     """Conmamba.py:439-449 (non-causal, non-chunked branch), GELU activation
-    (Transformer.py:746 passes branchformer_activation = nn.GELU)."""
+    (Transformer.py:746 passes branchformer_activation = nn.GELU).  ``masks``: training mode, the Dropout that closes
+    after_conv is masks[prefix + "drop"] (b, t, d)."""
     g = lambda k: p[prefix + k].to(x.dtype)
     out = _ln(x, g("layer_norm.weight"), g("layer_norm.bias"), 1e-5)            # :439
     out = out.transpose(1, 2)                                                   # :440
@@ -364,33 +441,36 @@ def conv_module(p, x, prefix="", kernel_size=31):
     out = out.transpose(1, 2)                                                   # :448
     out = _ln(out, g("after_conv.0.weight"), g("after_conv.0.bias"), 1e-5)      # :449 (LN)
     out = F.gelu(out)
-    return F.linear(out, g("after_conv.2.weight"), g("after_conv.2.bias"))
+    return _drop(F.linear(out, g("after_conv.2.weight"), g("after_conv.2.bias")), masks, prefix + "drop")
 
 
-def ffn_module(p, x, prefix):
-    """Conmamba.py:597-617: LayerNorm -> PositionalwiseFeedForward (Linear, GELU, Dropout, Linear)."""
+def ffn_module(p, x, prefix, masks=None):
+    """Conmamba.py:597-617: LayerNorm -> PositionalwiseFeedForward (Linear, GELU, Dropout, Linear) -> Dropout.  ``masks``:
+    training mode, masks[prefix + "drop1"] (b, t, d_ffn) after the GELU and masks[prefix + "drop2"] (b, t, d) after the
+    second Linear."""
     g = lambda k: p[prefix + k].to(x.dtype)
     h = _ln(x, g("0.weight"), g("0.bias"), 1e-5)
-    h = F.gelu(F.linear(h, g("1.ffn.0.weight"), g("1.ffn.0.bias")))
-    return F.linear(h, g("1.ffn.3.weight"), g("1.ffn.3.bias"))
+    h = _drop(F.gelu(F.linear(h, g("1.ffn.0.weight"), g("1.ffn.0.bias"))), masks, prefix + "drop1")
+    return _drop(F.linear(h, g("1.ffn.3.weight"), g("1.ffn.3.bias")), masks, prefix + "drop2")
 
 
-def encoder_layer(p, x, prefix="", scan=selective_scan, kernel_size=31):
-    """ConmambaEncoderLayer.forward, Conmamba.py:631-650 (eval mode: dropout off)."""
+def encoder_layer(p, x, prefix="", scan=selective_scan, kernel_size=31, masks=None):
+    """ConmambaEncoderLayer.forward, Conmamba.py:631-650 (eval mode: dropout off; ``masks``: training mode, the dropout
+    sites of both feed-forward modules and of the convolution module, keyed by their module prefix)."""
     g = lambda k: p[prefix + k].to(x.dtype)
-    x = x + 0.5 * ffn_module(p, x, prefix + "ffn_module1.")                     # :638
+    x = x + 0.5 * ffn_module(p, x, prefix + "ffn_module1.", masks)              # :638
     skip = x
     h = _ln(x, g("norm1.norm.weight"), g("norm1.norm.bias"), 1e-5)              # :641
     x = bimamba_v2(p, h, scan, prefix + "mamba.") + skip                        # :642-643
-    x = x + conv_module(p, x, prefix + "convolution_module.", kernel_size)      # :645
-    y = x + 0.5 * ffn_module(p, x, prefix + "ffn_module2.")
+    x = x + conv_module(p, x, prefix + "convolution_module.", kernel_size, masks)   # :645
+    y = x + 0.5 * ffn_module(p, x, prefix + "ffn_module2.", masks)
     return _ln(y, g("norm2.norm.weight"), g("norm2.norm.bias"), 1e-5)           # :649
 
 
-def encoder(p, x, num_layers, prefix="", scan=selective_scan, kernel_size=31):
+def encoder(p, x, num_layers, prefix="", scan=selective_scan, kernel_size=31, masks=None):
     """ConmambaEncoder.forward, Conmamba.py:716-727 (final LayerNorm eps 1e-6, :687)."""
     for i in range(num_layers):
-        x = encoder_layer(p, x, f"{prefix}layers.{i}.", scan, kernel_size)
+        x = encoder_layer(p, x, f"{prefix}layers.{i}.", scan, kernel_size, masks)
     return _ln(x, p[prefix + "norm.norm.weight"].to(x.dtype), p[prefix + "norm.norm.bias"].to(x.dtype), 1e-6)
 
 
@@ -518,11 +598,14 @@ def global_norm_stats(feats: torch.Tensor, lens: torch.Tensor):
     return torch.stack(means).mean(0), torch.stack(stds).mean(0)
 
 
-def cnn_frontend(p, feats, prefix=""):
+def cnn_frontend(p, feats, prefix="", masks=None):
     """ConvolutionFrontEnd(2 blocks, 1 layer each, channels (64, 32), k=3, stride 2 in time and frequency,
     'same' reflect padding, LayerNorm over (freq, ch), LeakyReLU(0.01)) — conmamba_large.yaml:187-194; eval
     mode.  feats (b, t, 80) -> (b, ceil(t/4), 20, 32).  Parameter names: blocks.{i}.conv.{weight,bias},
-    blocks.{i}.norm.norm.{weight,bias} (the build's naming; speechbrain's own key names are unpinned)."""
+    blocks.{i}.norm.norm.{weight,bias} (the build's naming; speechbrain's own key names are unpinned).
+    ``masks``: training mode, Dropout2d after each block's activation as masks[prefix + "blocks.{i}.drop"] (b, c), one factor
+    per (sample, channel) broadcast over time and frequency -- what the product does; its parity with speechbrain's
+    Dropout2d on the (b, t, f, c) tensor is unpinned."""
     x = feats[:, :, :, None]                                                    # b t f 1 (channels-last)
     for blk in range(2):
         w = p[f"{prefix}blocks.{blk}.conv.weight"].to(x.dtype)                  # (co, ci, 3, 3)
@@ -532,7 +615,19 @@ def cnn_frontend(p, feats, prefix=""):
         lw = p[f"{prefix}blocks.{blk}.norm.norm.weight"].to(x.dtype)
         lb = p[f"{prefix}blocks.{blk}.norm.norm.bias"].to(x.dtype)
         x = F.leaky_relu(F.layer_norm(y, tuple(y.shape[-2:]), lw, lb, 1e-5), 0.01)
+        if masks is not None:
+            x = x * masks[f"{prefix}blocks.{blk}.drop"].to(x.dtype)[:, None, None, :]
     return x
+
+
+def src_projection(p, src, prefix="Transformer.", masks=None):
+    """TransformerASR custom_src_module (TransformerASR.py:727-735, :760-773): (b, t, f, c) flattened to (b, t, f c) ->
+    Linear -> Dropout (``masks``: training mode, masks[prefix + "custom_src_module.drop"] (b, t, d))."""
+    if src.dim() == 4:
+        src = src.reshape(src.shape[0], src.shape[1], -1)
+    x = F.linear(src, p[prefix + "custom_src_module.layers.0.w.weight"].to(src.dtype),
+                 p[prefix + "custom_src_module.layers.0.w.bias"].to(src.dtype))
+    return _drop(x, masks, prefix + "custom_src_module.drop")
 
 
 def asr_encode(p, wav, wav_lens, num_layers, norm_mean, norm_std, scan=selective_scan, n_fft=512, win_ms=25):

@@ -279,3 +279,40 @@ def test_capture_failure_falls_back_to_the_eager_loop():
             assert abs(a - b) <= 2e-3 * max(1.0, abs(a)), (l_e, l_g)
     finally:
         ops.SEED_EPOCH = None
+
+
+@pytest.mark.parametrize("graph", [False, True])
+def test_nan_log_probs_skip_the_step_eager_and_graphed(graph):
+    """A micro-batch whose log-probabilities turn NaN (one ctc_lin bias element poisoned, then restored) returns a NaN loss and
+    leaves every parameter and the optimizer's step counts unchanged; the next clean micro-batch steps again.  The CTC kernel used
+    to write loss 0 for a NaN negative log-likelihood, so such a batch looked healthy."""
+    from mamba_asr_amd import ops
+    batch = _batches()[0]
+    try:
+        brain = _tiny_brain(graph, dropout=0.0)
+        brain.modules["asr"].calibrate(batch[0], batch[1])
+        brain.modules["asr"].normalize.eval()
+        for _ in range(3):                                                    # graphed: eager, capture + replay, replay
+            assert bool(torch.isfinite(brain.fit_batch(batch)))
+        if graph:
+            assert any(brain._graphs.values())
+        steps = brain.optimizer_step
+        adam = [int(s["step"]) for s in brain.optimizer.state.values() if "step" in s]
+        params = {k: p.detach().clone() for k, p in brain.modules.named_parameters()}
+        bias = brain.modules["asr"].ctc_lin.w.bias
+        with torch.no_grad():
+            keep = bias[3].clone()
+            bias[3] = float("nan")
+        loss = brain.fit_batch(batch)
+        with torch.no_grad():
+            bias[3] = keep
+        assert bool(torch.isnan(loss)), float(loss)
+        assert brain.optimizer_step == steps
+        assert [int(s["step"]) for s in brain.optimizer.state.values() if "step" in s] == adam
+        for k, p in brain.modules.named_parameters():
+            assert torch.equal(p.detach(), params[k]), k
+        assert bool(torch.isfinite(brain.fit_batch(batch)))
+        assert brain.optimizer_step == steps + 1
+        assert all(bool(torch.isfinite(p).all()) for p in brain.modules.parameters())
+    finally:
+        ops.SEED_EPOCH = None

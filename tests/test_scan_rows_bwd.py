@@ -236,10 +236,11 @@ def test_ffn_rows_node_vs_module_tree(dtype, monkeypatch):
 
 
 def _drop_masks(ops, rows, dim, p, seed):
-    """The keep decisions of csrc/cm_dropout.h for a (rows, dim) tensor, through the element-wise kernel's stored mask."""
-    z = torch.zeros(rows, dim, device=DEV, dtype=torch.bfloat16)
-    _, m = ops.bias_act_dropout_fwd(z, None, act=0, p=p, seed=seed, store_mask=True)
-    return m.bool()
+    """The keep decisions of csrc/cm_dropout.h for a (rows, dim) tensor, from the host restatement of the stream
+    (oracle.conmamba_oracle.drop_keep): no kernel under test produces them (tests/test_dropout_stream.py pins the kernels to it)."""
+    from oracle import conmamba_oracle as O
+    keep, _ = O.drop_keep(seed, (rows, dim), p)
+    return torch.from_numpy(keep).to(DEV)
 
 
 @pytest.mark.parametrize("rows,hidden", [(300, 1024), (64, 256), (1000, 2048)])
@@ -314,13 +315,23 @@ def test_ffn_bwd_fused_against_the_kernel_per_stage_chain(rows, hidden, p1, p2):
     assert torch.equal(da1 == 0, ra1 == 0) or float(((da1 == 0) != (ra1 == 0)).float().mean()) < 1e-3      # same dropout decisions
     close(dh.float(), rdh.float(), 2e-2, 1.5e-2)
     close(db1, rb1, 1e-2, 4e-3)
-    # fp64 reference of the chain on the same masks (read back through act / da1 zeros is not exact: use the kernel chain's masks)
+    # fp64 reference of the chain on the host restatement's masks (not read back through any kernel)
     m1 = _drop_masks(ops, rows, hidden, p1, s1).double() / (1 - round(p1 * 65536) / 65536.0) if p1 > 0 else 1.0
     x = pre.double()
     gp = 0.5 * (1 + torch.erf(x / 2 ** 0.5)) + x * torch.exp(-0.5 * x * x) / (2 * torch.pi) ** 0.5
     ref_da1 = (da2.double() @ w2c.double()) * m1 * gp
     close(da1.float(), ref_da1, 3e-2, 1e-2)
     close(dh.float(), ref_da1.bfloat16().double() @ w1c.double() if False else ref_da1 @ w1c.double(), 3e-2, 1.5e-2)
+    # ... and every other output: da2 / db2 on the second dropout's host mask, the recomputed activation, db1; exact zero patterns
+    m2 = _drop_masks(ops, rows, D, p2, s2).double() / (1 - round(p2 * 65536) / 65536.0) if p2 > 0 else torch.ones(rows, D, device=DEV, dtype=torch.float64)
+    ref_da2 = alpha * dout.double() * m2
+    close(da2.float(), ref_da2, 4e-3, 1e-5)
+    assert torch.equal(da2 == 0, m2 == 0)
+    m1t = m1 if p1 > 0 else torch.ones(rows, hidden, device=DEV, dtype=torch.float64)
+    assert torch.equal(da1 == 0, m1t == 0) and torch.equal((act == 0) | (m1t != 0), torch.ones_like(act, dtype=torch.bool))
+    close(act.float(), (0.5 * x * (1 + torch.erf(x / 2 ** 0.5))) * m1t, 1e-2, 4e-3)
+    close(db2, ref_da2.bfloat16().double().sum(0), 1e-3, 1e-4)
+    close(db1, ref_da1.bfloat16().double().sum(0), 2e-2, 4e-3)
 
 
 @pytest.mark.parametrize("p", [0.0, 0.15])
