@@ -19,8 +19,10 @@ def large_model():
 
 def test_utterances_are_independent_at_full_size(large_model):
     """Each utterance of a 6 x 40 s batch gives bit-identical encoder output when it is encoded alone, in another
-    position of the batch, or with the batch on 1 / 3 streams: no kernel leaks state across utterances, tile edges
-    or workgroup mappings at T = 1000 (63 ragged-tail scan blocks, 251 CNN tiles, 16 chunks)."""
+    position of the batch, or with fused.N_STREAMS forced to 1: no kernel leaks state across utterances, tile edges
+    or workgroup mappings at T = 1000 (63 ragged-tail scan blocks, 251 CNN tiles, 7 scan time chunks).  At 6 utterances the
+    default stream setting also runs one part (parts hold at least 16 utterances): the two-part joined route of the benchmark's
+    64 x 40 s batch is tested in test_bench_shapes.py."""
     from mamba_asr_amd import fused
     model, wavs, lens = large_model
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
