@@ -195,8 +195,14 @@ __device__ __forceinline__ float cm_softplus(float x) {
 // outstanding global STORES (and prefetch loads) at each barrier; kernels that barrier inside a streaming loop use this.
 __device__ __forceinline__ void cm_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// DPP helpers (full-rate cross-lane moves inside a row of 16 lanes)
+// DPP helpers (full-rate cross-lane moves inside a row of 16 lanes).  Every DPP source is settled first: pinned in a VGPR behind
+// 5 wait states (s_nop 4).  Left to itself the compiler packs two independent sums into v_pk_add_f32 / v_pk_fma_f32 and reads a
+// half of the pair by DPP only two wait states later; on gfx950 lanes 48-63 then picked up a stale value (a previous workgroup's
+// register) once a launch had more workgroups than the chip holds at once -- cm_ffn_fused's rows 7 mod 8 changed from run to run
+// at 32000 rows.  tests/test_isa_dpp_hazard.py checks the compiled library for any DPP read closer than 5 wait states behind a
+// packed write.
 template <int CTRL> __device__ __forceinline__ float cm_dpp(float v) {
+    asm volatile("s_nop 4" : "+v"(v));
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
 }
 #define CM_DPP_QUAD(a, b, c, d) ((a) | ((b) << 2) | ((c) << 4) | ((d) << 6))

@@ -38,23 +38,6 @@ constexpr int PF = 4;         // weight-fragment ring depth (k-steps in flight)
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// cm_group_sum<16> for the LayerNorm statistics of phase 0, with every DPP source settled first: the value is pinned in a VGPR
-// behind 5 wait states (s_nop 4).  Left to itself the compiler packs the sums of two tokens into v_pk_fma_f32 / v_pk_add_f32 and
-// reads the high half of the pair by DPP two instructions later; on gfx950 lanes 48-63 then picked up a stale value -- rows 7 mod 8
-// of a tile (odd round, lane row 3) changed from run to run once a launch had more workgroups than the chip holds at once (the
-// stale value was a previous workgroup's register), i.e. at the benchmark's 32000 / 64000 rows.
-__device__ __forceinline__ float group_sum16_settled(float v) {
-    asm volatile("s_nop 4" : "+v"(v));
-    v += cm_dpp<CM_DPP_QUAD(1, 0, 3, 2)>(v);
-    asm volatile("s_nop 4" : "+v"(v));
-    v += cm_dpp<CM_DPP_QUAD(2, 3, 0, 1)>(v);
-    asm volatile("s_nop 4" : "+v"(v));
-    v += cm_dpp<CM_DPP_ROW_HALF_MIRROR>(v);
-    asm volatile("s_nop 4" : "+v"(v));
-    v += cm_dpp<CM_DPP_ROW_MIRROR>(v);
-    return v;
-}
-
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 __device__ __forceinline__ uint32_t pack2(float a, float b) {         // one v_cvt_pk_bf16_f32
@@ -163,14 +146,14 @@ __global__ __launch_bounds__(NT, 2) void ffn_fused_kernel(const cm_ffn_args p) {
             float s = 0.f;
 #pragma unroll
             for (int i = 0; i < 4; ++i) s += (v[rd][i].x + v[rd][i].y) + (v[rd][i].z + v[rd][i].w);
-            const float mean = group_sum16_settled(s) * (1.f / D);
+            const float mean = cm_group_sum<16>(s) * (1.f / D);
             float q = 0.f;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 v[rd][i].x -= mean; v[rd][i].y -= mean; v[rd][i].z -= mean; v[rd][i].w -= mean;
                 q = fmaf(v[rd][i].x, v[rd][i].x, fmaf(v[rd][i].y, v[rd][i].y, fmaf(v[rd][i].z, v[rd][i].z, fmaf(v[rd][i].w, v[rd][i].w, q))));
             }
-            const float rstd = rsqrtf(group_sum16_settled(q) * (1.f / D) + p.pre_eps);
+            const float rstd = rsqrtf(cm_group_sum<16>(q) * (1.f / D) + p.pre_eps);
             if constexpr (TRAIN) {
                 const int trow = t0 + wv * 16 + rd * 4 + lq;
                 if (p.stats_out && l15 == 0 && trow < M) p.stats_out[trow] = mean, p.stats_out[(int64_t)M + trow] = rstd;

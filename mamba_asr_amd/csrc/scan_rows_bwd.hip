@@ -344,13 +344,14 @@ __device__ __forceinline__ void scan_rows_bwd(const cm_scan_cl_bwd_args &p, cons
                 // sums over the 16 states of the channel (in-lane, then the quad: 2 DPP adds each) and over the 4 channels of the row
                 // (row_shr:8, row_shr:4: valid in lanes 12..15), as ONE block of v_add_f32 with the DPP operand: through the
                 // builtin the compiler emitted v_mov_b32_dpp + packed adds + hazard nops (704 moves, 175 nops in the kernel), 6-8
-                // issue cycles per sum instead of 4.  One s_nop covers the VALU-write -> DPP-read hazard of every input; later
-                // reads are >= 2 instructions behind their writes.
+                // issue cycles per sum instead of 4.  One s_nop 4 puts every input 5 wait states behind its last write, however the
+                // compiler schedules the packed products that feed it (cm_dpp in cm_common.h); later reads are >= 2 instructions
+                // behind their writes.
                 float sbs = sb.x + sb.y, sas = sa.x + sa.y;
                 float b0 = aB01.x, b1 = aB01.y, b2 = aB23.x, b3 = aB23.y, c0_ = aC01.x, c1 = aC01.y, c2 = aC23.x, c3 = aC23.y;
 #if !defined(CM_BWD_ABL) || CM_BWD_ABL != 1
 #define CM_DPP_ADD(r, ctl) "v_add_f32_dpp " r ", " r ", " r " " ctl " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                asm volatile("s_nop 1\n\t"
+                asm volatile("s_nop 4\n\t"
                              CM_DPP_ADD("%0", "quad_perm:[1,0,3,2]") CM_DPP_ADD("%1", "quad_perm:[1,0,3,2]")
                              CM_DPP_ADD("%2", "row_shr:8") CM_DPP_ADD("%3", "row_shr:8") CM_DPP_ADD("%4", "row_shr:8") CM_DPP_ADD("%5", "row_shr:8")
                              CM_DPP_ADD("%6", "row_shr:8") CM_DPP_ADD("%7", "row_shr:8") CM_DPP_ADD("%8", "row_shr:8") CM_DPP_ADD("%9", "row_shr:8")
