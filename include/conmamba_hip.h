@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CM_ABI_VERSION 10
+#define CM_ABI_VERSION 11
 
 /* error codes */
 #define CM_OK            0
@@ -389,6 +389,40 @@ typedef struct cm_ctc_args {
 
 int64_t cm_ctc_workspace_floats(int32_t batch, int32_t T, int32_t S);
 int cm_ctc_loss(const cm_ctc_args *args);
+
+/* LM-free CTC beam search (csrc/ctc_beam.hip; replaces speechbrain.decoders.ctc.CTCBeamSearcher, reference train_CTC.py:309-310,
+ * 411-414 and 1155-1161).  The algorithm (mamba_asr_amd/ctc_decode.py): per processed frame select tokens, extend
+ * every beam, merge equal (text, partial word, last token), prune by beam_prune_logp, rank, keep beam_size, optionally prune the
+ * history; finish by merging equal texts.  Scores are float64.  One workgroup per utterance; bit-reproducible and independent of
+ * batch composition.  log_probs (batch, T, V) fp32 or bf16 with unit vocabulary stride; lengths[b] = frames to decode (<= T).
+ * Token classes and hashes come from the host: tok_class[v] = 1 for a word-start piece, 0 otherwise (blank's entry is ignored);
+ * tok_hash[v][k] = H_k(clean piece) and tok_pow[v][k] = base_k^len(clean piece), H_k(s) = sum_i (cp_i + 1) base_k^(n-1-i) mod
+ * 2^61 - 1 over the piece's code points.  hash_sep is the separator symbol (a value above every code point + 1).
+ * Outputs per utterance: num_hyps[b] hypotheses (<= topk), for each its text-changing tokens tokens[b][h][0 .. token_len[b][h])
+ * and its score; bad_frame[b] = first frame < lengths[b] holding a NaN (then num_hyps[b] = 0), else -1.
+ * cm_ctc_beam_search validates its arguments on the host before any launch. */
+typedef struct cm_ctc_beam_args {
+    int32_t batch, T, V, dtype;               /* dtype: CM_F32 or CM_BF16; V <= 4096                           */
+    int64_t lp_bs, lp_ts;                     /* log_probs element strides of batch and time                    */
+    const void *log_probs;
+    const int32_t *lengths;                   /* (batch) frames to decode                                       */
+    const int32_t *tok_class;                 /* (V)                                                            */
+    const uint64_t *tok_hash, *tok_pow;       /* (V, 2)                                                         */
+    uint64_t hash_base[2], hash_sep;
+    int32_t blank, beam_size, topk, prune_history;   /* beam_size <= 256                                        */
+    double beam_prune_logp, token_prune_min_logp, blank_skip_threshold;   /* skip frame if lp[blank] > log(threshold) */
+    double blank_skip_log;                    /* set by the library                                             */
+    int32_t *tokens;                          /* (batch, topk, T)                                               */
+    int32_t *token_len;                       /* (batch, topk)                                                  */
+    double *scores;                           /* (batch, topk)                                                  */
+    int32_t *num_hyps, *bad_frame;            /* (batch)                                                        */
+    void *workspace;                          /* cm_ctc_beam_workspace_bytes() bytes                            */
+    int64_t workspace_bytes;
+    void *stream;
+} cm_ctc_beam_args;
+
+int64_t cm_ctc_beam_workspace_bytes(const cm_ctc_beam_args *args);
+int cm_ctc_beam_search(const cm_ctc_beam_args *args);
 
 /* Element-wise stages of a feed-forward / convolution module's training step on (rows, dim) tensors (csrc/ffn_train.hip; the
  * reference leaves them to torch: reference modules/Conmamba.py:597-617):

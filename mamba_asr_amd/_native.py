@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("CM_LIB_PATH") or os.path.join(_HERE, "lib", "libconma
 
 CM_F32, CM_BF16, CM_F16 = 0, 1, 2
 CM_SCAN_CHUNK = 64
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 i32, i64, vp, fp = C.c_int32, C.c_int64, C.c_void_p, C.c_void_p
 
@@ -288,6 +288,19 @@ class SpecDropArgs(C.Structure):
     ]
 
 
+class CtcBeamArgs(C.Structure):
+    _fields_ = [
+        ("batch", i32), ("T", i32), ("V", i32), ("dtype", i32), ("lp_bs", i64), ("lp_ts", i64),
+        ("log_probs", vp), ("lengths", vp), ("tok_class", vp), ("tok_hash", vp), ("tok_pow", vp),
+        ("hash_base", C.c_uint64 * 2), ("hash_sep", C.c_uint64),
+        ("blank", i32), ("beam_size", i32), ("topk", i32), ("prune_history", i32),
+        ("beam_prune_logp", C.c_double), ("token_prune_min_logp", C.c_double), ("blank_skip_threshold", C.c_double),
+        ("blank_skip_log", C.c_double),
+        ("tokens", vp), ("token_len", vp), ("scores", vp), ("num_hyps", vp), ("bad_frame", vp),
+        ("workspace", vp), ("workspace_bytes", i64), ("stream", vp),
+    ]
+
+
 # every symbol include/conmamba_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("cm_abi_version", C.c_int, []),
@@ -315,6 +328,8 @@ SYMBOLS = [
     ("cm_sum_leading", C.c_int, [vp, vp, i32, i64, i32, i32, vp]),
     ("cm_ctc_workspace_floats", C.c_int64, [i32, i32, i32]),
     ("cm_ctc_loss", C.c_int, [C.POINTER(CtcArgs)]),
+    ("cm_ctc_beam_workspace_bytes", C.c_int64, [C.POINTER(CtcBeamArgs)]),
+    ("cm_ctc_beam_search", C.c_int, [C.POINTER(CtcBeamArgs)]),
     ("cm_bias_act_dropout_bwd_workspace_floats", C.c_int64, [i64, i32]),
     ("cm_bias_act_dropout_fwd", C.c_int, [C.POINTER(FfnElemArgs)]),
     ("cm_bias_act_dropout_bwd", C.c_int, [C.POINTER(FfnElemArgs)]),

@@ -1,0 +1,178 @@
+"""LM-free CTC beam search on the GPU: the drop-in for speechbrain.decoders.ctc.CTCBeamSearcher in the CTC recipe's TEST stage
+(reference train_CTC.py:1155-1161 builds it from hparams/CTC/conmamba_large.yaml:232-237; compute_forward calls it at :309-310;
+compute_objectives reads hyp[0].text at :411-414).  The search itself is the HIP kernel behind ops.ctc_beam_search
+(csrc/ctc_beam.hip); this module classifies the vocabulary once, maps relative lengths to frame counts and composes texts.
+
+The contract (speechbrain's searcher without an LM, itself a port of pyctcdecode, as restated here; parity with speechbrain is
+not pinned because speechbrain is not installable):
+
+State.  A beam is (text, partial, last, score): completed words joined by single spaces, the word being built, the last token
+index (initially none) and a float64 log score (initially 0).  Start with one beam ("", "", none, 0).
+
+Token classes.  blank = blank_index.  If any piece starts with spm_token the vocabulary is SentencePiece and every piece that
+starts with it is word-start with clean part piece[1:]; otherwise the piece equal to space_token is word-start with an empty
+clean part.  Every other piece is a char whose clean part is the whole piece (any length, e.g. "<unk>").
+
+Per frame t < n_b.  Skip the frame if logp[blank] > log(blank_skip_threshold) (never under the default 1.0).  Otherwise:
+  1. select {v : logp[v] > token_prune_min_logp} plus the first argmax, in ascending index order;
+  2. for each selected token (outer) and each beam in rank order (inner) make a candidate with score + logp[v] and last = v:
+     blank or v == last leave text and partial unchanged; word-start: text = join(text, partial), partial = clean(v);
+     char: partial += clean(v);  join(a, b) = a if b == "" else b if a == "" else a + " " + b;
+  3. merge candidates with equal (text, partial, last): the survivor sits at the earliest candidate's position and its score
+     is a left fold of logaddexp in candidate order, logaddexp(a, b) = max + log1p(exp(-|a - b|)) (-inf when both are -inf);
+  4. drop beams below max + beam_prune_logp;  5. rank by score descending, ties by earliest candidate, keep beam_size;
+  6. if prune_history, keep only the first beam per (last word of text, partial, last).
+Finish: text = join(text, partial), partial = ""; merge by text (same fold); prune by beam_prune_logp; rank; the first topk are
+returned as CTCHypothesis(text, None, score, score, None).
+
+Choices recorded where speechbrain could not be checked: n_b = round(wav_lens[b] * T) (dataio.ctc_greedy_decode's rule;
+speechbrain may truncate); the exact blank-skip comparison; the loop order over selected tokens (speechbrain iterates a Python
+set: only ties and rounding can differ).  n_b = 0 gives the single hypothesis "" with score 0.  NaN in a decoded frame raises
+ValueError naming the utterance.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import List, Optional, Sequence
+
+import torch
+
+from . import ops
+
+P61 = (1 << 61) - 1
+HASH_BASE = (0x1D2C3B4A59687F11 % P61, 0x0F1E2D3C4B5A6979 % P61)   # two fixed bases of the polynomial hashes mod 2^61 - 1
+HASH_SEP = 0x110001                                                 # word separator: above every code point + 1
+BLANK, CHAR, WORD_START = -1, 0, 1
+
+
+@dataclass
+class CTCHypothesis:
+    """One decoded hypothesis, with the fields of speechbrain.decoders.ctc.CTCHypothesis."""
+    text: str
+    last_lm_state: None = None
+    score: float = 0.0
+    lm_score: float = 0.0
+    text_frames: Optional[list] = None
+
+
+def piece_hash(s: str):
+    """(H_k(s), base_k^len(s)) mod 2^61 - 1 for both bases, H_k(s) = sum_i (ord(s_i) + 1) base_k^(n-1-i)."""
+    out_h, out_p = [], []
+    for base in HASH_BASE:
+        h, pw = 0, 1
+        for ch in s:
+            h = (h * base + ord(ch) + 1) % P61
+            pw = pw * base % P61
+        out_h.append(h)
+        out_p.append(pw)
+    return out_h, out_p
+
+
+def _join(a: str, b: str) -> str:
+    return a if not b else (b if not a else a + " " + b)
+
+
+class CTCBeamSearcher:
+    """CTC beam search without a language model, on the GPU (constructor keywords of speechbrain's CTCBeamSearcher).
+
+    __call__(log_probs (batch, T, V) on the GPU, wav_lens (batch) relative lengths or None) -> List[List[CTCHypothesis]]
+    with at most topk hypotheses per utterance, best first.  There is no host implementation: CPU tensors raise."""
+
+    def __init__(self, blank_index: int, vocab_list: Sequence[str], space_token: str = " ", spm_token: str = "▁",
+                 kenlm_model_path: Optional[str] = None, unigrams: Optional[List[str]] = None, alpha: float = 0.5,
+                 beta: float = 1.5, unk_score_offset: float = -10.0, score_boundary: bool = True, beam_size: int = 100,
+                 beam_prune_logp: float = -10.0, token_prune_min_logp: float = -5.0, prune_history: bool = True,
+                 blank_skip_threshold: float = 1.0, topk: int = 1):
+        if kenlm_model_path is not None:
+            raise NotImplementedError("CTCBeamSearcher: language-model fusion (kenlm_model_path) is not supported")
+        vocab = list(vocab_list)
+        if len(set(vocab)) != len(vocab):
+            dup = sorted({p for p in vocab if vocab.count(p) > 1})
+            raise ValueError(f"CTCBeamSearcher: duplicate pieces in vocab_list: {dup}")
+        if not 0 <= blank_index < len(vocab):
+            raise ValueError(f"CTCBeamSearcher: blank_index {blank_index} outside a vocabulary of {len(vocab)}")
+        if not 1 <= beam_size <= 256:
+            raise ValueError(f"CTCBeamSearcher: beam_size {beam_size} not in [1, 256]")
+        if topk < 1:
+            raise ValueError(f"CTCBeamSearcher: topk {topk} < 1")
+        if not blank_skip_threshold > 0:
+            raise ValueError("CTCBeamSearcher: blank_skip_threshold must be > 0")
+        self.blank_index, self.vocab_list = int(blank_index), vocab
+        self.space_token, self.spm_token = space_token, spm_token
+        self.beam_size, self.topk, self.prune_history = int(beam_size), int(topk), bool(prune_history)
+        self.beam_prune_logp, self.token_prune_min_logp = float(beam_prune_logp), float(token_prune_min_logp)
+        self.blank_skip_threshold = float(blank_skip_threshold)
+        self.is_spm = any(p.startswith(spm_token) for p in vocab)
+        self.classes, self.clean = [], []
+        for v, p in enumerate(vocab):
+            if v == self.blank_index:
+                cls, clean = BLANK, ""
+            elif self.is_spm and p.startswith(spm_token):
+                cls, clean = WORD_START, p[len(spm_token):]
+            elif not self.is_spm and p == space_token:
+                cls, clean = WORD_START, ""
+            else:
+                cls, clean = CHAR, p
+            self.classes.append(cls)
+            self.clean.append(clean)
+        hashes = [piece_hash(c) for c in self.clean]
+        self.tok_class = torch.tensor([1 if c == WORD_START else 0 for c in self.classes], dtype=torch.int32)
+        self.tok_hash = torch.tensor([h for h, _ in hashes], dtype=torch.int64)
+        self.tok_pow = torch.tensor([p for _, p in hashes], dtype=torch.int64)
+        self._dev_tables = {}
+
+    def compose(self, tokens: Sequence[int]) -> str:
+        """Text of a sequence of text-changing tokens, by the class rules."""
+        text, partial = "", ""
+        for v in tokens:
+            if self.classes[v] == WORD_START:
+                text, partial = _join(text, partial), self.clean[v]
+            elif self.classes[v] == CHAR:
+                partial += self.clean[v]
+        return _join(text, partial)
+
+    def _tables(self, device):
+        key = str(device)
+        if key not in self._dev_tables:
+            self._dev_tables[key] = tuple(t.to(device) for t in (self.tok_class, self.tok_hash, self.tok_pow))
+        return self._dev_tables[key]
+
+    def frame_counts(self, steps: int, wav_lens: Optional[torch.Tensor], batch: int) -> List[int]:
+        if wav_lens is None:
+            return [steps] * batch
+        return [min(max(int(round(rel * steps)), 0), steps) for rel in wav_lens.detach().cpu().tolist()]
+
+    def __call__(self, log_probs: torch.Tensor, wav_lens: Optional[torch.Tensor] = None) -> List[List[CTCHypothesis]]:
+        if not log_probs.is_cuda:
+            raise RuntimeError("CTCBeamSearcher runs on the GPU only (got a CPU tensor): move log_probs to the GPU")
+        if log_probs.dim() != 3 or log_probs.shape[2] != len(self.vocab_list):
+            raise ValueError(f"CTCBeamSearcher: log_probs must be (batch, T, {len(self.vocab_list)}), got {tuple(log_probs.shape)}")
+        b, steps, _ = log_probs.shape
+        counts = self.frame_counts(steps, wav_lens, b)
+        if steps == 0:
+            return [[CTCHypothesis("", None, 0.0, 0.0, None)] for _ in range(b)]
+        lengths = torch.tensor(counts, dtype=torch.int32).to(log_probs.device)
+        tc, th, tp = self._tables(log_probs.device)
+        tokens, token_len, scores, num_hyps, bad = ops.ctc_beam_search(
+            log_probs, lengths, tc, th, tp, HASH_BASE, HASH_SEP, blank=self.blank_index, beam_size=self.beam_size,
+            topk=self.topk, prune_history=self.prune_history, beam_prune_logp=self.beam_prune_logp,
+            token_prune_min_logp=self.token_prune_min_logp, blank_skip_threshold=self.blank_skip_threshold)
+        bad, num_hyps = bad.cpu().tolist(), num_hyps.cpu().tolist()
+        for u, f in enumerate(bad):
+            if f >= 0:
+                raise ValueError(f"CTCBeamSearcher: log_probs of utterance {u} hold NaN at frame {f}")
+        token_len, scores = token_len.cpu().tolist(), scores.cpu().tolist()
+        lmax = max((token_len[u][h] for u in range(b) for h in range(num_hyps[u])), default=0)
+        tok = tokens[:, :, :lmax].cpu().tolist()
+        out = []
+        for u in range(b):
+            hyps = []
+            for h in range(num_hyps[u]):
+                s = scores[u][h]
+                hyps.append(CTCHypothesis(self.compose(tok[u][h][:token_len[u][h]]), None, s, s, None))
+            out.append(hyps)
+        return out
+
+    def decode_beams(self, log_probs, wav_lens=None, lm_start_state=None):
+        """speechbrain's name for the same call."""
+        return self(log_probs, wav_lens)

@@ -797,6 +797,45 @@ def ctc_loss_grad(log_probs, targets, input_lengths, target_lengths, blank=0):
     return nll, grad
 
 
+def ctc_beam_search(log_probs, lengths, tok_class, tok_hash, tok_pow, hash_base, hash_sep, blank=0, beam_size=100, topk=1,
+                    prune_history=False, beam_prune_logp=-10.0, token_prune_min_logp=-5.0, blank_skip_threshold=1.0):
+    """LM-free CTC beam search (cm_ctc_beam_search).  log_probs (batch, T, V) fp32 / bf16, lengths (batch) frames to decode;
+    tok_class (V) int32, tok_hash / tok_pow (V, 2) int64 holding the unsigned hash tables (mamba_asr_amd.ctc_decode builds them).
+    -> (tokens (batch, topk, T) int32, token_len (batch, topk) int32, scores (batch, topk) fp64, num_hyps (batch) int32,
+    bad_frame (batch) int32): hypothesis h < num_hyps[b] of utterance b is its text-changing tokens tokens[b, h, :token_len[b, h]]."""
+    _dev_check(log_probs, lengths, tok_class, tok_hash, tok_pow)
+    if log_probs.dtype not in (torch.float32, torch.bfloat16):
+        log_probs = log_probs.float()
+    lp = log_probs.detach()
+    if lp.stride(2) != 1:
+        lp = lp.contiguous()
+    b, t, v = lp.shape
+    dev = lp.device
+    ln = lengths.detach().to(device=dev, dtype=torch.int32).contiguous()
+    tc = tok_class.detach().to(device=dev, dtype=torch.int32).contiguous()
+    th = tok_hash.detach().to(device=dev, dtype=torch.int64).contiguous()
+    tp = tok_pow.detach().to(device=dev, dtype=torch.int64).contiguous()
+    tokens = torch.empty((b, topk, t), dtype=torch.int32, device=dev)
+    token_len = torch.zeros((b, topk), dtype=torch.int32, device=dev)
+    scores = torch.zeros((b, topk), dtype=torch.float64, device=dev)
+    num_hyps = torch.empty((b,), dtype=torch.int32, device=dev)
+    bad_frame = torch.empty((b,), dtype=torch.int32, device=dev)
+    a = N.CtcBeamArgs()
+    a.batch, a.T, a.V, a.dtype = b, t, v, _DT[lp.dtype]
+    a.lp_bs, a.lp_ts = lp.stride(0), lp.stride(1)
+    a.log_probs, a.lengths, a.tok_class, a.tok_hash, a.tok_pow = _ptr(lp), _ptr(ln), _ptr(tc), _ptr(th), _ptr(tp)
+    a.hash_base[0], a.hash_base[1], a.hash_sep = int(hash_base[0]), int(hash_base[1]), int(hash_sep)
+    a.blank, a.beam_size, a.topk, a.prune_history = int(blank), int(beam_size), int(topk), int(bool(prune_history))
+    a.beam_prune_logp, a.token_prune_min_logp = float(beam_prune_logp), float(token_prune_min_logp)
+    a.blank_skip_threshold = float(blank_skip_threshold)
+    nws = int(N.lib().cm_ctc_beam_workspace_bytes(ct.byref(a)))
+    ws = torch.empty((max(nws, 1),), dtype=torch.uint8, device=dev)
+    a.tokens, a.token_len, a.scores, a.num_hyps, a.bad_frame = _ptr(tokens), _ptr(token_len), _ptr(scores), _ptr(num_hyps), _ptr(bad_frame)
+    a.workspace, a.workspace_bytes, a.stream = _ptr(ws), nws, _stream()
+    _launch("cm_ctc_beam_search", N.lib().cm_ctc_beam_search, a, units=b * t)
+    return tokens, token_len, scores, num_hyps, bad_frame
+
+
 class CtcLossFn(torch.autograd.Function):
     """sum over the batch of the per-utterance CTC negative log-likelihoods (zero_infinity), gradient from the same call."""
 
