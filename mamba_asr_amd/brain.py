@@ -49,7 +49,7 @@ class Brain:
         # padded length would capture forever: at most this many signatures stay captured, the least recently used one goes
         self.graph_max_shapes = int(run_opts.get("graph_max_shapes", 16))
         self._graph_pool = None
-        self._graph_generation = None              # ops.CACHE_GENERATION when the newest graph was captured
+        self._graph_generation = None              # weight_cache.CACHE_GENERATION when the newest graph was captured
         self._caches_epoch = None                  # _weights_epoch() the in-place weight caches were last refreshed at
         self._epoch_params = None
 
@@ -130,16 +130,16 @@ class Brain:
         What makes a replay a fresh training step: dropout seeds are offset by a device word the graph's first node
         increments (ops.SEED_EPOCH), torch's own generator is graph-registered by torch.cuda.graph, and the weight-derived
         operands (bf16 copies, packed images, the mixers' derived tensors) live in storage that is refreshed IN PLACE
-        (ops.CACHE_INPLACE).  Two variants are captured per signature: "fresh" contains the kernels that refresh those operands
+        (weight_cache.CACHE_INPLACE).  Two variants are captured per signature: "fresh" contains the kernels that refresh those operands
         and is replayed for the first micro-batch after an optimizer step; "warm" reads them as they are (the other micro-batches
         of an accumulation window: 2.5 ms of small kernels fewer per 32 x 40 s micro-batch).
         The gradient exchange (world > 1) is NOT captured: it runs after the replay, un-overlapped, through reducer.finish()."""
-        from . import ops
+        from . import ops, weight_cache
         if self.reducer is None:
             raise RuntimeError("graph_steps needs the flat gradient buckets (CM_FLAT_GRADS=1 or a GradAllReducer)")
-        ops.CACHE_INPLACE = True
-        if self._graph_generation != ops.CACHE_GENERATION and any(self._graphs.values()):
-            # a weight cache got new storage since the last capture (ops.invalidate_caches after a load_state_dict, a cache created by
+        weight_cache.CACHE_INPLACE = True
+        if self._graph_generation != weight_cache.CACHE_GENERATION and any(self._graphs.values()):
+            # a weight cache got new storage since the last capture (weight_cache.invalidate_caches after a load_state_dict, a cache created by
             # another code path): the captured launches may read addresses the caches no longer own -- start over
             self._graphs = {}
             self._graph_pool = None                                        # the pool dies with its last graph
@@ -173,7 +173,7 @@ class Brain:
                 before = set(self.reducer._touched)
                 graph = torch.cuda.CUDAGraph()
                 try:
-                    with (ops.forced_refresh() if variant == "fresh" else _null()) as log:
+                    with (weight_cache.forced_refresh() if variant == "fresh" else _null()) as log:
                         # thread_local: a process group's watchdog thread polls its events with hipEventQuery, which a capture in the
                         # default "global" mode turns into an error in THAT thread (and the process dies with it)
                         with torch.cuda.graph(graph, pool=self._graph_pool, capture_error_mode="thread_local"):
@@ -189,12 +189,12 @@ class Brain:
                     torch.cuda.synchronize()
                     self.reducer.discard_pending()
                     self.reducer._touched = before
-                    ops.invalidate_caches(self.modules)                    # entries created inside the failed capture point into its pool
+                    weight_cache.invalidate_caches(self.modules)           # entries created inside the failed capture point into its pool
                     self.graph_steps, self._graphs, self._graph_pool = False, {}, None
                     return self.fit_batch(batch)
                 if self._graph_pool is None:
                     self._graph_pool = graph.pool()
-                self._graph_generation = ops.CACHE_GENERATION              # entries created inside the capture are this graph's own
+                self._graph_generation = weight_cache.CACHE_GENERATION     # entries created inside the capture are this graph's own
                 g = self._graphs[key][variant] = SimpleNamespace(graph=graph, static=static, outputs=outputs, loss=loss,
                                                                   touched=set(self.reducer._touched),
                                                                   entries=list(log) if variant == "fresh" else [])
@@ -205,7 +205,7 @@ class Brain:
                         dst.copy_(src)
             g.graph.replay()
             if variant == "fresh":
-                ops.rekey_caches(g.entries)                                # the replay refreshed exactly these entries
+                weight_cache.rekey_caches(g.entries)                       # the replay refreshed exactly these entries
                 self._caches_epoch = self._weights_epoch()
             self.reducer._touched |= g.touched
             outputs, loss = g.outputs, g.loss.clone()

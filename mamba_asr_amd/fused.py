@@ -20,7 +20,7 @@ from typing import Dict, Optional
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, weight_cache
 
 
 class _LayerCache:
@@ -28,7 +28,6 @@ class _LayerCache:
 
     def __init__(self, layer, dtype):
         self.dtype = dtype
-        self.version = self._ver(layer)
         c = lambda t: t.detach().to(dtype).contiguous()
         f = lambda t: None if t is None else t.detach().float().contiguous()
         ffn = lambda m: dict(ln=(f(m[0].weight), f(m[0].bias), m[0].eps), w1=c(m[1].ffn[0].weight), b1=c(m[1].ffn[0].bias),
@@ -66,11 +65,7 @@ class _LayerCache:
                                   D=f(getattr(m, "D_b" if sfx else "D"))))
         cm = layer.convolution_module
         # both directions' x_proj as ONE GEMM over [u_fwd | u_bwd]: block-diagonal (2*(R+2N), 2E) weight
-        P = self.dt_rank + 2 * self.d_state
-        xbd = torch.zeros(2 * P, 2 * m.d_inner, dtype=dtype, device=m.x_proj.weight.device)
-        xbd[:P, :m.d_inner] = m.x_proj.weight.detach().to(dtype)
-        xbd[P:, m.d_inner:] = m.x_proj_b.weight.detach().to(dtype)
-        self.x_proj_bd = xbd
+        self.x_proj_bd = torch.block_diag(m.x_proj.weight.detach().to(dtype), m.x_proj_b.weight.detach().to(dtype))
         # row-major variant for cm_scan_cl_fwd's xdbl mode: output columns per direction are
         # [dt (zero padded to 16, or to 32 in bf16 when 16 < dt_rank <= 32) | B (16) | C (16)], so the scan reads the
         # GEMM's rows as written
@@ -78,19 +73,13 @@ class _LayerCache:
         self.rows_mode = (R <= 16 or (R <= 32 and dtype == torch.bfloat16)) and N == 16 and m.d_inner % 8 == 0
         if self.rows_mode:
             pad = ops.rows_dt_pad(R)
-            RW = self.row_width = pad + 32
-            xr = torch.zeros(2 * RW, 2 * m.d_inner, dtype=dtype, device=m.x_proj.weight.device)
-            for i, xp in enumerate((m.x_proj, m.x_proj_b)):
-                wsrc = xp.weight.detach().to(dtype)
-                cols = slice(i * m.d_inner, (i + 1) * m.d_inner)
-                xr[RW * i:RW * i + R, cols] = wsrc[:R]
-                xr[RW * i + pad:RW * (i + 1), cols] = wsrc[R:]
-            self.x_proj_rows = xr
+            self.row_width = pad + 32
+            rows = [ops.xproj_rows(xp.weight, R, pad, dtype) for xp in (m.x_proj, m.x_proj_b)]
+            self.x_proj_rows = torch.block_diag(*rows)            # (2 RW, 2 E)
             # per-direction (RW, E) images for cm_conv_xproj (conv + x_proj in one kernel, bf16)
             self.wx_packed = None
-            if dtype == torch.bfloat16 and m.d_inner % 32 == 0 and m.d_inner <= 2048 and xr.is_cuda and m.d_conv == 4:
-                self.wx_packed = [ops.PackedWeight(xr[RW * i:RW * (i + 1), i * m.d_inner:(i + 1) * m.d_inner].contiguous())
-                                  for i in range(2)]
+            if dtype == torch.bfloat16 and m.d_inner % 32 == 0 and m.d_inner <= 2048 and rows[0].is_cuda and m.d_conv == 4:
+                self.wx_packed = [ops.PackedWeight(r) for r in rows]
             for d_, dtp in zip(self.dirs, (m.dt_proj, m.dt_proj_b)):
                 d_["dt_w16"] = ops.pad_dt_weight(dtp.weight.detach().to(dtype))      # dtype-rounded like the reference's GEMM operand
         self.cm_ln = (f(cm.layer_norm.weight), f(cm.layer_norm.bias), cm.layer_norm.eps)
@@ -110,21 +99,18 @@ class _LayerCache:
             self.lin_packed = ops.PackedWeight(self.lin_w)
         self.kernel_size = cm.kernel_size
 
-    @staticmethod
-    def _ver(layer):
-        # (version, storage) per parameter: see ops.cast_cached / ops.invalidate_caches
-        return hash(tuple((p._version, p.data_ptr()) for p in layer.parameters()))
 
-    def stale(self, layer, dtype):
-        return dtype != self.dtype or self._ver(layer) != self.version
+def _params_key(dtype, *modules):
+    # (version, storage) per parameter: see ops.cast_cached / weight_cache.invalidate_caches
+    return (dtype,) + tuple((p._version, p.data_ptr()) for m in modules for p in m.parameters())
+
+
+# inference bundles: no captured training graph reads them
+_LAYER = weight_cache.Kind("_cm_fused_cache", graphs_read=False, build=_LayerCache)
 
 
 def _cache(layer, dtype) -> _LayerCache:
-    c = getattr(layer, "_cm_fused_cache", None)
-    if c is None or c.stale(layer, dtype):
-        c = _LayerCache(layer, dtype)
-        layer._cm_fused_cache = c
-    return c
+    return _LAYER.lookup(layer, _params_key(dtype, layer), dtype)
 
 
 def supports(layer) -> bool:
@@ -498,21 +484,22 @@ def encoder_forward(encoder, src, dtype: Optional[torch.dtype] = None, streams: 
 USE_CNN_FRONT = os.environ.get("CM_CNN_FRONT", "1") == "1"
 
 
+def _frontend_bundle(model, dtype):
+    b0, b1 = model.CNN.blocks
+    lin = model.Transformer.custom_src_module.layers[0].w
+    return dict(w2=b1.conv.weight.detach().to(dtype).contiguous(memory_format=torch.channels_last),
+                b2=b1.conv.bias.detach().to(dtype), b2f=b1.conv.bias.detach().float().contiguous(),
+                w2_ohwi=b1.conv.weight.detach().to(dtype).permute(0, 2, 3, 1).contiguous(),
+                ln2=(b1.norm.norm.weight.detach().float().reshape(-1).contiguous(),
+                     b1.norm.norm.bias.detach().float().reshape(-1).contiguous(), b1.norm.norm.eps),
+                lin_w=lin.weight.detach().to(dtype).contiguous(), lin_b=lin.bias.detach().to(dtype))
+
+
+_FRONTEND = weight_cache.Kind("_cm_frontend_cache", graphs_read=False, build=_frontend_bundle)
+
+
 def _frontend_cache(model, dtype):
-    c = getattr(model, "_cm_frontend_cache", None)
-    ver = hash(tuple((p._version, p.data_ptr()) for m in (model.CNN, model.Transformer.custom_src_module) for p in m.parameters()))
-    if c is None or c["dtype"] != dtype or c["ver"] != ver:
-        b0, b1 = model.CNN.blocks
-        lin = model.Transformer.custom_src_module.layers[0].w
-        c = dict(dtype=dtype, ver=ver,
-                 w2=b1.conv.weight.detach().to(dtype).contiguous(memory_format=torch.channels_last),
-                 b2=b1.conv.bias.detach().to(dtype), b2f=b1.conv.bias.detach().float().contiguous(),
-                 w2_ohwi=b1.conv.weight.detach().to(dtype).permute(0, 2, 3, 1).contiguous(),
-                 ln2=(b1.norm.norm.weight.detach().float().reshape(-1).contiguous(),
-                      b1.norm.norm.bias.detach().float().reshape(-1).contiguous(), b1.norm.norm.eps),
-                 lin_w=lin.weight.detach().to(dtype).contiguous(), lin_b=lin.bias.detach().to(dtype))
-        model._cm_frontend_cache = c
-    return c
+    return _FRONTEND.lookup(model, _params_key(dtype, model.CNN, model.Transformer.custom_src_module), dtype)
 
 
 @torch.no_grad()

@@ -23,7 +23,7 @@ import os
 import torch
 from torch.amp import custom_bwd, custom_fwd
 
-from ... import ops
+from ... import ops, weight_cache
 
 # CM_ROWS_TRAIN=0: the mixers run on the (B, E, T) operator API (selective_scan_interface._MambaInner) as in rounds 1-2
 ENABLED = os.environ.get("CM_ROWS_TRAIN", "1") == "1"
@@ -48,7 +48,6 @@ class _Derived:
     selective_scan_interface.py:187), A = -exp(A_log), the K-concatenated out_proj weight."""
 
     def __init__(self, m, sfx, cdt, scale):
-        self.key = self.make_key(m, cdt)
         self.cdt, self.nsfx = cdt, len(sfx)
         E, R = m.d_inner, m.dt_rank
         P = ops.rows_dt_pad(R)
@@ -59,10 +58,7 @@ class _Derived:
         self.xr, self.xr_packed, self.dtw, self.A = [], [], [], []
         for s in sfx:
             xp, dtp = getattr(m, "x_proj" + s), getattr(m, "dt_proj" + s)
-            xr = torch.zeros(self.RW, E, dtype=cdt, device=xp.weight.device)
-            xr[:R] = xp.weight.detach()[:R].to(cdt)
-            xr[P:] = xp.weight.detach()[R:].to(cdt)
-            self.xr.append(xr)
+            self.xr.append(ops.xproj_rows(xp.weight, R, P, cdt))
             self.dtw.append(ops.pad_dt_weight(dtp.weight.detach().to(cdt)))
             self.A.append((-torch.exp(getattr(m, "A_b_log" if s else "A_log").detach().float())).contiguous())
         if cdt == torch.bfloat16 and len(sfx) == 2 and E % 32 == 0 and E <= 2048:
@@ -73,47 +69,33 @@ class _Derived:
 
     def rebuild_(self, m, sfx, cdt, scale):
         """The same operands from the parameters' current values, written into the tensors this object already holds (their
-        addresses are what a captured hipGraph reads: ops.CACHE_INPLACE)."""
+        addresses are what a captured hipGraph reads: weight_cache.CACHE_INPLACE)."""
         E, R, P = m.d_inner, m.dt_rank, self.P
         self.w_in.copy_(m.in_proj.weight.detach())
         self.w_out.copy_(m.out_proj.weight.detach() * scale)
         for i, s in enumerate(sfx):
             xp, dtp = getattr(m, "x_proj" + s), getattr(m, "dt_proj" + s)
             self.w_out_cat[:, i * E:(i + 1) * E].copy_(self.w_out)
-            self.xr[i][:R].copy_(xp.weight.detach()[:R])
-            self.xr[i][P:].copy_(xp.weight.detach()[R:])
+            ops.xproj_rows_(self.xr[i], xp.weight, R, P)
             self.dtw[i].copy_(ops.pad_dt_weight(dtp.weight.detach().to(cdt)))
             self.A[i].copy_(-torch.exp(getattr(m, "A_b_log" if s else "A_log").detach().float()))
             if self.xr_packed:
                 self.xr_packed[i].repack_(self.xr[i])
             if self.xr_bd is not None:
                 self.xr_bd[i * self.RW:(i + 1) * self.RW, i * E:(i + 1) * E].copy_(self.xr[i])
-        self.key = self.make_key(m, cdt)
-        return self
 
-    @staticmethod
-    def make_key(m, cdt):
-        # the module's parameter OBJECTS, listed once (Module.parameters() walks the module tree: 3 ms of host time per training step,
-        # which is host-bound); ops.invalidate_caches drops the list
-        pl = m.__dict__.get("_cm_plist")
-        if pl is None:
-            pl = list(m.parameters())
-            m.__dict__["_cm_plist"] = pl
-        return (cdt,) + tuple((p._version, p.data_ptr()) for p in pl)
+
+def _key(m, cdt):
+    return (cdt,) + tuple((p._version, p.data_ptr()) for p in weight_cache.module_params(m))
+
+
+_DERIVED = weight_cache.Kind("_cm_rows_derived", graphs_read=True, key_of=lambda m, d: _key(m, d.cdt), build=_Derived,
+                             reusable=lambda d, m, sfx, cdt, scale: d.cdt == cdt and d.nsfx == len(sfx) and d.w_in.device == m.in_proj.weight.device,
+                             refresh_=_Derived.rebuild_)
 
 
 def _derived(m, sfx, cdt, scale) -> _Derived:
-    d = getattr(m, "_cm_rows_derived", None)
-    if d is not None and ops._cache_hit(m, "_cm_rows_derived", d.key == _Derived.make_key(m, cdt)):
-        return d
-    if ops.CACHE_INPLACE and d is not None and d.cdt == cdt and d.nsfx == len(sfx) and d.w_in.device == m.in_proj.weight.device:
-        d.rebuild_(m, sfx, cdt, scale)
-    else:
-        d = _Derived(m, sfx, cdt, scale)
-        m._cm_rows_derived = d
-        ops._cache_new_storage()
-    ops._cache_note(m, "_cm_rows_derived")
-    return d
+    return _DERIVED.lookup(m, _key(m, cdt), sfx, cdt, scale)
 
 
 class MixerRowsFn(torch.autograd.Function):

@@ -11,11 +11,12 @@ import ctypes as ct
 from typing import Optional, Tuple
 
 import os
-import contextlib
 
 import torch
 
 from . import _native as N
+from . import weight_cache
+from .weight_cache import invalidate_caches          # noqa: F401 -- the entry point callers and the load_state_dict hook know
 
 _DT = {torch.float32: N.CM_F32, torch.bfloat16: N.CM_BF16, torch.float16: N.CM_F16}
 
@@ -45,62 +46,22 @@ def _launch(name: str, fn, args, units: int = 0):
     log.append((name, e0, e1, units))
 
 
-# Weight-derived caches under hipGraph replay (brain.Brain graph_steps).  A captured launch reads a cached tensor by ADDRESS, so the
-# caches must keep their storage for as long as a graph lives and be refreshed in place:
-#   CACHE_INPLACE     a miss that finds an older entry of the same shape / dtype rewrites that entry's tensor instead of allocating
-#   forced_refresh()  context: every entry's FIRST lookup is treated as a miss (while the "fresh" variant of a graph is captured: the
-#                     refresh kernels land in the graph) and (owner, attribute) of every refreshed entry is collected, so that the keys
-#                     of exactly those entries can be brought up to date after a replay did the refresh (rekey_caches) -- Python does
-#                     not see a replay's kernels
-CACHE_INPLACE = False
-CACHE_GENERATION = 0                              # bumped whenever an entry gets NEW storage or entries are dropped: graphs captured
-                                                  # before the bump may hold addresses the caches no longer own (brain drops them)
-_FORCE = None                                     # None, or the set of (id(owner), attribute) already refreshed in this forced pass
-_LOG = None
+# The three kinds cached on the parameter they derive from (weight_cache.py holds the protocol); captured training graphs read them all.
+_CAST = weight_cache.Kind("_cm_cast", graphs_read=True, key_of=weight_cache.param_key,
+                          build=lambda p, dtype: p.detach().to(dtype), refresh_=lambda old, p, dtype: old.copy_(p.detach()),
+                          usable=lambda old, p, dtype: old.dtype == dtype and old.device == p.device,
+                          reusable=lambda old, p, dtype: old.shape == p.shape)
 
 
-@contextlib.contextmanager
-def forced_refresh():
-    global _FORCE, _LOG
-    old = (_FORCE, _LOG)
-    _FORCE, _LOG = set(), []
-    try:
-        yield _LOG
-    finally:
-        _FORCE, _LOG = old
+def _pack_kind(attr, matrix, shape):
+    """A PackedWeight of the bf16 matrix ``matrix(p)``, whose shape is ``shape(p)``."""
+    return weight_cache.Kind(attr, graphs_read=True, key_of=weight_cache.param_key,
+                             build=lambda p: PackedWeight(matrix(p)), refresh_=lambda old, p: old.repack_(matrix(p)),
+                             usable=lambda old, p: old.data.device == p.device, reusable=lambda old, p: old.shape == shape(p))
 
 
-def _cache_hit(owner, attr, key_matches: bool) -> bool:
-    if not key_matches:
-        return False
-    return _FORCE is None or (id(owner), attr) in _FORCE
-
-
-def _cache_new_storage():
-    global CACHE_GENERATION
-    CACHE_GENERATION += 1
-    if os.environ.get("CM_CACHE_TRACE"):                              # who allocates: one line per bump
-        import traceback
-        print("cache generation", CACHE_GENERATION, " <- ".join(f"{f.name}:{f.lineno}" for f in traceback.extract_stack()[-5:-1]), flush=True)
-
-
-def _cache_note(owner, attr):
-    if _FORCE is not None:
-        _FORCE.add((id(owner), attr))
-        _LOG.append((owner, attr))
-
-
-def rekey_caches(entries) -> None:
-    """entries: what forced_refresh() collected.  Marks each entry as holding the CURRENT version of its parameter(s): call only
-    right after the kernels that refresh exactly these entries ran (a replay of the graph they were captured into)."""
-    for owner, attr in entries:
-        c = getattr(owner, attr, None)
-        if c is None:
-            continue
-        if attr == "_cm_rows_derived":
-            c.key = c.make_key(owner, c.cdt)
-        else:
-            setattr(owner, attr, ((owner._version, owner.data_ptr()), c[1]))
+_PACK = _pack_kind("_cm_pack", lambda p: cast_cached(p, torch.bfloat16), lambda p: tuple(p.shape))
+_PACK_T = _pack_kind("_cm_pack_t", lambda p: cast_cached(p, torch.bfloat16).t().contiguous(), lambda p: tuple(p.shape)[::-1])
 
 
 def cast_cached(p: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
@@ -109,24 +70,7 @@ def cast_cached(p: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     step, and autocast's own cache does not reach into custom Functions."""
     if p.dtype == dtype:
         return p.detach()
-    c = getattr(p, "_cm_cast", None)
-    key = (p._version, p.data_ptr())             # data_ptr: `p.data = ...` swaps storage without bumping _version
-    usable = c is not None and c[1].dtype == dtype and c[1].device == p.device
-    if usable and _cache_hit(p, "_cm_cast", c[0] == key):
-        return c[1]
-    if CACHE_INPLACE and usable and c[1].shape == p.shape:
-        c[1].copy_(p.detach())                   # same storage, new values
-        p._cm_cast = (key, c[1])
-        _cache_note(p, "_cm_cast")
-        return c[1]
-    t = p.detach().to(dtype)
-    try:
-        p._cm_cast = (key, t)
-        _cache_new_storage()
-        _cache_note(p, "_cm_cast")
-    except (AttributeError, RuntimeError):
-        pass
-    return t
+    return _CAST.lookup(p, weight_cache.param_key(p), dtype)
 
 
 def reflect_pad_tf(x, pad, backward=False, shape=None):
@@ -185,46 +129,12 @@ def wgrad(a, b, nbatch=None, variant=0):
 
 def pack_cached(p: torch.Tensor) -> "PackedWeight":
     """p (2-D parameter) as a bf16 PackedWeight (cm_ffn_fused's fragment-tiled image), cached like cast_cached."""
-    c = getattr(p, "_cm_pack", None)
-    key = (p._version, p.data_ptr())
-    usable = c is not None and c[1].data.device == p.device
-    if usable and _cache_hit(p, "_cm_pack", c[0] == key):
-        return c[1]
-    if CACHE_INPLACE and usable and c[1].shape == tuple(p.shape):
-        c[1].repack_(cast_cached(p, torch.bfloat16))
-        p._cm_pack = (key, c[1])
-        _cache_note(p, "_cm_pack")
-        return c[1]
-    pw = PackedWeight(cast_cached(p, torch.bfloat16))
-    try:
-        p._cm_pack = (key, pw)
-        _cache_new_storage()
-        _cache_note(p, "_cm_pack")
-    except (AttributeError, RuntimeError):
-        pass
-    return pw
+    return _PACK.lookup(p, weight_cache.param_key(p))
 
 
 def pack_cached_t(p: torch.Tensor) -> "PackedWeight":
     """p^T as a bf16 PackedWeight (the "weights" of cm_ffn_bwd_fused's two GEMMs), cached like cast_cached."""
-    c = getattr(p, "_cm_pack_t", None)
-    key = (p._version, p.data_ptr())
-    usable = c is not None and c[1].data.device == p.device
-    if usable and _cache_hit(p, "_cm_pack_t", c[0] == key):
-        return c[1]
-    if CACHE_INPLACE and usable and c[1].shape == tuple(p.shape)[::-1]:
-        c[1].repack_(cast_cached(p, torch.bfloat16).t().contiguous())
-        p._cm_pack_t = (key, c[1])
-        _cache_note(p, "_cm_pack_t")
-        return c[1]
-    pw = PackedWeight(cast_cached(p, torch.bfloat16).t().contiguous())
-    try:
-        p._cm_pack_t = (key, pw)
-        _cache_new_storage()
-        _cache_note(p, "_cm_pack_t")
-    except (AttributeError, RuntimeError):
-        pass
-    return pw
+    return _PACK_T.lookup(p, weight_cache.param_key(p))
 
 
 def ffn_bwd_fused(dout, w2t, w1t, pre, alpha, p1, p2, seed1, seed2):
@@ -256,27 +166,6 @@ def ffn_bwd_fused(dout, w2t, w1t, pre, alpha, p1, p2, seed1, seed2):
     a.workspace, a.workspace_floats, a.stream = _ptr(ws), nws, _stream()
     _launch("cm_ffn_bwd_fused", N.lib().cm_ffn_bwd_fused, a, units=rows)
     return da2, da1, act, dh, db1, db2
-
-
-def invalidate_caches(module: torch.nn.Module) -> None:
-    """Drop every cached low-precision weight copy under ``module`` (cast_cached's per-parameter copies and the fused
-    path's per-layer images).  The caches key on (parameter version, storage pointer): in-place writes made under
-    torch.no_grad() on the parameter itself, optimizer steps, load_state_dict and `p.data = new` are seen; writes
-    THROUGH ``p.data`` (``p.data.copy_()``, EMA / SWA code, vector_to_parameters) are not -- call this after them.
-    load_state_dict calls it by itself (hook installed by asr.ConMambaASR)."""
-    _cache_new_storage()
-    for p in module.parameters():
-        for attr in ("_cm_pack", "_cm_pack_t", "_cm_cast"):
-            if hasattr(p, attr):
-                try:
-                    delattr(p, attr)
-                except AttributeError:
-                    pass
-    for m in module.modules():
-        m.__dict__.pop("_cm_plist", None)
-        for attr in ("_cm_fused_cache", "_cm_frontend_cache", "_cm_rows_derived"):
-            if hasattr(m, attr):
-                delattr(m, attr)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -514,6 +403,19 @@ def pad_dt_weight(dt_weight: torch.Tensor) -> torch.Tensor:
     d, r = dt_weight.shape
     out = torch.zeros((d, rows_dt_pad(r)), dtype=torch.float32, device=dt_weight.device)
     out[:, :r] = dt_weight.detach().float()
+    return out
+
+
+def xproj_rows(x_weight: torch.Tensor, dt_rank: int, pad: int, dtype: torch.dtype) -> torch.Tensor:
+    """x_proj's weight (dt_rank + 32, E) -> (pad + 32, E) in ``dtype``, rows [dt (zero padded to ``pad``) | B (16) | C (16)]: a GEMM with
+    it writes the x_dbl rows as cm_scan_cl_fwd's xdbl mode reads them."""
+    return xproj_rows_(torch.zeros(pad + 32, x_weight.shape[1], dtype=dtype, device=x_weight.device), x_weight, dt_rank, pad)
+
+
+def xproj_rows_(out: torch.Tensor, x_weight: torch.Tensor, dt_rank: int, pad: int) -> torch.Tensor:
+    """xproj_rows into an image that exists (its padding rows are zero already)."""
+    out[:dt_rank].copy_(x_weight.detach()[:dt_rank])
+    out[pad:].copy_(x_weight.detach()[dt_rank:])
     return out
 
 

@@ -403,9 +403,9 @@ def train():
             real(*a, **k)
     brain.optimizer.step = step
     yield dict(brain=brain, batch=(wavs, lens, tokens, lens.clone()), names=names, grabbed=grabbed, state=state, model=model)
-    from mamba_asr_amd import ops
+    from mamba_asr_amd import ops, weight_cache
     ops.SEED_EPOCH = None
-    ops.CACHE_INPLACE = False
+    weight_cache.CACHE_INPLACE = False
 
 
 # The CNN front end's conv2d backward is the vendor library's (MIOpen), whose weight gradient accumulates with atomics: under bf16
