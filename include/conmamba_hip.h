@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CM_ABI_VERSION 11
+#define CM_ABI_VERSION 12
 
 /* error codes */
 #define CM_OK            0
@@ -621,6 +621,39 @@ typedef struct cm_state_update_args {
 
 int cm_causal_conv1d_update(const cm_conv_update_args *args);
 int cm_selective_state_update(const cm_state_update_args *args);
+
+/* ---------------------------------------------------------------------------------------
+ * One decoding step of a Mamba mixer between in_proj and out_proj in ONE launch (mamba_step.hip): what UniMamba.step
+ * otherwise does with cm_causal_conv1d_update, the x_proj GEMM, the dt_proj GEMM and cm_selective_state_update
+ * (reference modules/mamba/bimamba.py:331-362).  Per batch row b, with x_in = xz[b, :dim] and z = xz[b, dim:]:
+ *   conv_state[b,c,:] <- (conv_state[b,c,1:], x_in[c]);  x[c] = silu(conv_bias[c] + sum_k conv_weight[c,k] conv_state[b,c,k])
+ *   x_dbl[j] = sum_c x_proj_weight[j,c] x[c]                    j < dt_rank + 2 * 16:  [dt_low | B | C]
+ *   dt[c]    = softplus(dt_bias[c] + sum_r dt_proj_weight[c,r] x_dbl[r])
+ *   ssm_state[b,c,n] <- ssm_state[b,c,n] exp(dt[c] A[c,n]) + dt[c] B[n] x[c]
+ *   out[b,c] = (sum_n ssm_state[b,c,n] C[n] + D[c] x[c]) silu(z[c])
+ * All arithmetic between the loads and the stores is fp32; only xz and out are in io_dtype.  One workgroup per batch row, the
+ * x_proj reduction through LDS in a fixed order: no atomics, bit-identical from run to run.  Both states are updated IN PLACE.
+ * Built for dstate 16, dconv 4, dim a multiple of 8 up to 4096, 1 <= dt_rank <= 32, fp32 / bf16 I/O; anything else returns
+ * CM_EUNSUPPORTED and launches nothing.  All tensors contiguous; the fp32 tensors 16-byte aligned.
+ * ------------------------------------------------------------------------------------- */
+typedef struct cm_mamba_step_args {
+    int32_t batch, dim, dstate, dconv, dt_rank;
+    int32_t io_dtype;              /* xz, out                                         */
+    const void  *xz;               /* (batch, 2 * dim): in_proj's output [x | z]      */
+    float       *conv_state;       /* (batch, dim, dconv) fp32, in place, oldest first */
+    float       *ssm_state;        /* (batch, dim, dstate) fp32, in place             */
+    const float *conv_weight;      /* (dim, dconv)                                    */
+    const float *conv_bias;        /* (dim) or NULL                                   */
+    const float *x_proj_weight;    /* (dt_rank + 2 * dstate, dim)                     */
+    const float *dt_proj_weight;   /* (dim, dt_rank)                                  */
+    const float *dt_bias;          /* (dim) or NULL                                   */
+    const float *A;                /* (dim, dstate), = -exp(A_log)                    */
+    const float *D;                /* (dim) or NULL                                   */
+    void        *out;              /* (batch, dim)                                    */
+    void *stream;
+} cm_mamba_step_args;
+
+int cm_mamba_step(const cm_mamba_step_args *args);
 
 /* ---------------------------------------------------------------------------------------
  * Depthwise Conv1d over time, forward and backward, on the module API's (batch, dim, seqlen) time-contiguous layout:

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("CM_LIB_PATH") or os.path.join(_HERE, "lib", "libconma
 
 CM_F32, CM_BF16, CM_F16 = 0, 1, 2
 CM_SCAN_CHUNK = 64
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 i32, i64, vp, fp = C.c_int32, C.c_int64, C.c_void_p, C.c_void_p
 
@@ -163,6 +163,14 @@ class StateUpdateArgs(C.Structure):
         ("batch", i32), ("dim", i32), ("dstate", i32), ("io_dtype", i32), ("dt_softplus", i32), ("pad_", i32),
         ("state", fp), ("x", vp), ("dt", vp), ("A", fp), ("B", vp), ("C", vp), ("D", fp), ("z", vp), ("dt_bias", fp),
         ("out", vp), ("stream", vp),
+    ]
+
+
+class MambaStepArgs(C.Structure):
+    _fields_ = [
+        ("batch", i32), ("dim", i32), ("dstate", i32), ("dconv", i32), ("dt_rank", i32), ("io_dtype", i32),
+        ("xz", vp), ("conv_state", fp), ("ssm_state", fp), ("conv_weight", fp), ("conv_bias", fp), ("x_proj_weight", fp),
+        ("dt_proj_weight", fp), ("dt_bias", fp), ("A", fp), ("D", fp), ("out", vp), ("stream", vp),
     ]
 
 
@@ -341,6 +349,7 @@ SYMBOLS = [
     ("cm_ln_pw_glu", C.c_int, [C.POINTER(LnPwGluArgs)]),
     ("cm_causal_conv1d_update", C.c_int, [C.POINTER(ConvUpdateArgs)]),
     ("cm_selective_state_update", C.c_int, [C.POINTER(StateUpdateArgs)]),
+    ("cm_mamba_step", C.c_int, [C.POINTER(MambaStepArgs)]),
     ("cm_layernorm_bwd_workspace_floats", C.c_int64, [i64, i32]),
     ("cm_layernorm_fwd", C.c_int, [C.POINTER(LayerNormArgs)]),
     ("cm_layernorm_bwd", C.c_int, [C.POINTER(LayerNormArgs)]),

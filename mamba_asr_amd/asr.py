@@ -33,6 +33,10 @@ class ASRConfig:
     bidirectional: bool = True
     seed: int = 3402
     blank_index: int = 0
+    bos_index: int = 1              # hparams/S2S/conmambamamba_large.yaml:266-267
+    eos_index: int = 2
+    min_decode_ratio: float = 0.0   # :270-271
+    max_decode_ratio: float = 1.0
 
 
 CONFIGS = {
@@ -114,6 +118,20 @@ class ConMambaASR(nn.Module):
         src = self.CNN(self.features(wavs, wav_lens, epoch, augment) if feats is None else feats)
         enc_out, pred = self.Transformer(src, tokens_bos, wav_lens, pad_idx=pad_idx)
         return torch.log_softmax(self.ctc_lin(enc_out), dim=-1), torch.log_softmax(self.seq_lin(pred), dim=-1)
+
+    @torch.no_grad()
+    def transcribe_s2s(self, wavs, wav_lens, searcher=None):
+        """wav (B, samples) -> (hyps, lengths, scores, log_probs) of the S2S searcher (s2s_decode.S2SGreedySearcher with the
+        config's bos / eos indices and decode ratios unless ``searcher`` is given): frontend -> encode -> token loop on
+        the stepped Mamba decoder.  What train_S2S.py:382-394 does at its VALID / TEST stages."""
+        assert self.cfg.num_decoder_layers > 0, "transcribe_s2s needs a decoder (S2S configuration)"
+        assert not self.training, "transcribe_s2s is the inference path: call eval() first"
+        if searcher is None:
+            from .s2s_decode import S2SGreedySearcher
+            searcher = S2SGreedySearcher(modules=[self.Transformer, self.seq_lin], bos_index=self.cfg.bos_index,
+                                         eos_index=self.cfg.eos_index, min_decode_ratio=self.cfg.min_decode_ratio,
+                                         max_decode_ratio=self.cfg.max_decode_ratio)
+        return searcher(self.encode(wavs, wav_lens), wav_lens)
 
     def s2s_objective(self, p_ctc, p_seq, tokens, tokens_lens, tokens_eos, tokens_eos_lens, wav_lens, ctc_weight=0.3,
                       label_smoothing=0.1, pad_idx=0):

@@ -195,6 +195,42 @@ class MambaDecoderLayer(nn.Module):
             tgt = self.norm3(tgt)
         return tgt, None, None
 
+    def step(self, tgt_t, self_state, cross_state):
+        """The body of ``forward`` (pre-norm, dropout = identity) for ONE target position: tgt_t (batch, 1, d_model);
+        self_state / cross_state are the (conv_state, ssm_state) pairs of the two mixers, updated in place.  The cross
+        mixer's states already hold the scan over ``memory`` (MambaDecoder.init_state), so this position continues the
+        scan over [memory ; tgt] that ``forward`` restarts from scratch."""
+        tgt = tgt_t + self.self_mamba.step(self.norm1(tgt_t), *self_state)[0]
+        tgt = tgt + self.cross_mamba.step(self.norm2(tgt), *cross_state)[0]
+        from . import ffn_rows
+        if ffn_rows.supported(tgt, self.norm3.norm, self.pos_ffn.ffn[0], self.pos_ffn.ffn[1], self.pos_ffn.ffn[3]):
+            return ffn_rows.ffn_rows(tgt, self.norm3.norm, self.pos_ffn.ffn[0], self.pos_ffn.ffn[2], self.pos_ffn.ffn[3], self.dropout3, 1.0)
+        return tgt + self.pos_ffn(self.norm3(tgt))
+
+
+class DecoderState:
+    """What a stepped MambaDecoder carries from token to token: per layer the (conv_state (batch, d_inner, d_conv),
+    ssm_state (batch, d_inner, d_state)) pairs, fp32, of the self mixer and of the cross mixer, and ``position``, the
+    number of steps taken.  Constant size: nothing grows with the number of tokens or of memory frames."""
+
+    def __init__(self, self_states, cross_states, position=0):
+        self.self_states, self.cross_states, self.position = self_states, cross_states, position
+
+    @property
+    def batch(self):
+        return self.self_states[0][0].shape[0]
+
+    def tensors(self):
+        return [t for pairs in (self.self_states, self.cross_states) for pair in pairs for t in pair]
+
+    def reorder(self, index):
+        """A NEW state whose batch row i is this state's row index[i] (index_select on the batch axis of every state
+        tensor): what a searcher does when hypotheses are re-ranked or duplicated."""
+        dev = self.self_states[0][0].device
+        index = torch.as_tensor(index, dtype=torch.long, device=dev)
+        pick = lambda pairs: [tuple(t.index_select(0, index) for t in pair) for pair in pairs]
+        return DecoderState(pick(self.self_states), pick(self.cross_states), self.position)
+
 
 class MambaDecoder(nn.Module):
     def __init__(self, num_layers, d_model, d_ffn, activation=nn.ReLU, dropout=0.0, normalize_before=False,
@@ -215,3 +251,28 @@ class MambaDecoder(nn.Module):
                               memory_key_padding_mask=memory_key_padding_mask, pos_embs_tgt=pos_embs_tgt,
                               pos_embs_src=pos_embs_src)
         return self.norm(out), [None], [None]
+
+    @torch.no_grad()
+    def init_state(self, memory) -> DecoderState:
+        """State of a stepped decode over ``memory`` (batch, T, d_model), the encoder output: zero states for every layer's
+        self mixer, and for every layer's cross mixer the states after a scan over memory (UniMamba.prefill) -- the
+        [memory ; ...] prefix of the concatenation ``forward`` scans.  As in ``forward``, the cross mixer sees the RAW
+        memory (norm2 applies to the target half only) and ALL T rows of it, padding frames included: the reference
+        scans them too, and there is no length argument here for the same reason ``TransformerASR.decode`` ignores
+        enc_len."""
+        assert self.layers[0].normalize_before, "the stepped decoder is built for normalize_before=True (the ConMamba recipes)"
+        b = memory.shape[0]
+        return DecoderState([layer.self_mamba.allocate_inference_cache(b) for layer in self.layers],
+                            [layer.cross_mamba.prefill(memory) for layer in self.layers])
+
+    @torch.no_grad()
+    def step(self, tgt_t, state: DecoderState):
+        """tgt_t (batch, 1, d_model), the embedded target position ``state.position`` -> out_t (batch, 1, d_model): row
+        ``state.position`` of what ``forward`` gives for the whole prefix.  ``state`` is updated in place."""
+        assert not self.training, "step() is the inference path: call eval() first (dropout is the identity)"
+        assert tgt_t.dim() == 3 and tgt_t.shape[1] == 1
+        out = tgt_t
+        for layer, s_self, s_cross in zip(self.layers, state.self_states, state.cross_states):
+            out = layer.step(out, s_self, s_cross)
+        state.position += 1
+        return self.norm(out)

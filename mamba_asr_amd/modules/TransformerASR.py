@@ -134,6 +134,22 @@ class TransformerASR(nn.Module):
         prediction, _, attn = self.decoder(t, encoder_out)
         return prediction, attn[-1]
 
+    @torch.no_grad()
+    def init_decode_state(self, encoder_out):
+        """The state ``decode_step`` advances: MambaDecoder.init_state over encoder_out (batch, T, d_model), all T rows."""
+        return self.decoder.init_state(encoder_out)
+
+    @torch.no_grad()
+    def decode_step(self, tokens_t, state):
+        """tokens_t (batch,) or (batch, 1): the target token at position ``state.position`` -> (batch, 1, d_model), the row
+        ``decode`` computes for that position from the whole prefix, at a cost that depends neither on the prefix length
+        nor on the number of encoder frames."""
+        t = self.custom_tgt_module(tokens_t.reshape(-1, 1))
+        pos = state.position
+        assert pos < self.positional_encoding_decoder.pe.shape[1], "decode_step: position beyond max_length"
+        t = t + self.positional_encoding_decoder.pe[:, pos:pos + 1]
+        return self.decoder.step(t, state)
+
 
 class EncoderWrapper(nn.Module):
     def __init__(self, transformer, *args, **kwargs):

@@ -13,13 +13,14 @@ MI355X-first differences (results identical):
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ... import ops
+from ... import ops, weight_cache
 from .selective_scan_interface import (bimamba_inner_fn, causal_conv1d_fn, mamba_inner_fn,
                                        mamba_inner_fn_no_out_proj, selective_scan_fn)
 
@@ -82,6 +83,25 @@ class _OutProjFn(torch.autograd.Function):
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = dy.reshape(batch * seqlen, -1).sum(0)
         return dmix, dw, db
+
+
+# UniMamba.step on the fused single-launch kernel (cm_mamba_step) where it is built for the shape; CM_FUSED_STEP=0 = the route
+# through cm_causal_conv1d_update / cm_selective_state_update and the two small GEMMs between them
+FUSED_STEP = os.environ.get("CM_FUSED_STEP", "1") == "1"
+
+
+def _build_step_operands(m):
+    """cm_mamba_step's fp32 operands of one mixer, derived once per parameter version instead of once per token."""
+    f = lambda p: None if p is None else p.detach().float().contiguous()
+    return {"conv_w": f(m.conv1d.weight).reshape(m.d_inner, -1), "conv_b": f(m.conv1d.bias), "x_proj": f(m.x_proj.weight),
+            "dt_proj": f(m.dt_proj.weight), "dt_bias": f(m.dt_proj.bias), "A": -torch.exp(f(m.A_log)), "D": f(m.D)}
+
+
+_STEP_OPERANDS = weight_cache.Kind("_cm_step_operands", graphs_read=False, build=_build_step_operands)
+
+
+def _step_operands(m):
+    return _STEP_OPERANDS.lookup(m, tuple((p._version, p.data_ptr()) for p in weight_cache.module_params(m)))
 
 
 def _init_dt_proj(dt_proj: nn.Linear, d_inner, dt_rank, dt_init, dt_scale, dt_min, dt_max, dt_init_floor, fk):
@@ -251,11 +271,17 @@ class UniMamba(nn.Module):
 
     def step(self, hidden_states, conv_state, ssm_state):
         """One decoding step (reference bimamba.py:320-365): hidden_states (batch, 1, d_model) -> (out (batch, 1,
-        d_model), conv_state, ssm_state); both states are updated in place by cm_causal_conv1d_update /
-        cm_selective_state_update.  Feeding a sequence step by step from zero states reproduces ``forward``."""
+        d_model), conv_state, ssm_state); both states are updated in place.  Between in_proj and out_proj this is one
+        launch of cm_mamba_step where that kernel is built for the shape (CM_FUSED_STEP=0: never), else
+        cm_causal_conv1d_update / cm_selective_state_update around the two small projections.  Feeding a sequence step by
+        step from zero states reproduces ``forward``."""
         assert hidden_states.shape[1] == 1, "Only support decoding with 1 token at a time for now"
         from ... import ops
         xz = self.in_proj(hidden_states.squeeze(1))                                     # (B, 2E)
+        if FUSED_STEP and xz.is_cuda and ops.mamba_step_supported(self.d_inner, self.d_state, self.d_conv, self.dt_rank, xz.dtype):
+            w = _step_operands(self)
+            y = ops.mamba_step(xz, conv_state, ssm_state, w["conv_w"], w["conv_b"], w["x_proj"], w["dt_proj"], w["dt_bias"], w["A"], w["D"])
+            return self.out_proj(y).unsqueeze(1), conv_state, ssm_state
         x, z = xz.chunk(2, dim=-1)
         x = ops.causal_conv1d_update(x, conv_state, self.conv1d.weight, self.conv1d.bias, silu=True)
         x_db = self.x_proj(x)
@@ -264,6 +290,48 @@ class UniMamba(nn.Module):
         y = ops.selective_state_update(ssm_state, x, dt, -torch.exp(self.A_log.float()), Bm, Cm, self.D.float(), z=z,
                                        dt_bias=self.dt_proj.bias.float(), dt_softplus=True)
         return self.out_proj(y).unsqueeze(1), conv_state, ssm_state
+
+    @torch.no_grad()
+    def prefill(self, hidden_states):
+        """(conv_state (batch, d_inner, d_conv), ssm_state (batch, d_inner, d_state)), fp32: the states that feeding
+        hidden_states (batch, T, d_model) through ``step`` frame by frame from zero states would leave, from ONE pass
+        over the sequence: in_proj over all rows, the sequence conv kernel, and a scan that returns its last state
+        (cm_scan_cl_fwd's h_last in xdbl mode where the rows kernels are built for the shape, else the last checkpoint of
+        cm_selective_scan_fwd).  out_proj is skipped: nothing reads the output rows."""
+        from ... import ops
+        from . import mixer_rows
+        B, T, _ = hidden_states.shape
+        E, R, N = self.d_inner, self.dt_rank, self.d_state
+        cdt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else hidden_states.dtype
+        cw, cb = self.conv1d.weight.detach().float().reshape(E, -1), (None if self.conv1d.bias is None else self.conv1d.bias.detach().float())
+        Dp, dt_bias = self.D.detach().float(), self.dt_proj.bias.detach().float()
+        h2 = hidden_states.detach().to(cdt).contiguous()
+        if mixer_rows.supported(self, hidden_states):
+            dv = mixer_rows._derived(self, ("",), cdt, 1.0)
+            xz = torch.mm(h2.view(B * T, -1), dv.w_in.t()).view(B, T, 2 * E)
+            x = xz[:, :, :E]
+            u = torch.empty((B, T, E), dtype=cdt, device=xz.device)
+            ops.conv_cl_fwd(x, cw, cb, out_f=u)
+            xdbl = torch.mm(u.view(B * T, E), dv.xr[0].t()).view(B, T, dv.RW)
+            ssm_state = torch.empty((B, E, N), dtype=torch.float32, device=xz.device)
+            ops.scan_cl_fwd([dict(u=u, xdbl=xdbl, A=dv.A[0], D=Dp, delta_bias=dt_bias, dt_weight=dv.dtw[0], h_last=ssm_state)],
+                            z=xz[:, :, E:], delta_softplus=True)             # with the gate: the kernel's everyday variant
+        else:
+            xz = F.linear(h2, self.in_proj.weight.detach().to(cdt), None if self.in_proj.bias is None else self.in_proj.bias.detach().to(cdt))
+            x = xz[:, :, :E]
+            u = ops.causal_conv1d_fwd(x.transpose(1, 2).contiguous(), cw, cb, True)                      # (B, E, T)
+            x_dbl = F.linear(u.transpose(1, 2).reshape(B * T, E), self.x_proj.weight.detach().to(cdt))      # (B T, R + 2N)
+            delta = (self.dt_proj.weight.detach().to(cdt) @ x_dbl[:, :R].t()).view(E, B, T).transpose(0, 1)
+            Bm = x_dbl[:, R:R + N].reshape(B, T, N).transpose(1, 2).contiguous()
+            Cm = x_dbl[:, R + N:].reshape(B, T, N).transpose(1, 2).contiguous()
+            _, ck, _ = ops.selective_scan_fwd(u, delta, -torch.exp(self.A_log.detach().float()), Bm, Cm, Dp, None, dt_bias, True)
+            ssm_state = ck[:, :, -1, 1::2].contiguous()                                               # h at the last processed step
+        # the conv state is the last d_conv inputs of the conv, oldest first, zero-filled on the left when T < d_conv
+        K = self.d_conv
+        conv_state = torch.zeros((B, E, K), dtype=torch.float32, device=xz.device)
+        k = min(T, K)
+        conv_state[:, :, K - k:] = x[:, T - k:, :].transpose(1, 2)
+        return conv_state, ssm_state
 
     def forward(self, hidden_states, inference_params=None):
         if inference_params is not None:

@@ -1018,6 +1018,42 @@ def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, 
     return out
 
 
+def mamba_step_supported(d_inner: int, d_state: int, d_conv: int, dt_rank: int, dtype) -> bool:
+    """The shapes cm_mamba_step is built for (include/conmamba_hip.h)."""
+    return (d_state == 16 and d_conv == 4 and d_inner % 8 == 0 and 8 <= d_inner <= 4096 and 1 <= dt_rank <= 32
+            and dtype in (torch.float32, torch.bfloat16))
+
+
+def mamba_step(xz, conv_state, ssm_state, conv_weight, conv_bias, x_proj_weight, dt_proj_weight, dt_bias, A, D):
+    """One mixer decoding step between in_proj and out_proj in one launch (cm_mamba_step; reference bimamba.py:331-362):
+    xz (batch, 2 * dim) in fp32 / bf16; conv_state (batch, dim, 4) and ssm_state (batch, dim, 16), fp32, updated IN PLACE;
+    conv_weight (dim, 4), x_proj_weight (dt_rank + 32, dim), dt_proj_weight (dim, dt_rank), A = -exp(A_log) (dim, 16), conv_bias,
+    dt_bias, D (dim) or None -- all used in fp32.  Returns y (batch, dim) in xz's dtype.  A shape the kernel is not built
+    for raises (code -2): nothing is launched."""
+    _dev_check(xz, conv_state, ssm_state, conv_weight, conv_bias, x_proj_weight, dt_proj_weight, dt_bias, A, D)
+    if xz.dim() != 2 or xz.shape[1] % 2:
+        raise RuntimeError("mamba_step: xz must be (batch, 2 * dim)")
+    batch, dim = xz.shape[0], xz.shape[1] // 2
+    for t, what in ((conv_state, "conv_state"), (ssm_state, "ssm_state")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 3 or tuple(t.shape[:2]) != (batch, dim):
+            raise RuntimeError(f"mamba_step: {what} must be a contiguous fp32 (batch, dim, width) tensor")
+    if xz.dtype not in _DT:
+        raise RuntimeError(f"mamba_step: unsupported dtype {xz.dtype}")
+    xz = xz.contiguous()
+    cw, cb, wx, wdt = _f32c(conv_weight).reshape(dim, -1), _f32c(conv_bias), _f32c(x_proj_weight), _f32c(dt_proj_weight)
+    dt_bias, A, D = _f32c(dt_bias), _f32c(A), _f32c(D)
+    a = N.MambaStepArgs()
+    a.batch, a.dim, a.dstate, a.dconv, a.dt_rank, a.io_dtype = batch, dim, ssm_state.shape[2], conv_state.shape[2], wdt.shape[1], _DT[xz.dtype]
+    if cw.shape != (dim, a.dconv) or wx.shape != (a.dt_rank + 2 * a.dstate, dim) or wdt.shape[0] != dim or A.shape != (dim, a.dstate):
+        raise RuntimeError("mamba_step: weight shapes do not match the states")
+    out = torch.empty((batch, dim), dtype=xz.dtype, device=xz.device)
+    a.xz, a.conv_state, a.ssm_state, a.out = _ptr(xz), _ptr(conv_state), _ptr(ssm_state), _ptr(out)
+    a.conv_weight, a.conv_bias, a.x_proj_weight, a.dt_proj_weight = _ptr(cw), _ptr(cb), _ptr(wx), _ptr(wdt)
+    a.dt_bias, a.A, a.D, a.stream = _ptr(dt_bias), _ptr(A), _ptr(D), _stream()
+    _launch("cm_mamba_step", N.lib().cm_mamba_step, a, units=batch)
+    return out
+
+
 def _dwconv_args(x, weight, bias, pad_left):
     _dev_check(x, weight, bias)
     x = _time_contig(x)
