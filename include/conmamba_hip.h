@@ -424,6 +424,42 @@ typedef struct cm_ctc_beam_args {
 int64_t cm_ctc_beam_workspace_bytes(const cm_ctc_beam_args *args);
 int cm_ctc_beam_search(const cm_ctc_beam_args *args);
 
+/* CTC prefix scores for joint CTC/attention S2S decoding (csrc/ctc_prefix.hip; what speechbrain's CTCScorer adds to the decoder's
+ * log-probabilities, the reference S2S recipes' `ctc_weight_decode`; DESIGN.md §4d holds the contract).  logp (U, T, V) fp32
+ * contiguous CTC log-posteriors; n_u[u] frames of utterance u to use (clamped to [0, T] in the kernels).  Hypothesis row r belongs
+ * to utterance row_utt[r]; its state is r_n / r_b (rows, T) (log-probability that frames 0..t emit exactly the prefix and end in a
+ * non-blank / in a blank), psi_g (rows) (the prefix's log prefix probability) and last (rows) (its last token, -1 = empty prefix).
+ *   cm_ctc_prefix_score    out[r][j] = psi(prefix + c) - psi_g[r] for c = j (K == 0, out is (rows, V)) or c = candidates[r][j]
+ *                          (out is (rows, K)); -inf for blank, for a candidate outside [0, V) and for an impossible extension,
+ *                          never NaN; for c == eos the prefix's own CTC log-likelihood.  No per-(row, c) state is stored.
+ *   cm_ctc_prefix_advance  the state of prefix + tokens[r] into r_n_out / r_b_out / psi_out / last_out (not in place: the outputs
+ *                          must not alias the inputs); tokens[r] == eos copies the row's state; blank or a token outside
+ *                          [0, V) gives the impossible prefix (all -inf).
+ * Fixed summation order, no atomics: a row's results do not depend on the other rows of the launch.  row_utt, n_u, last and
+ * tokens are read on the device; a row whose row_utt lies outside [0, U) reads nothing and gets -inf.  The workgroup of
+ * cm_ctc_prefix_score covers CM_CTC_PREFIX_TILE_C candidates and stages the row's phi in LDS CM_CTC_PREFIX_TCHUNK frames at a time. */
+#define CM_CTC_PREFIX_TILE_C 64
+#define CM_CTC_PREFIX_TCHUNK 512
+typedef struct cm_ctc_prefix_args {
+    int32_t U, T, V, rows;
+    int32_t blank, eos, K, reserved0;         /* K: candidates per row; 0 = every token                         */
+    const float *logp;                        /* (U, T, V)                                                      */
+    const int32_t *n_u;                       /* (U)                                                            */
+    const int32_t *row_utt;                   /* (rows)                                                         */
+    const int32_t *last;                      /* (rows)                                                         */
+    const float *r_n, *r_b;                   /* (rows, T)                                                      */
+    const float *psi_g;                       /* (rows)                                                         */
+    const int32_t *candidates;                /* score: (rows, K) or NULL                                       */
+    float *out;                               /* score: (rows, K ? K : V)                                       */
+    const int32_t *tokens;                    /* advance: (rows)                                                */
+    float *r_n_out, *r_b_out, *psi_out;       /* advance: (rows, T) x 2, (rows)                                 */
+    int32_t *last_out;                        /* advance: (rows)                                                */
+    void *stream;
+} cm_ctc_prefix_args;
+
+int cm_ctc_prefix_score(const cm_ctc_prefix_args *args);
+int cm_ctc_prefix_advance(const cm_ctc_prefix_args *args);
+
 /* Element-wise stages of a feed-forward / convolution module's training step on (rows, dim) tensors (csrc/ffn_train.hip; the
  * reference leaves them to torch: reference modules/Conmamba.py:597-617):
  *   cm_bias_act_dropout_fwd   y = dropout(act(a + bias))  [I/O dtype]      or, with res:  y = res + alpha * dropout(a + bias)  [fp32]

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("CM_LIB_PATH") or os.path.join(_HERE, "lib", "libconma
 
 CM_F32, CM_BF16, CM_F16 = 0, 1, 2
 CM_SCAN_CHUNK = 64
+CM_CTC_PREFIX_TILE_C, CM_CTC_PREFIX_TCHUNK = 64, 512      # cm_ctc_prefix_score: candidates per workgroup, frames of phi in LDS at a time
 ABI_VERSION = 12
 
 i32, i64, vp, fp = C.c_int32, C.c_int64, C.c_void_p, C.c_void_p
@@ -309,6 +310,15 @@ class CtcBeamArgs(C.Structure):
     ]
 
 
+class CtcPrefixArgs(C.Structure):
+    _fields_ = [
+        ("U", i32), ("T", i32), ("V", i32), ("rows", i32), ("blank", i32), ("eos", i32), ("K", i32), ("reserved0", i32),
+        ("logp", fp), ("n_u", vp), ("row_utt", vp), ("last", vp), ("r_n", fp), ("r_b", fp), ("psi_g", fp),
+        ("candidates", vp), ("out", fp), ("tokens", vp), ("r_n_out", fp), ("r_b_out", fp), ("psi_out", fp), ("last_out", vp),
+        ("stream", vp),
+    ]
+
+
 # every symbol include/conmamba_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("cm_abi_version", C.c_int, []),
@@ -338,6 +348,8 @@ SYMBOLS = [
     ("cm_ctc_loss", C.c_int, [C.POINTER(CtcArgs)]),
     ("cm_ctc_beam_workspace_bytes", C.c_int64, [C.POINTER(CtcBeamArgs)]),
     ("cm_ctc_beam_search", C.c_int, [C.POINTER(CtcBeamArgs)]),
+    ("cm_ctc_prefix_score", C.c_int, [C.POINTER(CtcPrefixArgs)]),
+    ("cm_ctc_prefix_advance", C.c_int, [C.POINTER(CtcPrefixArgs)]),
     ("cm_bias_act_dropout_bwd_workspace_floats", C.c_int64, [i64, i32]),
     ("cm_bias_act_dropout_fwd", C.c_int, [C.POINTER(FfnElemArgs)]),
     ("cm_bias_act_dropout_bwd", C.c_int, [C.POINTER(FfnElemArgs)]),

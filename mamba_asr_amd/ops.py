@@ -738,6 +738,61 @@ def ctc_beam_search(log_probs, lengths, tok_class, tok_hash, tok_pow, hash_base,
     return tokens, token_len, scores, num_hyps, bad_frame
 
 
+def _ctc_prefix_args(what, logp, n_u, row_utt, last, r_n, r_b, psi_g, blank, eos, validated):
+    """The arguments cm_ctc_prefix_score and cm_ctc_prefix_advance share, checked: sizes, dtypes and (one host read, skipped
+    with validated=True for a row_utt the caller has checked already) row_utt's range."""
+    _dev_check(logp, n_u, row_utt, last, r_n, r_b, psi_g)
+    if logp.dim() != 3 or logp.dtype != torch.float32 or not logp.is_contiguous():
+        raise RuntimeError(f"{what}: logp must be a contiguous fp32 (U, T, V) tensor")
+    U, T, V = logp.shape
+    rows = row_utt.shape[0]
+    for name, t, shape, dtype in (("n_u", n_u, (U,), torch.int32), ("row_utt", row_utt, (rows,), torch.int32),
+                                  ("last", last, (rows,), torch.int32), ("r_n", r_n, (rows, T), torch.float32),
+                                  ("r_b", r_b, (rows, T), torch.float32), ("psi_g", psi_g, (rows,), torch.float32)):
+        if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+            raise RuntimeError(f"{what}: {name} must be a contiguous {dtype} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    if not validated and rows and bool(((row_utt < 0) | (row_utt >= U)).any()):
+        raise RuntimeError(f"{what}: row_utt holds an utterance index outside [0, {U})")
+    a = N.CtcPrefixArgs()
+    a.U, a.T, a.V, a.rows, a.blank, a.eos = U, T, V, rows, int(blank), int(eos)
+    a.logp, a.n_u, a.row_utt, a.last, a.r_n, a.r_b, a.psi_g = _ptr(logp), _ptr(n_u), _ptr(row_utt), _ptr(last), _ptr(r_n), _ptr(r_b), _ptr(psi_g)
+    a.stream = _stream()
+    return a
+
+
+def ctc_prefix_score(logp, n_u, row_utt, last, r_n, r_b, psi_g, blank, eos, candidates=None, validated=False):
+    """CTC prefix score deltas (cm_ctc_prefix_score).  logp (U, T, V) fp32 CTC log-posteriors, n_u (U) int32 frames per
+    utterance; per hypothesis row: row_utt (rows) int32, last (rows) int32 (-1: empty prefix), r_n / r_b (rows, T) fp32,
+    psi_g (rows) fp32.  -> (rows, V) fp32 psi(prefix + c) - psi_g, or (rows, K) for candidates (rows, K) int32 (-inf for a
+    candidate outside [0, V)); -inf for blank and for impossible extensions; column eos holds the prefix's CTC log-likelihood."""
+    a = _ctc_prefix_args("ctc_prefix_score", logp, n_u, row_utt, last, r_n, r_b, psi_g, blank, eos, validated)
+    ncol = a.V
+    if candidates is not None:
+        _dev_check(candidates)
+        if candidates.dim() != 2 or candidates.shape[0] != a.rows or candidates.shape[1] < 1 or candidates.dtype != torch.int32 \
+                or not candidates.is_contiguous():
+            raise RuntimeError("ctc_prefix_score: candidates must be a contiguous int32 (rows, K >= 1) tensor")
+        ncol = a.K = candidates.shape[1]
+        a.candidates = _ptr(candidates)
+    out = torch.empty((a.rows, ncol), dtype=torch.float32, device=logp.device)
+    a.out = _ptr(out)
+    _launch("cm_ctc_prefix_score", N.lib().cm_ctc_prefix_score, a, units=a.rows * a.T)
+    return out
+
+
+def ctc_prefix_advance(logp, n_u, row_utt, last, r_n, r_b, psi_g, tokens, blank, eos, validated=False):
+    """Every row's prefix extended by tokens (rows) int32 (cm_ctc_prefix_advance; arguments as ctc_prefix_score) ->
+    new (r_n, r_b, psi_g, last) in fresh tensors.  A row whose token is eos keeps its state."""
+    a = _ctc_prefix_args("ctc_prefix_advance", logp, n_u, row_utt, last, r_n, r_b, psi_g, blank, eos, validated)
+    _dev_check(tokens)
+    if tuple(tokens.shape) != (a.rows,) or tokens.dtype != torch.int32 or not tokens.is_contiguous():
+        raise RuntimeError("ctc_prefix_advance: tokens must be a contiguous int32 (rows,) tensor")
+    r_n2, r_b2, psi2, last2 = torch.empty_like(r_n), torch.empty_like(r_b), torch.empty_like(psi_g), torch.empty_like(last)
+    a.tokens, a.r_n_out, a.r_b_out, a.psi_out, a.last_out = _ptr(tokens), _ptr(r_n2), _ptr(r_b2), _ptr(psi2), _ptr(last2)
+    _launch("cm_ctc_prefix_advance", N.lib().cm_ctc_prefix_advance, a, units=a.rows * a.T)
+    return r_n2, r_b2, psi2, last2
+
+
 class CtcLossFn(torch.autograd.Function):
     """sum over the batch of the per-utterance CTC negative log-likelihoods (zero_infinity), gradient from the same call."""
 
