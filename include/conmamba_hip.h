@@ -460,6 +460,37 @@ typedef struct cm_ctc_prefix_args {
 int cm_ctc_prefix_score(const cm_ctc_prefix_args *args);
 int cm_ctc_prefix_advance(const cm_ctc_prefix_args *args);
 
+/* Per-token selection of an S2S beam search (csrc/beam_select.hip; s2s_decode.S2SBeamSearcher; DESIGN.md §4e holds the contract).
+ * Hypothesis row r = u * B + k is beam slot k of utterance u.  Candidate (u, k, c), flat index k * V + c within its utterance:
+ *   a   = -inf if c == eos and eos_blocked[u] != 0, else att[r][c]
+ *   inc = a                          (delta == NULL)        or  a + weight * delta[r][c]
+ *   s   = alive[r] + inc
+ * as separately rounded fp32 operations (a multiply, then two adds; never an FMA).  A NaN s ranks as -inf; +0 and -0 tie.  Output
+ * slot j of utterance u is the j-th candidate under (s descending, flat index ascending): a total order, so all B slots are always
+ * filled -- with fewer than B finite candidates by -inf ones in index order (their score is -inf, whatever inc holds).
+ * Two launches: every (row, chunk of CM_BEAM_SELECT_CHUNK tokens) keeps its best min(B, chunk length) in the workspace, then one
+ * workgroup per utterance ranks them.  Integer LDS histograms only: bit-identical from run to run, and an utterance's result does
+ * not depend on the other utterances of the launch.  Nothing is read on the host; an eos outside [0, V) never matches. */
+#define CM_BEAM_SELECT_MAX_B 128
+#define CM_BEAM_SELECT_CHUNK 5120
+typedef struct cm_beam_select_args {
+    int32_t U, B, V, eos;                     /* 1 <= B <= CM_BEAM_SELECT_MAX_B, V >= 1, B * V < 2^31           */
+    const float *att;                         /* (U * B, V) decoder log-probabilities                           */
+    const float *delta;                       /* (U * B, V) CTC prefix scores, or NULL                          */
+    const float *alive;                       /* (U * B) running scores; -inf: dead slot                        */
+    const int32_t *eos_blocked;               /* (U) or NULL                                                    */
+    float weight;                             /* of delta                                                       */
+    int32_t reserved0;
+    float *score, *inc;                       /* out (U, B)                                                     */
+    int32_t *parent, *token;                  /* out (U, B): parent slot in [0, B), token in [0, V)             */
+    void *workspace;                          /* cm_beam_select_workspace_bytes(U, B, V) bytes, 8-byte aligned  */
+    int64_t workspace_bytes;
+    void *stream;
+} cm_beam_select_args;
+
+int64_t cm_beam_select_workspace_bytes(int32_t U, int32_t B, int32_t V);   /* 0 for sizes cm_beam_select refuses */
+int cm_beam_select(const cm_beam_select_args *args);
+
 /* Element-wise stages of a feed-forward / convolution module's training step on (rows, dim) tensors (csrc/ffn_train.hip; the
  * reference leaves them to torch: reference modules/Conmamba.py:597-617):
  *   cm_bias_act_dropout_fwd   y = dropout(act(a + bias))  [I/O dtype]      or, with res:  y = res + alpha * dropout(a + bias)  [fp32]

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("CM_LIB_PATH") or os.path.join(_HERE, "lib", "libconma
 CM_F32, CM_BF16, CM_F16 = 0, 1, 2
 CM_SCAN_CHUNK = 64
 CM_CTC_PREFIX_TILE_C, CM_CTC_PREFIX_TCHUNK = 64, 512      # cm_ctc_prefix_score: candidates per workgroup, frames of phi in LDS at a time
+CM_BEAM_SELECT_MAX_B, CM_BEAM_SELECT_CHUNK = 128, 5120    # cm_beam_select: largest beam, tokens per workgroup of its first launch
 ABI_VERSION = 12
 
 i32, i64, vp, fp = C.c_int32, C.c_int64, C.c_void_p, C.c_void_p
@@ -319,6 +320,14 @@ class CtcPrefixArgs(C.Structure):
     ]
 
 
+class BeamSelectArgs(C.Structure):
+    _fields_ = [
+        ("U", i32), ("B", i32), ("V", i32), ("eos", i32), ("att", fp), ("delta", fp), ("alive", fp), ("eos_blocked", vp),
+        ("weight", C.c_float), ("reserved0", i32), ("score", fp), ("inc", fp), ("parent", vp), ("token", vp),
+        ("workspace", vp), ("workspace_bytes", i64), ("stream", vp),
+    ]
+
+
 # every symbol include/conmamba_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("cm_abi_version", C.c_int, []),
@@ -350,6 +359,8 @@ SYMBOLS = [
     ("cm_ctc_beam_search", C.c_int, [C.POINTER(CtcBeamArgs)]),
     ("cm_ctc_prefix_score", C.c_int, [C.POINTER(CtcPrefixArgs)]),
     ("cm_ctc_prefix_advance", C.c_int, [C.POINTER(CtcPrefixArgs)]),
+    ("cm_beam_select_workspace_bytes", C.c_int64, [i32, i32, i32]),
+    ("cm_beam_select", C.c_int, [C.POINTER(BeamSelectArgs)]),
     ("cm_bias_act_dropout_bwd_workspace_floats", C.c_int64, [i64, i32]),
     ("cm_bias_act_dropout_fwd", C.c_int, [C.POINTER(FfnElemArgs)]),
     ("cm_bias_act_dropout_bwd", C.c_int, [C.POINTER(FfnElemArgs)]),

@@ -793,6 +793,43 @@ def ctc_prefix_advance(logp, n_u, row_utt, last, r_n, r_b, psi_g, tokens, blank,
     return r_n2, r_b2, psi2, last2
 
 
+def beam_select(att, alive, B, eos, delta=None, weight=0.0, eos_blocked=None):
+    """One token's selection of an S2S beam search (cm_beam_select).  att (U * B, V) fp32 decoder
+    log-probabilities and alive (U * B) fp32 running scores (-inf: dead slot) of rows u * B + k; delta (U * B, V) fp32 CTC
+    prefix scores added with ``weight``, or None; eos_blocked (U) int32, nonzero where <eos> may not be chosen, or None.
+    -> (score, inc, parent, token), each (U, B): per utterance the B best candidates under (alive + inc descending, flat index
+    k * V + c ascending), inc = att [+ weight * delta] as separately rounded fp32 operations; parent / token int32."""
+    _dev_check(att, alive, delta, eos_blocked)
+    B = int(B)
+    if not 1 <= B <= N.CM_BEAM_SELECT_MAX_B:
+        raise RuntimeError(f"beam_select: B must be in [1, {N.CM_BEAM_SELECT_MAX_B}], got {B}")
+    if att.dim() != 2 or att.dtype != torch.float32 or not att.is_contiguous() or att.shape[0] < B or att.shape[0] % B or att.shape[1] < 1:
+        raise RuntimeError(f"beam_select: att must be a contiguous fp32 (U * {B}, V) tensor, got {att.dtype} {tuple(att.shape)}")
+    rows, V = att.shape
+    U = rows // B
+    if B * V >= 2 ** 31:
+        raise RuntimeError(f"beam_select: B * V = {B * V} must stay below 2^31")
+    for name, t, shape, dtype in (("alive", alive, (rows,), torch.float32), ("delta", delta, (rows, V), torch.float32),
+                                  ("eos_blocked", eos_blocked, (U,), torch.int32)):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != att.device):
+            raise RuntimeError(f"beam_select: {name} must be a contiguous {dtype} tensor of shape {shape} on {att.device}, "
+                               f"got {t.dtype} {tuple(t.shape)}")
+    lib = N.lib()
+    nws = lib.cm_beam_select_workspace_bytes(U, B, V)
+    if nws <= 0:
+        raise RuntimeError(f"beam_select: unsupported sizes U={U} B={B} V={V}")
+    ws = torch.empty((nws + 7) // 8, dtype=torch.int64, device=att.device)      # int64: the 8-byte alignment the library asks for
+    score, inc = (torch.empty((U, B), dtype=torch.float32, device=att.device) for _ in range(2))
+    parent, token = (torch.empty((U, B), dtype=torch.int32, device=att.device) for _ in range(2))
+    a = N.BeamSelectArgs()
+    a.U, a.B, a.V, a.eos, a.weight = U, B, V, int(eos), float(weight)
+    a.att, a.delta, a.alive, a.eos_blocked = _ptr(att), _ptr(delta), _ptr(alive), _ptr(eos_blocked)
+    a.score, a.inc, a.parent, a.token = _ptr(score), _ptr(inc), _ptr(parent), _ptr(token)
+    a.workspace, a.workspace_bytes, a.stream = _ptr(ws), ws.numel() * 8, _stream()
+    _launch("cm_beam_select", lib.cm_beam_select, a, units=rows * V)
+    return score, inc, parent, token
+
+
 class CtcLossFn(torch.autograd.Function):
     """sum over the batch of the per-utterance CTC negative log-likelihoods (zero_infinity), gradient from the same call."""
 

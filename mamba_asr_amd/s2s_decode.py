@@ -1,4 +1,4 @@
-"""Greedy S2S search on the stepped Mamba decoder: what a recipe's ``valid_search`` / ``test_search`` slot takes
+"""Greedy and beam S2S search on the stepped Mamba decoder: what a recipe's ``valid_search`` / ``test_search`` slot takes
 (reference train_S2S.py:388-394 unpacks ``hyps, _, _, _ = searcher(enc_out, wav_lens)``; the reference fills the slot with
 speechbrain's S2STransformerBeamSearcher, which re-runs ``TransformerASR.decode`` over the whole prefix for every token).
 
@@ -7,8 +7,12 @@ constant size, and the scan over the encoder frames is done once, by ``init_deco
 
 Joint CTC/attention decoding (the recipes' ``ctc_weight_decode``): ``CTCPrefixScorer`` gives, for every hypothesis row, the
 CTC prefix score of each possible next token from the encoder's CTC head (native kernels cm_ctc_prefix_score /
-cm_ctc_prefix_advance), and the searcher adds it, weighted, to the decoder's log-probabilities.  Beam
-search, LM scoring, temperature and length normalisation are not provided.
+cm_ctc_prefix_advance), and the searcher adds it, weighted, to the decoder's log-probabilities.
+
+``S2SBeamSearcher`` is the recipes' beam search (beam size, length normalisation, temperature, joint CTC scoring) on the same
+stepped decoder: per token one native selection (cm_beam_select) keeps every utterance's best beam_size of
+its beam_size x vocabulary candidates, and the decoder and CTC states are reordered by the chosen parents.  LM scoring, the
+eos threshold and the coverage penalty are not provided.
 """
 from __future__ import annotations
 
@@ -84,6 +88,16 @@ class CTCPrefixScorer:
                        psi_g=state.psi_g[idx])
 
 
+def _default_step(transformer, seq_lin, temperature=1.0):
+    """The searchers' default per-token function: log_softmax(seq_lin(transformer.decode_step(tokens, state)) / temperature)."""
+    def step(tokens, state):
+        logits = seq_lin(transformer.decode_step(tokens, state))[:, 0].float()    # decode_step: (batch, 1, d_model)
+        if temperature != 1.0:
+            logits = logits / temperature
+        return torch.log_softmax(logits, dim=-1), state
+    return step
+
+
 class S2SGreedySearcher:
     """``searcher(enc_states, wav_lens) -> (hyps, lengths, scores, log_probs)``
 
@@ -112,6 +126,8 @@ class S2SGreedySearcher:
     The loop reads one flag per token from the device (have all rows finished?); everything else stays on the device.
     """
 
+    temperature = 1.0                                                            # of the default step; S2SBeamSearcher sets its own
+
     def __init__(self, modules=None, bos_index: int = 1, eos_index: int = 2, min_decode_ratio: float = 0.0,
                  max_decode_ratio: float = 1.0, step_fn: Optional[Callable] = None, init_fn: Optional[Callable] = None,
                  ctc_weight: float = 0.0, ctc_scorer=None, ctc_fn: Optional[Callable] = None, blank_index: int = 0):
@@ -133,15 +149,13 @@ class S2SGreedySearcher:
         self.ctc_scorer, self.ctc_fn = ctc_scorer, ctc_fn
         if step_fn is None or init_fn is None:
             if modules is None or len(modules) != 2:
-                raise ValueError("S2SGreedySearcher needs modules=[transformer, seq_lin] (or step_fn and init_fn)")
+                raise ValueError(f"{type(self).__name__} needs modules=[transformer, seq_lin] (or step_fn and init_fn)")
             transformer, seq_lin = modules
 
             def default_init(enc_states):
                 return transformer.init_decode_state(enc_states)
 
-            def default_step(tokens, state):
-                out = transformer.decode_step(tokens, state)                      # (batch, 1, d_model)
-                return torch.log_softmax(seq_lin(out)[:, 0].float(), dim=-1), state
+            default_step = _default_step(transformer, seq_lin, self.temperature)
 
             init_fn, step_fn = init_fn or default_init, step_fn or default_step
         self.init_fn, self.step_fn = init_fn, step_fn
@@ -198,3 +212,194 @@ class S2SGreedySearcher:
         tok_host, len_host = tok.cpu().tolist(), lengths.cpu().tolist()
         hyps = [row[:n] for row, n in zip(tok_host, len_host)]                    # a row's tokens before its <eos>
         return hyps, lengths, scores, log_probs
+
+
+def select_torch(att, alive, B, eos, delta=None, weight=0.0, eos_blocked=None):
+    """ops.beam_select restated in torch (the CM_BEAM_SELECT=0 route; any device): the same three fp32 operations, then
+    torch.topk over each utterance's B * V joint scores.  Among EQUAL scores topk's order is not the native kernel's (lowest
+    flat index first); for a searcher that only matters among the -inf candidates that fill dead slots."""
+    rows, V = att.shape
+    U = rows // B
+    a = att
+    if eos_blocked is not None and 0 <= eos < V:
+        a = att.clone()
+        blocked = eos_blocked.bool().repeat_interleave(B)
+        a[:, eos] = torch.where(blocked, torch.full_like(alive, float("-inf")), a[:, eos])
+    inc = a if delta is None else a + weight * delta
+    s = alive.unsqueeze(1) + inc
+    s = torch.where(torch.isnan(s), torch.full_like(s, float("-inf")), s)
+    score, flat = torch.topk(s.view(U, B * V), B, dim=1)
+    parent = torch.div(flat, V, rounding_mode="floor")
+    token = flat - parent * V
+    inc_sel = inc.reshape(U, B * V).gather(1, flat)
+    return score, inc_sel, parent.to(torch.int32), token.to(torch.int32)
+
+
+class S2SBeamSearcher(S2SGreedySearcher):
+    """Beam search in the call shape of S2SGreedySearcher: ``searcher(enc_states, wav_lens) -> (hyps, lengths, scores,
+    log_probs)``, the slot the reference recipes fill with speechbrain's S2STransformerBeamSearcher (hparams/S2S/*.yaml:
+    valid_beam_size 10, test_beam_size 66, length_normalization True, temperature 1.15, ctc_weight_decode 0.40).
+
+    modules / step_fn / init_fn / ctc_weight / ctc_scorer / ctc_fn / blank_index / bos_index / eos_index / min_decode_ratio /
+    max_decode_ratio are the greedy searcher's.  The state ``init_fn`` returns and the CTC scorer's state must have
+    ``reorder`` (DecoderState and CTCPrefixScorer do).  Added:
+      beam_size             1 .. 128 hypotheses per utterance; hypothesis rows are u * beam_size + slot
+      length_normalization  rank finished hypotheses by score / (number of summed increments) instead of the raw sum
+      temperature           the default step is log_softmax(seq_lin(out) / temperature)
+      topk                  hypotheses returned per utterance
+      select_fn             the per-token selection, ``ops.beam_select``'s signature and contract; default ops.beam_select
+                            (cm_beam_select), or ``select_torch`` with CM_BEAM_SELECT=0 in the environment
+    No LM scorer, eos threshold or coverage penalty: asking for one raises NotImplementedError.
+
+    Per token: step every row, add the weighted CTC prefix scores, and keep per utterance the beam_size best of its
+    beam_size x vocab candidates (<eos> masked below the utterance's min_decode_ratio floor; <eos> candidates compete for
+    the slots like any other).  A slot that took <eos> is a finished hypothesis; it and the slots filled with -inf candidates
+    are dead from then on (they step on <eos>, as the greedy searcher's finished rows do).  An utterance's search is over once
+    it has beam_size finished hypotheses or no live slot, whatever the rest of the batch does; the loop ends when that holds
+    for all, or after floor(max_decode_ratio * max(enc_len)) steps.  That cap is the batch's (as in the greedy searcher), so an
+    utterance decoded alone equals the same utterance in a batch only where its search ends below its own cap.  Slots still alive when their utterance's search ends are
+    closed as they are (no <eos> term).  Per utterance the hypotheses are ranked by final score,
+    then earlier completion, then lower slot.  One flag is read from the device per token; the records of all steps come to
+    the host at the end (one fp32 and one int32 copy).
+
+    topk == 1: hyps / lengths (U,) / scores (U,) / log_probs (U, steps) as the greedy searcher's, scores the final (raw or
+    normalised) scores, log_probs the increments along the best path and 0 behind it.  topk > 1: hyps[u] is a list of up to
+    topk token lists, lengths / scores are (U, topk) padded with 0 / -inf; log_probs belongs to the best hypothesis."""
+
+    def __init__(self, modules=None, beam_size: int = 10, length_normalization: bool = True, temperature: float = 1.0,
+                 topk: int = 1, select_fn: Optional[Callable] = None, using_eos_threshold: bool = False, scorer=None,
+                 lm_weight: float = 0.0, lm_modules=None, **greedy_args):
+        if using_eos_threshold:
+            raise NotImplementedError("S2SBeamSearcher: the eos threshold (using_eos_threshold) is not provided")
+        if scorer is not None:
+            raise NotImplementedError("S2SBeamSearcher: a scorer= object (ScorerBuilder) is not provided; joint CTC decoding "
+                                      "is ctc_weight=")
+        if lm_weight or lm_modules is not None:
+            raise NotImplementedError("S2SBeamSearcher: LM scoring (lm_weight / lm_modules) is not provided")
+        self.beam_size, self.topk = int(beam_size), int(topk)
+        if not 1 <= self.beam_size <= 128:
+            raise ValueError(f"beam_size must be in [1, 128], got {beam_size}")
+        if self.topk < 1:
+            raise ValueError(f"topk must be >= 1, got {topk}")
+        self.temperature = float(temperature)
+        if not self.temperature > 0.0:
+            raise ValueError(f"temperature must be > 0, got {temperature}")
+        self.length_normalization = bool(length_normalization)
+        super().__init__(modules=modules, **greedy_args)
+        if select_fn is None:
+            import os
+            if os.environ.get("CM_BEAM_SELECT", "1") == "0":
+                select_fn = select_torch
+            else:
+                from . import ops
+                select_fn = ops.beam_select
+        self.select_fn = select_fn
+
+    @torch.no_grad()
+    def __call__(self, enc_states, wav_lens):
+        U, T = enc_states.shape[0], enc_states.shape[1]
+        B, eos_index = self.beam_size, self.eos_index
+        dev = enc_states.device
+        enc_lens = torch.round(T * wav_lens.to(device=dev, dtype=torch.float32))
+        min_steps = torch.floor(self.min_decode_ratio * enc_lens.double()).long()
+        max_steps = int(torch.floor(self.max_decode_ratio * enc_lens.double().max()))
+        idx = torch.arange(U, device=dev).repeat_interleave(B)
+        state = self.init_fn(enc_states).reorder(idx)                            # the prefill runs once per utterance
+        joint = self.ctc_weight > 0.0
+        if joint:
+            ctc_state = self.ctc_scorer.init(self.ctc_fn(enc_states), enc_lens, row_utt=idx)
+        neg_inf = torch.full((U, B), float("-inf"), dtype=torch.float32, device=dev)
+        alive = neg_inf.clone()
+        alive[:, 0] = 0.0
+        tokens = torch.full((U * B,), self.bos_index, dtype=torch.long, device=dev)
+        eos = torch.full((U, B), eos_index, dtype=torch.long, device=dev)
+        row0 = (torch.arange(U, device=dev) * B).unsqueeze(1)
+        n_fin = torch.zeros(U, dtype=torch.long, device=dev)
+        records, choices = [], []                                                # per step (score, inc) fp32 and (parent, token) int32
+        for t in range(max_steps):
+            lp, state = self.step_fn(tokens, state)
+            lp = lp.float().contiguous()
+            delta = self.ctc_scorer.score(ctc_state).float().contiguous() if joint else None
+            score, inc, parent, token = self.select_fn(lp, alive.reshape(-1).contiguous(), B, eos_index, delta=delta,
+                                                       weight=self.ctc_weight if joint else 0.0,
+                                                       eos_blocked=(min_steps > t).to(torch.int32))
+            parent, token = parent.int(), token.int()
+            finite = torch.isfinite(score)
+            is_eos = token == eos_index
+            n_fin = n_fin + (is_eos & finite).sum(dim=1)
+            alive = torch.where(is_eos | ~finite, neg_inf, score)
+            tokens = torch.where(finite, token.long(), eos).reshape(-1)          # a dead slot steps on <eos>, never on blank
+            rows = (row0 + parent.long()).reshape(-1)
+            state = state.reorder(rows)
+            if joint:
+                ctc_state = self.ctc_scorer.advance(self.ctc_scorer.reorder(ctc_state, rows), tokens)
+            records.append(torch.stack([score, inc]))
+            choices.append(torch.stack([parent, token]))
+            full = n_fin >= B
+            if bool((full | ~torch.isfinite(alive).any(dim=1)).all()):           # the one host read per token
+                break
+            # an utterance with beam_size finished hypotheses is over, whatever the rest of the batch still does: its live slots
+            # (recorded above) are closed as they are and extend no further
+            alive = torch.where(full.unsqueeze(1), neg_inf, alive)
+        return self._finish(records, choices, U, dev)
+
+    def _finish(self, records, choices, U, dev):
+        """Ranking and backtrace on the host, from one copy each of the stacked (steps, 2, U, B) fp32 and int32 records."""
+        B, steps = self.beam_size, len(records)
+        if steps == 0:                                                           # a cap of zero steps: the empty hypothesis, score 0
+            hyps = [[] for _ in range(U)] if self.topk == 1 else [[[]] for _ in range(U)]
+            shape = (U,) if self.topk == 1 else (U, self.topk)
+            lengths = torch.zeros(shape, dtype=torch.long, device=dev)
+            scores = torch.zeros(shape, dtype=torch.float32, device=dev)
+            if self.topk > 1:
+                scores[:, 1:] = float("-inf")
+            return hyps, lengths, scores, torch.zeros((U, 0), dtype=torch.float32, device=dev)
+        rec, cho = torch.stack(records).cpu(), torch.stack(choices).cpu()
+        score, inc, parent, token = rec[:, 0], rec[:, 1], cho[:, 0], cho[:, 1]   # (steps, U, B)
+        finite = torch.isfinite(score)
+        fin = finite & (token == self.eos_index)                                 # finished at step t: t tokens and the <eos>
+        reached = fin.sum(dim=2).cumsum(dim=0) >= B                              # (steps, U): the utterance's search is over
+        last = torch.where(reached.any(dim=0), reached.long().argmax(dim=0), torch.full((U,), steps - 1))
+        open_ = torch.zeros_like(fin)
+        for u in range(U):                                                       # alive when the utterance's search ended: closed as it is
+            open_[last[u], u] = finite[last[u], u] & ~fin[last[u], u]
+        n_inc = torch.arange(1, steps + 1, dtype=torch.float32).view(-1, 1, 1).expand_as(score)
+        final = score / n_inc if self.length_normalization else score            # fp32; open slots: `steps` tokens, no <eos>
+        done_step = torch.arange(steps).view(-1, 1, 1).expand_as(score) + open_.long()   # open slots complete after the last step
+        score_l, inc_l, parent_l, token_l = score.tolist(), inc.tolist(), parent.tolist(), token.tolist()
+        hyps_all, len_all, score_all = [], [], []
+        log_probs = torch.zeros((U, steps), dtype=torch.float32)
+        for u in range(U):
+            cand = (fin[:, u] | open_[:, u]).nonzero().tolist()                  # (step, slot) pairs
+            cand.sort(key=lambda ts: (-float(final[ts[0], u, ts[1]]), int(done_step[ts[0], u, ts[1]]), ts[1]))
+            hyps_u, scores_u = [], []
+            for rank, (t, j) in enumerate(cand[:self.topk]):
+                toks, incs, slot = [], [], j
+                for s in range(t, -1, -1):
+                    toks.append(token_l[s][u][slot])
+                    incs.append(inc_l[s][u][slot])
+                    slot = parent_l[s][u][slot]
+                toks.reverse()
+                incs.reverse()
+                if bool(fin[t, u, j]):
+                    toks.pop()                                                   # the closing <eos>
+                hyps_u.append(toks)
+                scores_u.append(float(final[t, u, j]))
+                if rank == 0:
+                    log_probs[u, :len(incs)] = torch.tensor(incs, dtype=torch.float32)
+            hyps_all.append(hyps_u)
+            score_all.append(scores_u)
+            len_all.append([len(h) for h in hyps_u])
+        if self.topk == 1:
+            hyps = [h[0] if h else [] for h in hyps_all]
+            lengths = torch.tensor([n[0] if n else 0 for n in len_all], dtype=torch.long)
+            scores = torch.tensor([s[0] if s else float("-inf") for s in score_all], dtype=torch.float32)
+        else:
+            hyps = hyps_all
+            lengths = torch.zeros((U, self.topk), dtype=torch.long)
+            scores = torch.full((U, self.topk), float("-inf"), dtype=torch.float32)
+            for u in range(U):
+                n = len(len_all[u])
+                lengths[u, :n] = torch.tensor(len_all[u], dtype=torch.long)
+                scores[u, :n] = torch.tensor(score_all[u], dtype=torch.float32)
+        return hyps, lengths.to(dev), scores.to(dev), log_probs.to(dev)
