@@ -599,21 +599,22 @@ int cm_conv_xproj(const cm_conv_xproj_args *args);
  *   if norm2: out = LN(r1; g2, b2, eps2) else out = r1;  written in out_dtype if out != NULL
  * Covers the four residual/normalisation seams of ConmambaEncoderLayer.forward
  * (reference modules/Conmamba.py:638-649) and the encoder's final norm (:725).
+ * dim: a multiple of 4, at most 1024.  Every check is made before anything is launched.
  * ------------------------------------------------------------------------------------- */
 typedef struct cm_add_ln_args {
     int64_t rows;
     int32_t dim;
-    int32_t y_dtype;             /* dtype of y (CM_BF16 / CM_F32)        */
-    int32_t out_dtype;           /* dtype of out                          */
-    int32_t out_act;             /* activation applied to `out`: 0 none, 1 LeakyReLU(0.01) */
-    const float *x;              /* (rows, dim) fp32, or NULL (treated as zeros)            */
-    const void  *y;              /* (rows, dim) or NULL                   */
+    int32_t y_dtype;             /* dtype of y: CM_F32 or CM_BF16 (read when y != NULL); anything else, CM_F16 included: CM_EUNSUPPORTED */
+    int32_t out_dtype;           /* dtype of out: CM_F32 or CM_BF16 (read when out != NULL); anything else: CM_EUNSUPPORTED             */
+    int32_t out_act;             /* activation applied to `out`: 0 none, 1 LeakyReLU(0.01); other values: CM_EUNSUPPORTED */
+    const float *x;              /* (rows, dim) fp32, 16-byte aligned (CM_EALIGN), or NULL (treated as zeros)            */
+    const void  *y;              /* (rows, dim) y_dtype, or NULL; x and y both NULL: CM_EINVAL */
     float alpha;
     float eps1, eps2;
     int32_t pad2_;
     const float *g1, *b1;        /* first LN (applied to the residual) or NULL  */
     const float *g2, *b2;        /* second LN (produces `out`) or NULL          */
-    float *x_out;                /* (rows, dim) fp32 or NULL                    */
+    float *x_out;                /* (rows, dim) fp32, 16-byte aligned (CM_EALIGN), or NULL */
     void  *out;                  /* (rows, dim) out_dtype or NULL               */
     void  *stream;
 } cm_add_ln_args;

@@ -699,6 +699,11 @@ extern "C" int cm_add_layernorm(const cm_add_ln_args *args) {
     CM_REQUIRE(a.rows > 0 && a.dim > 0 && (a.x || a.y), CM_EINVAL, "add_layernorm: bad sizes / x and y both NULL");
     CM_REQUIRE(a.dim % 4 == 0 && a.dim <= 1024, CM_EUNSUPPORTED, "add_layernorm: dim %d unsupported (multiple of 4, <= 1024)", a.dim);
     CM_REQUIRE((!a.g1 || a.b1) && (!a.g2 || a.b2), CM_EINVAL, "add_layernorm: LayerNorm weight without bias");
+    // the instances below are fp32 / bf16 only: any other dtype would be read or written as 4-byte elements
+    CM_REQUIRE(!a.y || a.y_dtype == CM_F32 || a.y_dtype == CM_BF16, CM_EUNSUPPORTED, "add_layernorm: y dtype %d unsupported (fp32 / bf16)", a.y_dtype);
+    CM_REQUIRE(!a.out || a.out_dtype == CM_F32 || a.out_dtype == CM_BF16, CM_EUNSUPPORTED, "add_layernorm: out dtype %d unsupported (fp32 / bf16)", a.out_dtype);
+    CM_REQUIRE(a.out_act == 0 || a.out_act == 1, CM_EUNSUPPORTED, "add_layernorm: out_act %d (0 none, 1 LeakyReLU(0.01))", a.out_act);
+    CM_REQUIRE(cm_aligned(a.x, 16) && cm_aligned(a.x_out, 16), CM_EALIGN, "add_layernorm: x / x_out must be 16-byte aligned");
     dim3 grid((unsigned)((a.rows + 3) / 4));
     hipStream_t st = reinterpret_cast<hipStream_t>(a.stream);
     const int nv = (a.dim + 255) / 256;

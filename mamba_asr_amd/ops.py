@@ -1044,6 +1044,12 @@ def add_layernorm(x, y=None, alpha=1.0, norm1=None, norm2=None, x_out=None, out_
     ref = x if x is not None else y
     if x is not None and (x.dtype != torch.float32 or not x.is_contiguous()):
         raise RuntimeError("add_layernorm: x must be contiguous fp32")
+    od = out_dtype or torch.bfloat16
+    for t, what in ((y.dtype if y is not None else None, "y"), (od if want_out else None, "out_dtype")):
+        if t is not None and t not in (torch.float32, torch.bfloat16):     # cm_add_layernorm has fp32 / bf16 instances only
+            raise RuntimeError(f"add_layernorm: {what} must be fp32 or bf16, not {t}")
+    if x_out is not None and (x_out.dtype != torch.float32 or not x_out.is_contiguous() or x_out.numel() != ref.numel()):
+        raise RuntimeError("add_layernorm: x_out must be contiguous fp32 with x's size")
     d = ref.shape[-1]
     rows = ref.numel() // d
     a = N.AddLnArgs()
@@ -1064,7 +1070,6 @@ def add_layernorm(x, y=None, alpha=1.0, norm1=None, norm2=None, x_out=None, out_
         a.g2, a.b2, a.eps2 = _ptr(g), _ptr(bt), float(norm2[2])
     out = None
     if want_out:
-        od = out_dtype or torch.bfloat16
         out = torch.empty(ref.shape, dtype=od, device=ref.device)
         a.out, a.out_dtype = _ptr(out), _DT[od]
     a.x = _ptr(x)
