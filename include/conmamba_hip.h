@@ -491,6 +491,33 @@ typedef struct cm_beam_select_args {
 int64_t cm_beam_select_workspace_bytes(int32_t U, int32_t B, int32_t V);   /* 0 for sizes cm_beam_select refuses */
 int cm_beam_select(const cm_beam_select_args *args);
 
+/* One decoding step of multi-head self-attention over a KV cache addressed through a beam-ancestry table (csrc/attn_step.hip;
+ * modules/TransformerLM.py; DESIGN.md §4f holds the contract).  dh = D / H.  For hypothesis row r and head h:
+ *   kc[t][r], vc[t][r] <- this step's k, v (the bits of qkv)
+ *   x[s] = q . K[s][anc[s][r]] / sqrt(dh) for s < t,  x[t] = q . k;   p = softmax(x) in fp32;   out = sum over s of p[s] * V[s][..]
+ * with position t's k and v taken from this launch's own copy, never from the cache: a row reads only cache lines written by
+ * earlier launches.  anc[t][.] is not read.  An anc entry outside [0, R) is clamped for the load and scores -inf: it adds
+ * nothing and is no out-of-bounds access.  fp32 arithmetic for both I/O dtypes; each dot product is an fma chain in ascending d,
+ * the sum over s runs in ascending s; no atomics: bit-identical from run to run, and row r's result depends only on qkv[r],
+ * anc[.][r] and the cache lines it names.  One launch; nothing is read on the host.
+ * CM_EUNSUPPORTED (before any launch): io_dtype other than CM_F32 / CM_BF16, dh not 32 or 64, H > CM_ATTN_STEP_MAX_H,
+ * t >= CM_ATTN_STEP_MAX_T (the scores live in LDS).  CM_EINVAL: NULL or misaligned pointers (16 bytes; anc 4), Lcap <= t,
+ * kv_stride below R * D or not a multiple of 16 bytes. */
+#define CM_ATTN_STEP_MAX_T 4096
+#define CM_ATTN_STEP_MAX_H 32
+typedef struct cm_attn_step_args {
+    int32_t R, D, H, t;                       /* rows, model dimension, heads, positions cached so far          */
+    int32_t Lcap, io_dtype;                   /* positions the caches and anc hold (> t); CM_F32 or CM_BF16     */
+    int64_t kv_stride;                        /* elements between consecutive positions of kc and of vc         */
+    const void *qkv;                          /* (R, 3 D) io: q | k | v of this step, bias added                */
+    void *kc, *vc;                            /* (Lcap, R, D) io, position stride kv_stride                     */
+    const int32_t *anc;                       /* (Lcap, R) contiguous                                           */
+    void *out;                                /* (R, D) io                                                      */
+    void *stream;
+} cm_attn_step_args;
+
+int cm_attn_step(const cm_attn_step_args *args);
+
 /* Element-wise stages of a feed-forward / convolution module's training step on (rows, dim) tensors (csrc/ffn_train.hip; the
  * reference leaves them to torch: reference modules/Conmamba.py:597-617):
  *   cm_bias_act_dropout_fwd   y = dropout(act(a + bias))  [I/O dtype]      or, with res:  y = res + alpha * dropout(a + bias)  [fp32]

@@ -121,14 +121,15 @@ class ConMambaASR(nn.Module):
 
     @torch.no_grad()
     def transcribe_s2s(self, wavs, wav_lens, searcher=None, ctc_weight=None, beam_size=None, length_normalization=True,
-                       temperature=1.0, topk=1):
+                       temperature=1.0, topk=1, lm_scorer=None, lm_weight=None):
         """wav (B, samples) -> (hyps, lengths, scores, log_probs) of the S2S searcher (s2s_decode.S2SGreedySearcher with the
         config's bos / eos indices and decode ratios unless ``searcher`` is given): frontend -> encode -> token loop on
         the stepped Mamba decoder.  What train_S2S.py:382-394 does at its VALID / TEST stages.  ``ctc_weight`` (the recipes'
         ``ctc_weight_decode``, 0.40): joint CTC/attention decoding, the CTC prefix score of log_softmax(ctc_lin(encoder
         output)) added with this weight to every token's log-probability; None: the decoder alone.  ``beam_size`` (the recipes'
         valid_beam_size 10 / test_beam_size 66): s2s_decode.S2SBeamSearcher with ``length_normalization``, ``temperature`` and
-        ``topk``; None: the greedy searcher."""
+        ``topk``; None: the greedy searcher.  ``lm_scorer`` / ``lm_weight`` (the recipes' TransformerLMScorer at lm_weight 0.60):
+        a language model as a second scorer of the beam search (s2s_decode.TransformerLMScorer); both need ``beam_size``."""
         assert self.cfg.num_decoder_layers > 0, "transcribe_s2s needs a decoder (S2S configuration)"
         assert not self.training, "transcribe_s2s is the inference path: call eval() first"
         if searcher is not None and ctc_weight is not None:
@@ -136,6 +137,10 @@ class ConMambaASR(nn.Module):
         if searcher is not None and (beam_size is not None or length_normalization is not True or temperature != 1.0 or topk != 1):
             raise ValueError("transcribe_s2s: give either a searcher or beam_size / length_normalization / temperature / topk "
                              "(a searcher carries its own)")
+        if searcher is not None and (lm_scorer is not None or lm_weight is not None):
+            raise ValueError("transcribe_s2s: give either a searcher or lm_scorer / lm_weight (a searcher carries its own)")
+        if searcher is None and beam_size is None and (lm_scorer is not None or lm_weight is not None):
+            raise ValueError("transcribe_s2s: lm_scorer / lm_weight belong to the beam search: give beam_size")
         if searcher is None and beam_size is None and (length_normalization is not True or temperature != 1.0 or topk != 1):
             raise ValueError("transcribe_s2s: length_normalization / temperature / topk belong to the beam search: give beam_size")
         if searcher is None:
@@ -150,7 +155,8 @@ class ConMambaASR(nn.Module):
                 searcher = S2SGreedySearcher(modules=modules, **args)
             else:
                 searcher = S2SBeamSearcher(modules=modules, beam_size=beam_size, length_normalization=length_normalization,
-                                           temperature=temperature, topk=topk, **args)
+                                           temperature=temperature, topk=topk, lm_scorer=lm_scorer,
+                                           lm_weight=0.0 if lm_weight is None else lm_weight, **args)
         return searcher(self.encode(wavs, wav_lens), wav_lens)
 
     def s2s_objective(self, p_ctc, p_seq, tokens, tokens_lens, tokens_eos, tokens_eos_lens, wav_lens, ctc_weight=0.3,

@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as ct
 from typing import Optional, Tuple
 
+import math
 import os
 
 import torch
@@ -828,6 +829,71 @@ def beam_select(att, alive, B, eos, delta=None, weight=0.0, eos_blocked=None):
     a.workspace, a.workspace_bytes, a.stream = _ptr(ws), ws.numel() * 8, _stream()
     _launch("cm_beam_select", lib.cm_beam_select, a, units=rows * V)
     return score, inc, parent, token
+
+
+def _attn_step_shapes(qkv, kc, vc, anc, t, H):
+    """The shape checks both routes of attn_step share -> (R, D, Lcap)."""
+    if qkv.dim() != 2 or qkv.shape[0] < 1 or qkv.shape[1] % 3 or not qkv.is_contiguous():
+        raise RuntimeError(f"attn_step: qkv must be a contiguous (R, 3 * D) tensor, got {tuple(qkv.shape)}")
+    R, D = qkv.shape[0], qkv.shape[1] // 3
+    H, t = int(H), int(t)
+    if H < 1 or D % H:
+        raise RuntimeError(f"attn_step: D = {D} is no multiple of H = {H}")
+    for name, c in (("kc", kc), ("vc", vc)):
+        if (c.dim() != 3 or tuple(c.shape[1:]) != (R, D) or c.dtype != qkv.dtype or c.device != qkv.device or c.stride(2) != 1
+                or c.stride(1) != D or (c.shape[0] > 1 and c.stride(0) < R * D)):
+            raise RuntimeError(f"attn_step: {name} must be a (Lcap, {R}, {D}) {qkv.dtype} tensor with contiguous positions on "
+                               f"{qkv.device}, got {c.dtype} {tuple(c.shape)} strides {tuple(c.stride())}")
+    Lcap = kc.shape[0]
+    if vc.shape[0] != Lcap or vc.stride(0) != kc.stride(0):
+        raise RuntimeError("attn_step: kc and vc must have the same positions and position stride")
+    if tuple(anc.shape) != (Lcap, R) or anc.dtype != torch.int32 or not anc.is_contiguous() or anc.device != qkv.device:
+        raise RuntimeError(f"attn_step: anc must be a contiguous int32 ({Lcap}, {R}) tensor on {qkv.device}, got {anc.dtype} "
+                           f"{tuple(anc.shape)}")
+    if not 0 <= t < Lcap:
+        raise RuntimeError(f"attn_step: position t = {t} does not fit caches of {Lcap} positions")
+    return R, D, Lcap
+
+
+def attn_step(qkv, kc, vc, anc, t, H):
+    """One decoding step of H-head self-attention over a KV cache addressed through a beam-ancestry table (cm_attn_step,
+    DESIGN.md §4f).  qkv (R, 3 D) bf16 / fp32: this step's q | k | v; kc, vc (Lcap, R, D) caches of qkv's dtype, written in place
+    at position t and nowhere else; anc (Lcap, R) int32: anc[s, r] is the row in which row r's prefix token of position s < t was
+    cached (an entry outside [0, R) scores -inf); -> out (R, D) in qkv's dtype.  fp32 arithmetic; D / H in {32, 64}, H <= 32,
+    t < 4096."""
+    _dev_check(qkv, kc, vc, anc)
+    if qkv.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"attn_step: unsupported dtype {qkv.dtype} (fp32 / bf16)")
+    R, D, Lcap = _attn_step_shapes(qkv, kc, vc, anc, t, H)
+    out = torch.empty((R, D), dtype=qkv.dtype, device=qkv.device)
+    a = N.AttnStepArgs()
+    a.R, a.D, a.H, a.t, a.Lcap, a.io_dtype = R, D, int(H), int(t), Lcap, _DT[qkv.dtype]
+    a.kv_stride = kc.stride(0) if Lcap > 1 else R * D
+    a.qkv, a.kc, a.vc, a.anc, a.out, a.stream = _ptr(qkv), _ptr(kc), _ptr(vc), _ptr(anc), _ptr(out), _stream()
+    _launch("cm_attn_step", N.lib().cm_attn_step, a, units=R * int(H) * (int(t) + 1))
+    return out
+
+
+def attn_step_torch(qkv, kc, vc, anc, t, H):
+    """attn_step's contract restated in torch (the CM_ATTN_STEP=0 route; any device): gather the cached K and V by ``anc``,
+    matmul, softmax, matmul.  Arithmetic in fp32 (fp64 for fp64 tensors), the result rounded to qkv's dtype."""
+    R, D, _ = _attn_step_shapes(qkv, kc, vc, anc, t, H)
+    H, t = int(H), int(t)
+    dh = D // H
+    q, k, v = qkv.split(D, dim=1)
+    kc[t].copy_(k)
+    vc[t].copy_(v)
+    ct = torch.float64 if qkv.dtype == torch.float64 else torch.float32
+    idx = anc[:t].long()
+    valid = (idx >= 0) & (idx < R)
+    take = idx.clamp(0, R - 1).unsqueeze(-1).expand(t, R, D)
+    K = torch.cat([kc[:t].gather(1, take), k.unsqueeze(0)]).to(ct).view(t + 1, R, H, dh).permute(1, 2, 0, 3)   # (R, H, t + 1, dh)
+    V = torch.cat([vc[:t].gather(1, take), v.unsqueeze(0)]).to(ct).view(t + 1, R, H, dh).permute(1, 2, 0, 3)
+    x = torch.matmul(K, q.to(ct).view(R, H, dh, 1)).squeeze(-1) / math.sqrt(dh)                                # (R, H, t + 1)
+    valid = torch.cat([valid, torch.ones((1, R), dtype=torch.bool, device=qkv.device)]).t().unsqueeze(1)       # (R, 1, t + 1)
+    p = torch.softmax(x.masked_fill(~valid, float("-inf")), dim=-1)
+    V = V.masked_fill(~valid.unsqueeze(-1), 0.0)                   # a position without weight adds nothing, whatever it holds
+    return torch.matmul(p.unsqueeze(2), V).reshape(R, D).to(qkv.dtype)
 
 
 class CtcLossFn(torch.autograd.Function):

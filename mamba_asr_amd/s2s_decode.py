@@ -11,8 +11,9 @@ cm_ctc_prefix_advance), and the searcher adds it, weighted, to t
 
 ``S2SBeamSearcher`` is the recipes' beam search (beam size, length normalisation, temperature, joint CTC scoring) on the same
 stepped decoder: per token one native selection (cm_beam_select) keeps every utterance's best beam_size of
-its beam_size x vocabulary candidates, and the decoder and CTC states are reordered by the chosen parents.  LM scoring, the
-eos threshold and the coverage penalty are not provided.
+its beam_size x vocabulary candidates, and the decoder and CTC states are reordered by the chosen parents.
+``TransformerLMScorer`` adds the recipes' language model (modules/TransformerLM.py on cm_attn_step) as a second
+full scorer.  ScorerBuilder objects, the eos threshold and the coverage penalty are not provided.
 """
 from __future__ import annotations
 
@@ -86,6 +87,37 @@ class CTCPrefixScorer:
         idx = torch.as_tensor(index, dtype=torch.long, device=state.row_utt.device)
         return replace(state, row_utt=state.row_utt[idx], last=state.last[idx], r_n=state.r_n[idx], r_b=state.r_b[idx],
                        psi_g=state.psi_g[idx])
+
+
+class TransformerLMScorer:
+    """The recipes' LM scorer (speechbrain's TransformerLMScorer; reference hparams/S2S/*.yaml: lm_weight 0.60, temperature
+    1.15) on the stepped language model of modules/TransformerLM.py.
+
+      state = init(R, device, max_steps)      the LM's caches for R hypothesis rows
+      score(tokens (R,), state) -> (log_softmax(logits / temperature) (R, V) fp32, state)   consumes one token per row
+      reorder(state, rows) -> state whose row i continues the old row rows[i] (no K or V is moved)"""
+
+    def __init__(self, language_model, temperature: float = 1.0):
+        self.lm, self.temperature = language_model, float(temperature)
+        if not self.temperature > 0.0:
+            raise ValueError(f"temperature must be > 0, got {temperature}")
+
+    def init(self, R, device, max_steps):
+        have, want = next(self.lm.parameters()).device, torch.device(device)
+        if want.type == "cuda" and want.index is None:              # "cuda" names the current card
+            want = torch.device("cuda", torch.cuda.current_device())
+        if have != want:
+            raise ValueError(f"TransformerLMScorer: the language model is on {have}, not on {want}")
+        return self.lm.init_state(int(R), int(max_steps))
+
+    def score(self, tokens, state):
+        logits = self.lm.step(tokens, state).float()
+        if self.temperature != 1.0:
+            logits = logits / self.temperature
+        return torch.log_softmax(logits, dim=-1), state
+
+    def reorder(self, state, rows):
+        return state.reorder(rows)
 
 
 def _default_step(transformer, seq_lin, temperature=1.0):
@@ -249,7 +281,13 @@ class S2SBeamSearcher(S2SGreedySearcher):
       topk                  hypotheses returned per utterance
       select_fn             the per-token selection, ``ops.beam_select``'s signature and contract; default ops.beam_select
                             (cm_beam_select), or ``select_torch`` with CM_BEAM_SELECT=0 in the environment
-    No LM scorer, eos threshold or coverage penalty: asking for one raises NotImplementedError.
+      lm_scorer, lm_weight  a language model as a second full scorer: any object with TransformerLMScorer's init / score /
+                            reorder; lm_weight > 0 is required with it.  Per token ``lm_scorer.score(tokens, state)`` is called
+                            once with the tokens just chosen, and lm_weight * its log-probabilities joins the increment: as the
+                            selection's delta (LM alone), or as ctc_weight * delta_ctc + lm_weight * lm_lp formed in torch
+                            (fp32, two separately rounded products) and passed with weight 1.0
+    No ScorerBuilder object, eos threshold or coverage penalty: asking for one raises NotImplementedError, as does an lm_weight
+    without an lm_scorer.
 
     Per token: step every row, add the weighted CTC prefix scores, and keep per utterance the beam_size best of its
     beam_size x vocab candidates (<eos> masked below the utterance's min_decode_ratio floor; <eos> candidates compete for
@@ -268,14 +306,18 @@ class S2SBeamSearcher(S2SGreedySearcher):
 
     def __init__(self, modules=None, beam_size: int = 10, length_normalization: bool = True, temperature: float = 1.0,
                  topk: int = 1, select_fn: Optional[Callable] = None, using_eos_threshold: bool = False, scorer=None,
-                 lm_weight: float = 0.0, lm_modules=None, **greedy_args):
+                 lm_weight: float = 0.0, lm_modules=None, lm_scorer=None, **greedy_args):
         if using_eos_threshold:
             raise NotImplementedError("S2SBeamSearcher: the eos threshold (using_eos_threshold) is not provided")
         if scorer is not None:
             raise NotImplementedError("S2SBeamSearcher: a scorer= object (ScorerBuilder) is not provided; joint CTC decoding "
                                       "is ctc_weight=")
-        if lm_weight or lm_modules is not None:
-            raise NotImplementedError("S2SBeamSearcher: LM scoring (lm_weight / lm_modules) is not provided")
+        if lm_modules is not None or (lm_scorer is None and lm_weight):
+            raise NotImplementedError("S2SBeamSearcher: LM scoring without an lm_scorer (lm_weight alone / lm_modules) is not "
+                                      "provided; give lm_scorer=TransformerLMScorer(language_model) and lm_weight")
+        self.lm_scorer, self.lm_weight = lm_scorer, float(lm_weight or 0.0)
+        if lm_scorer is not None and not self.lm_weight > 0.0:
+            raise ValueError(f"lm_scorer needs lm_weight > 0, got {lm_weight}")
         self.beam_size, self.topk = int(beam_size), int(topk)
         if not 1 <= self.beam_size <= 128:
             raise ValueError(f"beam_size must be in [1, 128], got {beam_size}")
@@ -308,6 +350,9 @@ class S2SBeamSearcher(S2SGreedySearcher):
         joint = self.ctc_weight > 0.0
         if joint:
             ctc_state = self.ctc_scorer.init(self.ctc_fn(enc_states), enc_lens, row_utt=idx)
+        lm = self.lm_scorer is not None
+        if lm:
+            lm_state = self.lm_scorer.init(U * B, dev, max_steps)
         neg_inf = torch.full((U, B), float("-inf"), dtype=torch.float32, device=dev)
         alive = neg_inf.clone()
         alive[:, 0] = 0.0
@@ -320,8 +365,16 @@ class S2SBeamSearcher(S2SGreedySearcher):
             lp, state = self.step_fn(tokens, state)
             lp = lp.float().contiguous()
             delta = self.ctc_scorer.score(ctc_state).float().contiguous() if joint else None
+            weight = self.ctc_weight if joint else 0.0
+            if lm:
+                lm_lp, lm_state = self.lm_scorer.score(tokens, lm_state)
+                lm_lp = lm_lp.float().contiguous()
+                if joint:                                                        # two separately rounded products, then one add;
+                    delta, weight = self.ctc_weight * delta + self.lm_weight * lm_lp, 1.0   # the selection's multiply by 1.0 is exact
+                else:
+                    delta, weight = lm_lp, self.lm_weight
             score, inc, parent, token = self.select_fn(lp, alive.reshape(-1).contiguous(), B, eos_index, delta=delta,
-                                                       weight=self.ctc_weight if joint else 0.0,
+                                                       weight=weight,
                                                        eos_blocked=(min_steps > t).to(torch.int32))
             parent, token = parent.int(), token.int()
             finite = torch.isfinite(score)
@@ -333,6 +386,8 @@ class S2SBeamSearcher(S2SGreedySearcher):
             state = state.reorder(rows)
             if joint:
                 ctc_state = self.ctc_scorer.advance(self.ctc_scorer.reorder(ctc_state, rows), tokens)
+            if lm:
+                lm_state = self.lm_scorer.reorder(lm_state, rows)
             records.append(torch.stack([score, inc]))
             choices.append(torch.stack([parent, token]))
             full = n_fin >= B
