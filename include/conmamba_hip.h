@@ -518,6 +518,38 @@ typedef struct cm_attn_step_args {
 
 int cm_attn_step(const cm_attn_step_args *args);
 
+/* One decoding step of multi-head CROSS-attention: R hypothesis rows over the encoder memory of their utterance
+ * (csrc/xattn_step.hip; modules/Transformer.py; DESIGN.md §4g holds the contract).  K and V were projected once per utterance
+ * and are shared by all rows of that utterance; nothing is written but out.  dh = D / H, u = row_utt[r], n = min(enc_len[u], T):
+ *   out[r, h] = sum over s < n of softmax_s(q[r, h] . K[u, s, h] / sqrt(dh)) * V[u, s, h]
+ * Frames s >= n are never loaded.  A row whose row_utt lies outside [0, U), or whose n < 1, gets zeros and loads nothing.
+ * fp32 arithmetic for both I/O dtypes; each score is an fma chain in ascending d; the sum over s is formed in 64 / (lanes per
+ * V row) interleaved partial sums, each in ascending s, folded in ascending order, then divided by the softmax denominator;
+ * no atomics: bit-identical from run to run, and row r's result depends only on q[r] and on K / V of its utterance, not on R
+ * or on the other rows of the launch.  One launch; nothing is read on the host.
+ * k and v are (U, T, .) views: element strides per utterance and per frame, the frame stride at least D (K and V may be the
+ * two halves of one (U, T, 2 D) projection).
+ * CM_EUNSUPPORTED (before any launch): io_dtype other than CM_F32 / CM_BF16, dh not 32, 36 or 64, H > CM_XATTN_STEP_MAX_H,
+ * T >= CM_XATTN_STEP_MAX_T (the fp32 scores of one (row, head) live in the LDS strip of its wave: T floats + 2 KiB of partial
+ * sums, inside the 64 KiB a workgroup may ask for).  CM_EINVAL: NULL or misaligned pointers (16 bytes; row_utt / enc_len 4),
+ * sizes below 1, D no multiple of H, a frame stride below D, an utterance stride below (T - 1) * frame stride + D, strides
+ * that are no multiple of 16 bytes. */
+#define CM_XATTN_STEP_MAX_T 8192
+#define CM_XATTN_STEP_MAX_H 32
+typedef struct cm_xattn_step_args {
+    int32_t R, U, T, D, H, io_dtype;          /* rows, utterances, frames K / V hold, model dimension, heads; CM_F32 / CM_BF16 */
+    int64_t k_utt_stride, k_frame_stride;     /* elements between utterances / frames of k                      */
+    int64_t v_utt_stride, v_frame_stride;     /* the same of v                                                  */
+    const void *q;                            /* (R, D) io, contiguous                                          */
+    const void *k, *v;                        /* (U, T, D) io views with the strides above                      */
+    const int32_t *row_utt;                   /* (R): the utterance of each row                                 */
+    const int32_t *enc_len;                   /* (U): valid frames of each utterance                            */
+    void *out;                                /* (R, D) io, contiguous                                          */
+    void *stream;
+} cm_xattn_step_args;
+
+int cm_xattn_step(const cm_xattn_step_args *args);
+
 /* Element-wise stages of a feed-forward / convolution module's training step on (rows, dim) tensors (csrc/ffn_train.hip; the
  * reference leaves them to torch: reference modules/Conmamba.py:597-617):
  *   cm_bias_act_dropout_fwd   y = dropout(act(a + bias))  [I/O dtype]      or, with res:  y = res + alpha * dropout(a + bias)  [fp32]

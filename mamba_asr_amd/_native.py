@@ -17,6 +17,7 @@ CM_SCAN_CHUNK = 64
 CM_CTC_PREFIX_TILE_C, CM_CTC_PREFIX_TCHUNK = 64, 512      # cm_ctc_prefix_score: candidates per workgroup, frames of phi in LDS at a time
 CM_BEAM_SELECT_MAX_B, CM_BEAM_SELECT_CHUNK = 128, 5120    # cm_beam_select: largest beam, tokens per workgroup of its first launch
 CM_ATTN_STEP_MAX_T, CM_ATTN_STEP_MAX_H = 4096, 32          # cm_attn_step: positions whose scores fit in LDS, heads
+CM_XATTN_STEP_MAX_T, CM_XATTN_STEP_MAX_H = 8192, 32         # cm_xattn_step: frames whose scores fit in LDS, heads
 ABI_VERSION = 12
 
 i32, i64, vp, fp = C.c_int32, C.c_int64, C.c_void_p, C.c_void_p
@@ -336,6 +337,14 @@ class AttnStepArgs(C.Structure):
     ]
 
 
+class XattnStepArgs(C.Structure):
+    _fields_ = [
+        ("R", i32), ("U", i32), ("T", i32), ("D", i32), ("H", i32), ("io_dtype", i32),
+        ("k_utt_stride", i64), ("k_frame_stride", i64), ("v_utt_stride", i64), ("v_frame_stride", i64),
+        ("q", vp), ("k", vp), ("v", vp), ("row_utt", vp), ("enc_len", vp), ("out", vp), ("stream", vp),
+    ]
+
+
 # every symbol include/conmamba_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("cm_abi_version", C.c_int, []),
@@ -370,6 +379,7 @@ SYMBOLS = [
     ("cm_beam_select_workspace_bytes", C.c_int64, [i32, i32, i32]),
     ("cm_beam_select", C.c_int, [C.POINTER(BeamSelectArgs)]),
     ("cm_attn_step", C.c_int, [C.POINTER(AttnStepArgs)]),
+    ("cm_xattn_step", C.c_int, [C.POINTER(XattnStepArgs)]),
     ("cm_bias_act_dropout_bwd_workspace_floats", C.c_int64, [i64, i32]),
     ("cm_bias_act_dropout_fwd", C.c_int, [C.POINTER(FfnElemArgs)]),
     ("cm_bias_act_dropout_bwd", C.c_int, [C.POINTER(FfnElemArgs)]),

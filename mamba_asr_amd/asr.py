@@ -37,6 +37,8 @@ class ASRConfig:
     eos_index: int = 2
     min_decode_ratio: float = 0.0   # :270-271
     max_decode_ratio: float = 1.0
+    decoder_module: str = "mamba"   # "transformer": hparams/S2S/conmamba_{small,large}.yaml leave the default decoder
+    nhead: int = 4                  # heads of the Transformer decoder (the ConMamba encoder and the Mamba decoder have none)
 
 
 CONFIGS = {
@@ -48,6 +50,14 @@ CONFIGS = {
     # hparams/S2S/conmambamamba_large.yaml:251-257 (encoder + Mamba decoder, 5000-piece vocabulary)
     "conmambamamba_large_s2s": ASRConfig("conmambamamba_large_s2s", d_model=512, d_ffn=2048, num_encoder_layers=12,
                                          num_decoder_layers=6, output_neurons=5000, win_length=32),
+    # hparams/S2S/conmamba_large.yaml:121, 178-180, 220-229 (encoder + the default Transformer decoder, 8 heads)
+    "conmamba_large_s2s": ASRConfig("conmamba_large_s2s", d_model=512, d_ffn=2048, num_encoder_layers=12, num_decoder_layers=6,
+                                    output_neurons=5000, n_fft=512, win_length=32, seed=3407, decoder_module="transformer",
+                                    nhead=8),
+    # hparams/S2S/conmamba_small.yaml:129, 188, 229-236 (win_length left at Fbank's 25 ms)
+    "conmamba_small_s2s": ASRConfig("conmamba_small_s2s", d_model=144, d_ffn=1024, num_encoder_layers=12, num_decoder_layers=4,
+                                    output_neurons=5000, n_fft=400, win_length=25, seed=7775, decoder_module="transformer",
+                                    nhead=4),
 }
 
 
@@ -67,10 +77,10 @@ class ConMambaASR(nn.Module):
         mamba_config = {"d_state": cfg.d_state, "expand": cfg.expand, "d_conv": cfg.d_conv,
                         "bidirectional": cfg.bidirectional}
         self.Transformer = TransformerASR(
-            input_size=(cfg.n_mels // 4) * 32, tgt_vocab=cfg.output_neurons, d_model=cfg.d_model, nhead=4,
+            input_size=(cfg.n_mels // 4) * 32, tgt_vocab=cfg.output_neurons, d_model=cfg.d_model, nhead=cfg.nhead,
             num_encoder_layers=cfg.num_encoder_layers, num_decoder_layers=cfg.num_decoder_layers, d_ffn=cfg.d_ffn,
             dropout=cfg.transformer_dropout, activation=nn.GELU, encoder_module="conmamba",
-            decoder_module="mamba", attention_type="RelPosMHAXL", normalize_before=True, causal=False,
+            decoder_module=cfg.decoder_module, attention_type="RelPosMHAXL", normalize_before=True, causal=False,
             mamba_config=mamba_config)
         self.ctc_lin = sb.Linear(input_size=cfg.d_model, n_neurons=cfg.output_neurons)
         if cfg.num_decoder_layers > 0:
@@ -124,7 +134,7 @@ class ConMambaASR(nn.Module):
                        temperature=1.0, topk=1, lm_scorer=None, lm_weight=None):
         """wav (B, samples) -> (hyps, lengths, scores, log_probs) of the S2S searcher (s2s_decode.S2SGreedySearcher with the
         config's bos / eos indices and decode ratios unless ``searcher`` is given): frontend -> encode -> token loop on
-        the stepped Mamba decoder.  What train_S2S.py:382-394 does at its VALID / TEST stages.  ``ctc_weight`` (the recipes'
+        the stepped decoder (Mamba, or Transformer with the memory frames beyond each utterance's length masked).  What train_S2S.py:382-394 does at its VALID / TEST stages.  ``ctc_weight`` (the recipes'
         ``ctc_weight_decode``, 0.40): joint CTC/attention decoding, the CTC prefix score of log_softmax(ctc_lin(encoder
         output)) added with this weight to every token's log-probability; None: the decoder alone.  ``beam_size`` (the recipes'
         valid_beam_size 10 / test_beam_size 66): s2s_decode.S2SBeamSearcher with ``length_normalization``, ``temperature`` and

@@ -1,10 +1,10 @@
-"""ASR wrapper around the ConMamba encoder (and Mamba decoder) — the ConMamba/Mamba branches of the
-reference's modules/TransformerASR.py (:674-743 constructor, :745-819 forward, :868-929 encode,
+"""ASR wrapper around the ConMamba encoder (and a Mamba or Transformer decoder) — the ConMamba/Mamba branches of the
+reference's modules/TransformerASR.py (:674-743 constructor, :745-819 forward, :821-866 decode, :868-929 encode,
 :1051-1054 Xavier re-init, :1057-1105 EncoderWrapper) and of the factory in modules/Transformer.py
-(:740-758 encoder_module == 'conmamba', :778-787 decoder_module == 'mamba').
+(:740-758 encoder_module == 'conmamba', :764-777 decoder_module == 'transformer', :778-787 decoder_module == 'mamba').
 
-Only these branches are provided: the attention model families (transformer / conformer / branchformer
-encoders, transformer decoder) are out of the hot path and raise NotImplementedError.
+Only these branches are provided: the attention model families' encoders (transformer / conformer / branchformer)
+are out of the hot path and raise NotImplementedError.
 state_dict keys follow the reference: custom_src_module.layers.0.w.{weight,bias}, encoder.*, decoder.*,
 custom_tgt_module.layers.0.emb.Embedding.weight.
 """
@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from ..sb_compat import Linear, ModuleList, Swish
 from .Conmamba import ConmambaEncoder, MambaDecoder
+from .Transformer import TransformerDecoder
 
 
 class PositionalEncoding(nn.Module):
@@ -62,6 +63,13 @@ def length_to_mask(length, max_len=None):
     return torch.arange(max_len, device=length.device)[None, :] < length[:, None]
 
 
+def lookahead_mask(padded_input):
+    """(L, L) bool, True above the diagonal: position i does not see positions > i (reference Transformer.py:1902-1933, there an
+    additive 0 / -inf matrix)."""
+    L = padded_input.shape[1]
+    return torch.ones(L, L, dtype=torch.bool, device=padded_input.device).triu(1)
+
+
 class TransformerASR(nn.Module):
     def __init__(self, tgt_vocab, input_size, d_model=512, nhead=8, num_encoder_layers=6, num_decoder_layers=6,
                  d_ffn=2048, dropout=0.1, activation=nn.ReLU, positional_encoding="fixed_abs_sine",
@@ -79,7 +87,7 @@ class TransformerASR(nn.Module):
             raise NotImplementedError(f"attention_type={attention_type!r}: only 'RelPosMHAXL' (the ConMamba recipes' setting) "
                                       "is implemented; other types add sinusoidal positions to src in the reference")
         self.causal, self.attention_type, self.positional_encoding_type = causal, attention_type, positional_encoding
-        self.num_decoder_layers = num_decoder_layers
+        self.num_decoder_layers, self.decoder_module = num_decoder_layers, decoder_module
         if encoder_module != "conmamba":
             raise NotImplementedError(f"encoder_module={encoder_module!r}: only 'conmamba' is on the MI355X hot path")
         assert normalize_before, "normalize_before must be True for Conmamba"          # reference Transformer.py:752
@@ -88,11 +96,17 @@ class TransformerASR(nn.Module):
                                        activation=branchformer_activation, kernel_size=kernel_size, bias=bias,
                                        causal=causal, mamba_config=mamba_config)
         if num_decoder_layers > 0:
-            if decoder_module != "mamba":
-                raise NotImplementedError(f"decoder_module={decoder_module!r}: only 'mamba' has a HIP path")
-            self.decoder = MambaDecoder(num_layers=num_decoder_layers, d_ffn=d_ffn, d_model=d_model,
-                                        activation=activation, dropout=dropout, normalize_before=normalize_before,
-                                        mamba_config=mamba_config)
+            if decoder_module == "transformer":
+                # the factory builds its decoder with regularMHA and causal=True whatever the encoder uses, reference :765-777
+                self.decoder = TransformerDecoder(num_layers=num_decoder_layers, nhead=nhead, d_ffn=d_ffn, d_model=d_model,
+                                                  dropout=dropout, activation=activation, normalize_before=normalize_before,
+                                                  causal=True, attention_type="regularMHA", max_length=max_length)
+            elif decoder_module == "mamba":
+                self.decoder = MambaDecoder(num_layers=num_decoder_layers, d_ffn=d_ffn, d_model=d_model,
+                                            activation=activation, dropout=dropout, normalize_before=normalize_before,
+                                            mamba_config=mamba_config)
+            else:
+                raise NotImplementedError(f"decoder_module={decoder_module!r}: 'mamba' and 'transformer' are provided")
             self.positional_encoding_decoder = PositionalEncoding(d_model, max_length)
             self.custom_tgt_module = ModuleList(NormalizedEmbedding(d_model, tgt_vocab))
         self.custom_src_module = ModuleList(Linear(input_size=input_size, n_neurons=d_model, bias=True,
@@ -124,19 +138,42 @@ class TransformerASR(nn.Module):
             return encoder_out, None
         t = self.custom_tgt_module(tgt)
         t = t + self.positional_encoding_decoder(t)                      # attention_type RelPosMHAXL branch, :793-796
+        if self.decoder_module == "transformer":
+            # reference make_transformer_src_tgt_masks, :367-425, handed over at :805-814 (the Mamba decoder ignores them)
+            memory_kpm = None
+            if wav_len is not None:
+                T = encoder_out.shape[1]
+                memory_kpm = ~length_to_mask(torch.round(wav_len.to(encoder_out.device) * T), T)
+            decoder_out, _, _ = self.decoder(tgt=t, memory=encoder_out, memory_mask=None, tgt_mask=lookahead_mask(tgt),
+                                             tgt_key_padding_mask=tgt.eq(pad_idx), memory_key_padding_mask=memory_kpm)
+            return encoder_out, decoder_out
         decoder_out, _, _ = self.decoder(tgt=t, memory=encoder_out)
         return encoder_out, decoder_out
 
     @torch.no_grad()
     def decode(self, tgt, encoder_out, enc_len=None):
+        """-> (prediction (batch, L, d_model), the last layer's cross-attention weights (batch, L, T) or None), reference
+        :821-866.  The Transformer decoder masks the future and the memory frames at or beyond ``enc_len``; the Mamba decoder
+        takes neither and returns no weights."""
         t = self.custom_tgt_module(tgt)
         t = t + self.positional_encoding_decoder(t)
+        if self.decoder_module == "transformer":
+            memory_kpm = None
+            if enc_len is not None:
+                memory_kpm = ~length_to_mask(torch.as_tensor(enc_len).to(encoder_out.device), encoder_out.shape[1])
+            prediction, _, attn = self.decoder(t, encoder_out, tgt_mask=lookahead_mask(tgt), memory_key_padding_mask=memory_kpm)
+            return prediction, attn[-1]
         prediction, _, attn = self.decoder(t, encoder_out)
         return prediction, attn[-1]
 
     @torch.no_grad()
-    def init_decode_state(self, encoder_out):
-        """The state ``decode_step`` advances: MambaDecoder.init_state over encoder_out (batch, T, d_model), all T rows."""
+    def init_decode_state(self, encoder_out, enc_lens=None):
+        """The state ``decode_step`` advances.  Mamba decoder: MambaDecoder.init_state over encoder_out (batch, T, d_model), all
+        T rows (``enc_lens`` is not used: the reference's Mamba decoder scans the padding too).  Transformer decoder:
+        TransformerDecoder.init_state, which projects encoder_out once per layer and masks the frames at or beyond
+        ``enc_lens`` (batch,) (None: none)."""
+        if self.decoder_module == "transformer":
+            return self.decoder.init_state(encoder_out, enc_lens)
         return self.decoder.init_state(encoder_out)
 
     @torch.no_grad()

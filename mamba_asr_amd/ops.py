@@ -896,6 +896,86 @@ def attn_step_torch(qkv, kc, vc, anc, t, H):
     return torch.matmul(p.unsqueeze(2), V).reshape(R, D).to(qkv.dtype)
 
 
+def _xattn_step_shapes(q, k, v, row_utt, enc_len, H):
+    """The shape checks both routes of xattn_step share -> (R, D, U, T)."""
+    if q.dim() != 2 or q.shape[0] < 1 or not q.is_contiguous():
+        raise RuntimeError(f"xattn_step: q must be a contiguous (R, D) tensor, got {tuple(q.shape)}")
+    R, D = q.shape
+    H = int(H)
+    if H < 1 or D % H:
+        raise RuntimeError(f"xattn_step: D = {D} is no multiple of H = {H}")
+    for name, c in (("k", k), ("v", v)):
+        if (c.dim() != 3 or c.shape[0] < 1 or c.shape[1] < 1 or c.shape[2] != D or c.dtype != q.dtype or c.device != q.device
+                or c.stride(2) != 1 or (c.shape[1] > 1 and c.stride(1) < D)
+                or (c.shape[0] > 1 and c.stride(0) < (c.shape[1] - 1) * c.stride(1) + D)):
+            raise RuntimeError(f"xattn_step: {name} must be a (U, T, {D}) {q.dtype} view on {q.device} with unit element stride and "
+                               f"non-overlapping frames, got {c.dtype} {tuple(c.shape)} strides {tuple(c.stride())}")
+    U, T = k.shape[0], k.shape[1]
+    if tuple(v.shape) != (U, T, D):
+        raise RuntimeError(f"xattn_step: k {tuple(k.shape)} and v {tuple(v.shape)} differ")
+    for name, c, n in (("row_utt", row_utt, R), ("enc_len", enc_len, U)):
+        if tuple(c.shape) != (n,) or c.dtype != torch.int32 or not c.is_contiguous() or c.device != q.device:
+            raise RuntimeError(f"xattn_step: {name} must be a contiguous int32 ({n},) tensor on {q.device}, got {c.dtype} "
+                               f"{tuple(c.shape)}")
+    return R, D, U, T
+
+
+def xattn_step(q, k, v, row_utt, enc_len, H):
+    """One decoding step of H-head cross-attention of R hypothesis rows over the encoder memory of their utterance
+    (cm_xattn_step).  q (R, D) bf16 / fp32; k, v (U, T, D) views of q's dtype, projected once per utterance
+    (any utterance / frame strides: the two halves of one (U, T, 2 D) GEMM result work); row_utt (R) int32: the utterance of
+    each row; enc_len (U) int32: its valid frames -> out (R, D) in q's dtype, softmax over frames s < min(enc_len[u], T) only;
+    a row with row_utt outside [0, U) or no valid frame is zero.  fp32 arithmetic; D / H in {32, 36, 64}, H <= 32, T < 8192."""
+    _dev_check(q, k, v, row_utt, enc_len)
+    if q.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"xattn_step: unsupported dtype {q.dtype} (fp32 / bf16)")
+    R, D, U, T = _xattn_step_shapes(q, k, v, row_utt, enc_len, H)
+    out = torch.empty((R, D), dtype=q.dtype, device=q.device)
+    a = N.XattnStepArgs()
+    a.R, a.U, a.T, a.D, a.H, a.io_dtype = R, U, T, D, int(H), _DT[q.dtype]
+    for name, c in (("k", k), ("v", v)):
+        fs = c.stride(1) if T > 1 else D
+        setattr(a, name + "_frame_stride", fs)
+        setattr(a, name + "_utt_stride", c.stride(0) if U > 1 else (T - 1) * fs + D)
+    a.q, a.k, a.v, a.row_utt, a.enc_len, a.out, a.stream = _ptr(q), _ptr(k), _ptr(v), _ptr(row_utt), _ptr(enc_len), _ptr(out), _stream()
+    _launch("cm_xattn_step", N.lib().cm_xattn_step, a, units=R * int(H) * T)
+    return out
+
+
+def xattn_step_torch(q, k, v, row_utt, enc_len, H, grouped=None):
+    """xattn_step's contract restated in torch (the CM_XATTN_STEP=0 route; any device, fp64 included): scores, a length mask,
+    softmax, the weighted sum.  Where row_utt is arange(U).repeat_interleave(B) -- a beam search's rows -- the B rows of an
+    utterance form one (B, dh) x (dh, T) product per head against the shared K and V (the grouped form); otherwise K and V are
+    gathered by row_utt.  ``grouped``: True / False when the caller knows which holds; None reads it from row_utt (one host
+    read).  Arithmetic in fp32 (fp64 for fp64 tensors), the result rounded to q's dtype."""
+    R, D, U, T = _xattn_step_shapes(q, k, v, row_utt, enc_len, H)
+    H = int(H)
+    dh = D // H
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    if grouped is None:
+        grouped = R % U == 0 and torch.equal(row_utt, torch.arange(U, dtype=torch.int32, device=q.device).repeat_interleave(R // U))
+    frames = torch.arange(T, device=q.device)
+    n = enc_len.clamp(max=T)
+    if grouped:
+        B = R // U
+        valid = (frames[None, :] < n[:, None]).view(U, 1, 1, T)
+        qh = q.to(ct).view(U, B, H, dh).permute(0, 2, 1, 3)                          # (U, H, B, dh)
+        K = k.to(ct).view(U, T, H, dh).permute(0, 2, 3, 1)                           # (U, H, dh, T)
+        V = v.to(ct).view(U, T, H, dh).permute(0, 2, 1, 3)                           # (U, H, T, dh)
+        V = V.masked_fill(~valid.view(U, 1, T, 1), 0.0)                              # a masked frame adds nothing, whatever it holds
+    else:
+        ok = (row_utt >= 0) & (row_utt < U)
+        take = row_utt.clamp(0, U - 1).long()
+        valid = (frames[None, :] < torch.where(ok, n[take], torch.zeros_like(n[take]))[:, None]).view(R, 1, 1, T)
+        qh = q.to(ct).view(R, H, 1, dh)
+        K = k[take].to(ct).view(R, T, H, dh).permute(0, 2, 3, 1)
+        V = v[take].to(ct).view(R, T, H, dh).permute(0, 2, 1, 3)
+        V = V.masked_fill(~valid.view(R, 1, T, 1), 0.0)
+    x = (torch.matmul(qh, K) / math.sqrt(dh)).masked_fill(~valid, float("-inf"))
+    p = torch.softmax(x, dim=-1).masked_fill(~valid, 0.0)                            # a row without a valid frame: zeros, not NaN
+    return torch.matmul(p, V).permute(0, 2, 1, 3).reshape(R, D).to(q.dtype)
+
+
 class CtcLossFn(torch.autograd.Function):
     """sum over the batch of the per-utterance CTC negative log-likelihoods (zero_infinity), gradient from the same call."""
 

@@ -1,9 +1,12 @@
-"""Greedy and beam S2S search on the stepped Mamba decoder: what a recipe's ``valid_search`` / ``test_search`` slot takes
+"""Greedy and beam S2S search on the stepped decoder (Mamba or Transformer): what a recipe's ``valid_search`` / ``test_search`` slot takes
 (reference train_S2S.py:388-394 unpacks ``hyps, _, _, _ = searcher(enc_out, wav_lens)``; the reference fills the slot with
 speechbrain's S2STransformerBeamSearcher, which re-runs ``TransformerASR.decode`` over the whole prefix for every token).
 
-Here each token costs one ``TransformerASR.decode_step``: the decoder's state (modules/Conmamba.py DecoderState) has a
-constant size, and the scan over the encoder frames is done once, by ``init_decode_state``.
+Here each token costs one ``TransformerASR.decode_step``.  Mamba decoder: the state (modules/Conmamba.py DecoderState) has a
+constant size, and the scan over the encoder frames is done once, by ``init_decode_state``.  Transformer decoder
+(modules/Transformer.py TransformerDecoderState): the encoder frames are projected to keys and values once per
+utterance by ``init_decode_state``, which also takes the utterances' lengths; per token cm_xattn_step attends to them and
+cm_attn_step to the prefix's own cache, and a reorder moves no key or value.
 
 Joint CTC/attention decoding (the recipes' ``ctc_weight_decode``): ``CTCPrefixScorer`` gives, for every hypothesis row, the
 CTC prefix score of each possible next token from the encoder's CTC head (native kernels cm_ctc_prefix_score /
@@ -143,7 +146,8 @@ class S2SGreedySearcher:
     log_probs (batch, steps) fp32: each chosen token's log-probability, 0 behind a row's <eos>.
 
     ``modules`` = [transformer (TransformerASR), seq_lin]: the default per-token function is
-    log_softmax(seq_lin(transformer.decode_step(tokens, state))) on the state of transformer.init_decode_state.  Both are
+    log_softmax(seq_lin(transformer.decode_step(tokens, state))) on the state of transformer.init_decode_state (called with
+    enc_len as well where the transformer's decoder is the Transformer one, which masks the frames beyond it).  Both are
     injectable -- ``init_fn(enc_states) -> state`` and ``step_fn(tokens (batch,) long, state) -> (log_probs (batch, vocab),
     state)`` -- which is also how the host logic is tested without a GPU.
 
@@ -184,15 +188,25 @@ class S2SGreedySearcher:
                 raise ValueError(f"{type(self).__name__} needs modules=[transformer, seq_lin] (or step_fn and init_fn)")
             transformer, seq_lin = modules
 
-            def default_init(enc_states):
-                return transformer.init_decode_state(enc_states)
+            if init_fn is None and getattr(transformer, "decoder_module", "mamba") == "transformer":
+                self._init_takes_lens = True                                      # the memory frames beyond enc_len are masked
+
+            def default_init(enc_states, enc_lens=None):
+                if enc_lens is None:
+                    return transformer.init_decode_state(enc_states)
+                return transformer.init_decode_state(enc_states, enc_lens)
 
             default_step = _default_step(transformer, seq_lin, self.temperature)
 
             init_fn, step_fn = init_fn or default_init, step_fn or default_step
         self.init_fn, self.step_fn = init_fn, step_fn
+        self._init_takes_lens = getattr(self, "_init_takes_lens", False)
         self.bos_index, self.eos_index = int(bos_index), int(eos_index)
         self.min_decode_ratio, self.max_decode_ratio = float(min_decode_ratio), float(max_decode_ratio)
+
+    def _init_state(self, enc_states, enc_lens):
+        """A user's ``init_fn(enc_states)`` keeps its one-argument call; the default one of a Transformer decoder gets enc_lens."""
+        return self.init_fn(enc_states, enc_lens) if self._init_takes_lens else self.init_fn(enc_states)
 
     @torch.no_grad()
     def __call__(self, enc_states, wav_lens) -> Tuple[List[List[int]], torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -202,7 +216,7 @@ class S2SGreedySearcher:
         # the truncations, in fp64: in fp32 the product 0.3 * 10 falls just below 3
         min_steps = torch.floor(self.min_decode_ratio * enc_lens.double()).long()   # per row
         max_steps = int(torch.floor(self.max_decode_ratio * enc_lens.double().max()))   # the loop bound: read once, before the loop
-        state = self.init_fn(enc_states)
+        state = self._init_state(enc_states, enc_lens)
         joint = self.ctc_weight > 0.0
         if joint:
             ctc_state = self.ctc_scorer.init(self.ctc_fn(enc_states), enc_lens)
@@ -346,7 +360,7 @@ class S2SBeamSearcher(S2SGreedySearcher):
         min_steps = torch.floor(self.min_decode_ratio * enc_lens.double()).long()
         max_steps = int(torch.floor(self.max_decode_ratio * enc_lens.double().max()))
         idx = torch.arange(U, device=dev).repeat_interleave(B)
-        state = self.init_fn(enc_states).reorder(idx)                            # the prefill runs once per utterance
+        state = self._init_state(enc_states, enc_lens).reorder(idx)                          # the prefill runs once per utterance
         joint = self.ctc_weight > 0.0
         if joint:
             ctc_state = self.ctc_scorer.init(self.ctc_fn(enc_states), enc_lens, row_utt=idx)
