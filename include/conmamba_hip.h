@@ -900,6 +900,27 @@ typedef struct cm_ln_pw_glu_args {
 
 int cm_ln_pw_glu(const cm_ln_pw_glu_args *args);
 
+/* The same seam with the mixer's out_proj in front: y = ycat @ proj_w^T is formed inside the kernel (rounded to bf16 as a
+ * GEMM's output would be) and never reaches memory.  ycat (rows, proj_k) bf16 contiguous; proj_w (256, proj_k) bf16 packed
+ * with cm_ffn_pack_weights; proj_k a multiple of 128, at most 8192.  The other fields are cm_ln_pw_glu_args'.  out and
+ * x_out may overlap no input, except x_out == x. */
+typedef struct cm_ln_pw_glu_mix_args {
+    int32_t rows, dim;
+    const float *x;
+    const float *ln_g, *ln_b;
+    const void  *w;
+    const float *bias;
+    float *x_out;
+    void  *out;
+    float alpha, eps;
+    void *stream;
+    const void *ycat;
+    const void *proj_w;
+    int32_t proj_k;
+} cm_ln_pw_glu_mix_args;
+
+int cm_ln_pw_glu_mix(const cm_ln_pw_glu_mix_args *args);
+
 /* ---------------------------------------------------------------------------------------
  * First block of the CNN front end (speechbrain ConvolutionFrontEnd as configured at reference
  * hparams/CTC/conmamba_large.yaml:187-194): Conv2d(1 -> C, 3x3, stride 2 in time and frequency, reflect

@@ -213,6 +213,14 @@ class LnPwGluArgs(C.Structure):
     ]
 
 
+class LnPwGluMixArgs(C.Structure):
+    _fields_ = [
+        ("rows", i32), ("dim", i32), ("x", fp), ("ln_g", fp), ("ln_b", fp), ("w", vp), ("bias", fp),
+        ("x_out", fp), ("out", vp), ("alpha", C.c_float), ("eps", C.c_float), ("stream", vp),
+        ("ycat", vp), ("proj_w", vp), ("proj_k", i32),
+    ]
+
+
 class CnnFrontArgs(C.Structure):
     _fields_ = [
         ("batch", i32), ("T", i32), ("F", i32), ("C1", i32), ("C2", i32), ("pad_", i32),
@@ -389,6 +397,7 @@ SYMBOLS = [
     ("cm_add_layernorm", C.c_int, [C.POINTER(AddLnArgs)]),
     ("cm_glu_dwconv_ln_gelu", C.c_int, [C.POINTER(GluDwconvArgs)]),
     ("cm_ln_pw_glu", C.c_int, [C.POINTER(LnPwGluArgs)]),
+    ("cm_ln_pw_glu_mix", C.c_int, [C.POINTER(LnPwGluMixArgs)]),
     ("cm_causal_conv1d_update", C.c_int, [C.POINTER(ConvUpdateArgs)]),
     ("cm_selective_state_update", C.c_int, [C.POINTER(StateUpdateArgs)]),
     ("cm_mamba_step", C.c_int, [C.POINTER(MambaStepArgs)]),

@@ -10,6 +10,11 @@
 // 64 features x 64 tokens of BOTH halves with v_mfma_f32_16x16x32_bf16 (weights as the A operand straight from their
 // packed image in L2, as in cm_ffn_fused), so a lane holds matching (value, gate) pairs and the GLU happens in
 // registers; only x (once in, once out) and the D-wide bf16 g touch HBM.
+//
+// cm_ln_pw_glu_mix puts the mixer's out_proj in front (MIX instantiation): y = ycat @ proj_w^T is formed per 64-token tile by the
+// same waves (wave = 64 features x 64 tokens, weights as the A operand from their packed image), ycat arriving in 128-column chunks
+// by LDS-DMA into two stages that overlay the token tile, and is laid into that tile rounded to bf16 -- the rounding the library
+// GEMM's output had -- so phase 0 reads y from LDS and y never reaches HBM.
 #include "cm_common.h"
 
 
@@ -19,6 +24,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 constexpr int D = 256;        // d_model
 constexpr int TOK = 64;       // tokens per workgroup
@@ -29,9 +35,37 @@ __device__ __forceinline__ uint32_t pack2(float a, float b) {
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
 }
 
-// OCC: workgroups per CU the register budget is cut for; PF: weight-fragment ring depth (k-steps in flight)
-template <int OCC, int PF>
-__global__ __launch_bounds__(256, OCC) void ln_pw_glu_kernel(const cm_ln_pw_glu_args p) {
+// ---- the projection phase's ycat stream (MIX).  A chunk is 64 tokens x 128 columns = 64 rows of 256 bytes, stored with the XOR
+// swizzle of wgrad_bf16.hip's image (16-byte piece ch of row r sits at piece ch ^ swz(r)): the 16 lanes of a ds_read_b128 token
+// fragment (rows r .. r + 15, one logical piece) then cover all 64 banks once.  Two stages of 16 KB overlay the 33 KB token tile.
+constexpr int CK = 128;                   // ycat columns per chunk
+constexpr int STAGE = TOK * CK * 2;       // bytes per stage
+static_assert(2 * STAGE <= TOK * XS * 2, "the two ycat stages must fit the token tile they overlay");
+
+struct mix_extra {
+    const void *ycat;                     // (rows, proj_k) bf16
+    const void *proj_w;                   // (256, proj_k) bf16, packed (cm_ffn_pack_weights)
+    int32_t proj_k;
+};
+
+__device__ __forceinline__ u32x4 raw_rsrc(const void *base, uint32_t bytes) {
+    const uint64_t a = reinterpret_cast<uint64_t>(base);
+    return u32x4{(uint32_t)a, (uint32_t)(a >> 32) & 0xffffu, bytes, 0x00020000u};
+}
+// One LDS-DMA instruction (16 bytes per lane, the wave's 1 KB lands lane-linear at lds_addr), issued where it is written; its
+// arrival is waited for by hand (see wgrad_bf16.hip: through the builtin the compiler drains vmcnt in front of every ds_read).
+__device__ __forceinline__ void dma16(const u32x4 rsrc, uint32_t lds_addr, int voff) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "s"(lds_addr), "v"(voff), "s"(rsrc)
+                 : "memory");
+}
+
+// OCC: workgroups per CU the register budget is cut for; PF: weight-fragment ring depth (k-steps in flight); MIX: y is formed
+// here from (ycat, proj_w) instead of read from p.y
+template <int OCC, int PF, bool MIX>
+__global__ __launch_bounds__(256, OCC) void ln_pw_glu_kernel(const cm_ln_pw_glu_args p, const mix_extra mx) {
     __shared__ __attribute__((aligned(16))) uint16_t xn[TOK * XS];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -53,8 +87,84 @@ __global__ __launch_bounds__(256, OCC) void ln_pw_glu_kernel(const cm_ln_pw_glu_
                                                      wr, vl, (((half * D + wave * 64) / 16 + 2 * ps + mb) * (D / 32) + ks) * 1024, 0));
     };
     bf16x8 wq[PF][2];
+    if constexpr (MIX) {
+        // ---- phase A: Y (64 tokens, 256) = ycat tile @ proj_w^T.  Step g = 2 * k-tile + feature pair: the wave's 64 features are
+        // four 16-row bands, two per step (the ring stays 2 fragments wide as below); 8 steps per 128-column chunk.
+        static_assert(PF == 2, "the projection phase's ring indexing assumes two steps in flight");
+        const int K = mx.proj_k, kt = K / 32, nch = K / CK, nstep = 2 * kt;
+        const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(mx.proj_w), 0, D * K * 2, 0x00020000);
+        auto pload = [&](int g, bf16x8(&dst)[2]) {
+            g = min(g, nstep - 1);                                    // the ring's last refills: a valid step, never used
+            const int ks = g >> 1, mp = g & 1;
 #pragma unroll
-    for (int s = 0; s < PF; ++s) wload(0, s, wq[s]);
+            for (int mb = 0; mb < 2; ++mb)
+                dst[mb] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(pr, vl, ((wave * 4 + mp * 2 + mb) * kt + ks) * 1024, 0));
+        };
+        // the tile's rows of ycat behind a descriptor of their own: rows past the end of a tail tile read as zero
+        const int vrows = min(TOK, M - t0);
+        const u32x4 yr = raw_rsrc(reinterpret_cast<const unsigned char *>(mx.ycat) + (int64_t)t0 * K * 2, (uint32_t)(vrows * K * 2));
+        const uint32_t lds0 = (uint32_t)reinterpret_cast<uintptr_t>(&xn[0]);    // the LDS offset is the low half of the flat address
+        // a chunk's 16 pieces of 4 rows: this wave fills pieces 4 wave .. 4 wave + 3; lane -> row 4 piece + lane / 16, stored piece
+        // lane % 16 = logical piece ^ swz(row)
+        int go[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = 4 * (4 * wave + i) + lq;
+            go[i] = row * K * 2 + 16 * (l15 ^ (((row & 3) << 2) | ((row >> 2) & 3)));
+        }
+        auto request = [&](int c) {                                   // every piece of the chunk before any wait
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dma16(yr, lds0 + (uint32_t)((c & 1) * STAGE + (4 * wave + i) * 1024), go[i] + c * (CK * 2));
+        };
+        request(0);
+#pragma unroll
+        for (int s = 0; s < PF; ++s) pload(s, wq[s]);
+        f32x4 acc[4][4];
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb) acc[mb][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // token fragments: lane = token nb * 16 + l15 (swz depends on row % 16 = l15 only), k = 32 kk + 8 lq .. + 7
+        const unsigned char *xb = reinterpret_cast<const unsigned char *>(xn);
+        const int yrow = l15 * (CK * 2), yswz = ((l15 & 3) << 2) | (l15 >> 2);
+        auto read_y = [&](int st, int kk, bf16x8(&bf)[4]) {
+            const int off = st * STAGE + yrow + 16 * ((kk * 4 + lq) ^ yswz);
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb) bf[nb] = *reinterpret_cast<const bf16x8 *>(xb + off + nb * 16 * (CK * 2));
+        };
+        for (int c = 0; c < nch; ++c) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's pieces of chunk c (and the ring's two steps)
+            lds_barrier();                                            // everyone's pieces are in; everyone has read the other stage
+            if (c + 1 < nch) request(c + 1);
+            const int st = c & 1;
+            bf16x8 bf[4];                                             // one set: a second would not fit beside 64 accumulators
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                const int kk = s >> 1, mp = s & 1;
+                if (mp == 0) read_y(st, kk, bf);
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                    for (int nb = 0; nb < 4; ++nb)
+                        acc[mp * 2 + mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wq[s % PF][mb], bf[nb], acc[mp * 2 + mb][nb], 0, 0, 0);
+                pload(c * 8 + s + PF, wq[s % PF]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        lds_barrier();                                                // every wave has read its last fragments: the stages are dead
+        // Y rounded to bf16 into the token tile: lane holds token nb*16 + l15, features wave*64 + mb*16 + lq*4 + j
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb)
+                *reinterpret_cast<uint2 *>(xn + (nb * 16 + l15) * XS + wave * 64 + mb * 16 + lq * 4) =
+                    uint2{pack2(acc[mb][nb][0], acc[mb][nb][1]), pack2(acc[mb][nb][2], acc[mb][nb][3])};
+    }
+    if constexpr (MIX) lds_barrier();
+    else {
+#pragma unroll
+        for (int s = 0; s < PF; ++s) wload(0, s, wq[s]);
+    }
 
     // ---- phase 0: x <- x + alpha*y (written back), xn = LayerNorm(x) in bf16.  Wave w owns tokens 16w .. 16w+15, four per
     // round; a row of 16 lanes holds one token (16 floats per lane): statistics = in-lane adds + four DPP steps.
@@ -67,8 +177,10 @@ __global__ __launch_bounds__(256, OCC) void ln_pw_glu_kernel(const cm_ln_pw_glu_
             for (int i = 0; i < 4; ++i) {
                 const int col = (l15 + 16 * i) * 4;
                 float4 x4 = *reinterpret_cast<const float4 *>(p.x + (int64_t)tok * D + col);
-                if (yv) {
-                    const uint2 a = *reinterpret_cast<const uint2 *>(yv + (int64_t)tok * D + col);
+                if (MIX || yv) {
+                    // MIX: the lane reads the 8 bytes of the tile it overwrites with xn below
+                    const uint2 a = MIX ? *reinterpret_cast<const uint2 *>(xn + (wave * 16 + rd * 4 + lq) * XS + col)
+                                        : *reinterpret_cast<const uint2 *>(yv + (int64_t)tok * D + col);
                     x4.x = fmaf(p.alpha, cm_bf16_lo(a.x), x4.x);
                     x4.y = fmaf(p.alpha, cm_bf16_hi(a.x), x4.y);
                     x4.z = fmaf(p.alpha, cm_bf16_lo(a.y), x4.z);
@@ -107,6 +219,10 @@ __global__ __launch_bounds__(256, OCC) void ln_pw_glu_kernel(const cm_ln_pw_glu_
                 *reinterpret_cast<uint2 *>(dst + col) = pk;
             }
         }
+    }
+    if constexpr (MIX) {                                              // (requested here: beside phase 0's rows the ring would spill)
+#pragma unroll
+        for (int s = 0; s < PF; ++s) wload(0, s, wq[s]);
     }
     lds_barrier();
 
@@ -192,10 +308,40 @@ extern "C" int cm_ln_pw_glu(const cm_ln_pw_glu_args *args) {
     // cm_debug_set(41) keeps the old shape for A/B runs.
 #ifdef CM_ABLATE
     if (cm_debug_get() == 41) {
-        hipLaunchKernelGGL((ln_pw_glu_kernel<3, 4>), grid, dim3(256), 0, st, a);
+        hipLaunchKernelGGL((ln_pw_glu_kernel<3, 4, false>), grid, dim3(256), 0, st, a, mix_extra{});
         return cm_launch_status("cm_ln_pw_glu");
     }
 #endif
-    hipLaunchKernelGGL((ln_pw_glu_kernel<4, 2>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((ln_pw_glu_kernel<4, 2, false>), grid, dim3(256), 0, st, a, mix_extra{});
     return cm_launch_status("cm_ln_pw_glu");
+}
+
+extern "C" int cm_ln_pw_glu_mix(const cm_ln_pw_glu_mix_args *args) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "ln_pw_glu_mix: args is NULL");
+    const cm_ln_pw_glu_mix_args &m = *args;
+    CM_REQUIRE(m.rows > 0 && m.x && m.ln_g && m.ln_b && m.w && m.bias && m.out && m.ycat && m.proj_w, CM_EINVAL,
+               "ln_pw_glu_mix: bad sizes or NULL tensor");
+    CM_REQUIRE(m.dim == D, CM_EUNSUPPORTED, "ln_pw_glu_mix: d_model must be 256 (got %d)", m.dim);
+    CM_REQUIRE(m.proj_k >= CK && m.proj_k % CK == 0 && m.proj_k <= 8192, CM_EUNSUPPORTED,
+               "ln_pw_glu_mix: proj_k must be a multiple of 128, at most 8192 (got %d)", m.proj_k);
+    CM_REQUIRE(cm_aligned(m.x, 16) && cm_aligned(m.ln_g, 16) && cm_aligned(m.ln_b, 16) && cm_aligned(m.w, 16) && cm_aligned(m.bias, 16) &&
+                   cm_aligned(m.out, 16) && cm_aligned(m.ycat, 16) && cm_aligned(m.proj_w, 16) && (!m.x_out || cm_aligned(m.x_out, 16)),
+               CM_EALIGN, "ln_pw_glu_mix: tensors must be 16-byte aligned");
+    // a workgroup reads its rows of ycat and x before it writes them, other workgroups' rows at any time: the outputs may
+    // overlap no input, except x_out == x (in place)
+    const auto overlap = [](const void *a, int64_t na, const void *b, int64_t nb) {
+        const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+        return a && b && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
+    };
+    const int64_t nx = (int64_t)m.rows * D * 4, no = (int64_t)m.rows * D * 2, ny = (int64_t)m.rows * m.proj_k * 2;
+    CM_REQUIRE(!overlap(m.out, no, m.x, nx) && !overlap(m.out, no, m.ycat, ny) && !overlap(m.out, no, m.x_out, nx) &&
+                   !overlap(m.x_out, nx, m.ycat, ny) && (m.x_out == m.x || !overlap(m.x_out, nx, m.x, nx)),
+               CM_EALIGN, "ln_pw_glu_mix: out / x_out overlap an input (only x_out == x is allowed)");
+    cm_ln_pw_glu_args a{};
+    a.rows = m.rows, a.dim = m.dim, a.x = m.x, a.y = nullptr, a.ln_g = m.ln_g, a.ln_b = m.ln_b, a.w = m.w, a.bias = m.bias;
+    a.x_out = m.x_out, a.out = m.out, a.alpha = m.alpha, a.eps = m.eps, a.stream = m.stream;
+    const mix_extra mx{m.ycat, m.proj_w, m.proj_k};
+    // four workgroups per CU as above: the projection phase keeps 64 accumulators + the 2-deep ring + two sets of token fragments
+    hipLaunchKernelGGL((ln_pw_glu_kernel<4, 2, true>), dim3((a.rows + TOK - 1) / TOK), dim3(256), 0, reinterpret_cast<hipStream_t>(a.stream), a, mx);
+    return cm_launch_status("cm_ln_pw_glu_mix");
 }

@@ -88,6 +88,10 @@ class _LayerCache:
         self.pw_packed = None                                     # cm_ln_pw_glu's fragment-tiled pointwise-conv weight
         if dtype == torch.bfloat16 and self.pw_w.is_cuda and tuple(self.pw_w.shape) == (512, 256) and self.pw_bf is not None:
             self.pw_packed = ops.PackedWeight(self.pw_w)
+        self.out_packed = None                                    # out_proj inside cm_ln_pw_glu (mixer_tail): no bias, no layer scale
+        if (self.pw_packed is not None and self.out_cat.is_cuda and self.out_cat.shape[0] == 256 and self.out_cat.shape[1] % 128 == 0
+                and self.out_cat.shape[1] <= 8192 and self.out_bias is None and self.gamma is None):
+            self.out_packed = ops.PackedWeight(self.out_cat)
         self.in_bias_f = None if m.in_proj.bias is None else f(m.in_proj.bias)
         self.out_bias_f = None if m.out_proj.bias is None else f(m.out_proj.bias)
         self.dw_w, self.dw_b = f(cm.conv.weight), f(cm.conv.bias)
@@ -176,9 +180,33 @@ def _scan_dirs(c: _LayerCache, ucat, ycat, batch, seqlen, xdbl=None):
     return dirs
 
 
-def bimamba_fused(c: _LayerCache, h, batch, seqlen, xz=None):
+# the mixer's out_proj inside cm_ln_pw_glu (cm_ln_pw_glu_mix); CM_MIXER_TAIL=0 = library GEMM + cm_ln_pw_glu
+USE_MIXER_TAIL = os.environ.get("CM_MIXER_TAIL", "1") == "1"
+
+
+def _out_proj(c: _LayerCache, ycat):
+    """Both directions' gated scan outputs (rows, 2E) -> mixer output (rows, D): 0.5*(y_f + y_b) @ W_out^T, one library GEMM."""
+    y = ycat @ c.out_cat.t()
+    if c.out_bias is not None:
+        y = y + c.out_bias
+    if c.gamma is not None:
+        y = y * c.gamma.to(y.dtype)
+    return y
+
+
+def mixer_tail(c: _LayerCache, x, ycat):
+    """The mixer's tail on the residual stream: x += out_proj(ycat); conv-module LN; pointwise conv; GLU.  x (rows, D) fp32, updated in
+    place; ycat (rows, 2E) bf16 contiguous.  One kernel (cm_ln_pw_glu with the projection in front) when out_proj has neither bias nor
+    layer scale, else the library GEMM and cm_ln_pw_glu.  Returns the gated (rows, D) bf16 tensor."""
+    if USE_MIXER_TAIL and c.out_packed is not None:
+        return ops.ln_pw_glu(x, None, 1.0, c.cm_ln, c.pw_packed, c.pw_bf, ycat=ycat, out_w=c.out_packed)
+    return ops.ln_pw_glu(x, _out_proj(c, ycat), 1.0, c.cm_ln, c.pw_packed, c.pw_bf)
+
+
+def bimamba_fused(c: _LayerCache, h, batch, seqlen, xz=None, want_ycat=False):
     """h: LN'd input (rows, D) in the compute dtype -> mixer output (rows, D) (reference bimamba.py:192-253).
-    ``xz``: in_proj's output when the caller already has it (cm_ffn_fused's projection epilogue)."""
+    ``xz``: in_proj's output when the caller already has it (cm_ffn_fused's projection epilogue).
+    ``want_ycat``: stop in front of out_proj and return the scan's (rows, 2E) output (for mixer_tail)."""
     E, R, N = c.d_inner, c.dt_rank, c.d_state
     rows = batch * seqlen
     if xz is None:
@@ -197,12 +225,9 @@ def bimamba_fused(c: _LayerCache, h, batch, seqlen, xz=None):
     ycat = torch.empty_like(ucat)
     dirs = _scan_dirs(c, ucat, ycat, batch, seqlen, xdbl)
     ops.scan_cl_fwd(dirs, z=xz3[:, :, E:], delta_softplus=True)
-    y = ycat.view(rows, 2 * E) @ c.out_cat.t()                           # 0.5*(y_f + y_b) @ W_out^T
-    if c.out_bias is not None:
-        y = y + c.out_bias
-    if c.gamma is not None:
-        y = y * c.gamma.to(y.dtype)
-    return y
+    if want_ycat:
+        return ycat.view(rows, 2 * E)
+    return _out_proj(c, ycat.view(rows, 2 * E))
 
 
 # cm_ffn_fused: the whole feed-forward module (LayerNorm, both Linears, GELU, scaled residual, the next LayerNorm) in
@@ -226,15 +251,16 @@ def _layer_forward_ffn_fused(c, x, batch, seqlen, dtype, final_ln=None):
         inp = getattr(c, "in_packed_s", None)
     else:
         inp = c.in_packed
+    seam = USE_LN_PW_GLU and c.pw_packed is not None and dtype == torch.bfloat16
     if c.in_packed is not None:                                                                                # x += 0.5 ffn1 ; norm1 ; in_proj
         _, xz = ops.ffn_fused(x, f1["ln"], f1["w1p"], f1["b1f"], f1["w2p"], f1["b2f"], alpha=0.5, norm2=c.norm1, proj_w=inp)
-        y = bimamba_fused(c, None, batch, seqlen, xz=xz)
+        y = bimamba_fused(c, None, batch, seqlen, xz=xz, want_ycat=seam)
     else:
         _, h = ops.ffn_fused(x, f1["ln"], f1["w1p"], f1["b1f"], f1["w2p"], f1["b2f"], alpha=0.5, norm2=c.norm1)   # x += 0.5 ffn1 ; norm1
-        y = bimamba_fused(c, h, batch, seqlen)
-    if USE_LN_PW_GLU and c.pw_packed is not None and y.dtype == torch.bfloat16 and y.is_contiguous():
+        y = bimamba_fused(c, h, batch, seqlen, want_ycat=seam)
+    if seam:
         # x += mamba ; conv-module LN ; pointwise conv ; GLU -- one kernel, the 2D-wide tensor never exists
-        gl = ops.ln_pw_glu(x, y, 1.0, c.cm_ln, c.pw_packed, c.pw_bf)
+        gl = mixer_tail(c, x, y)
         g = ops.glu_dwconv_ln_gelu(gl.view(batch, seqlen, D), c.dw_w, c.dw_b, c.cm_ln2[0], c.cm_ln2[1], c.cm_ln2[2],
                                    weight_t=c.dw_wt, glu_done=True, lin_w=c.lin_packed, lin_b=c.lin_bf)
     else:
@@ -413,8 +439,7 @@ def _encoder_forward_joined(encoder, src, dtype, ns, paired=False):
             for pi, (b0, b1) in enumerate(parts):
                 with torch.cuda.stream(streams[pi]):
                     xp = x[b0 * seqlen:b1 * seqlen]
-                    y = ycat[b0:b1].view(-1, 2 * E) @ c.out_cat.t()
-                    gl = ops.ln_pw_glu(xp, y, 1.0, c.cm_ln, c.pw_packed, c.pw_bf)
+                    gl = mixer_tail(c, xp, ycat[b0:b1].view(-1, 2 * E))
                     g = ops.glu_dwconv_ln_gelu(gl.view(b1 - b0, seqlen, D), c.dw_w, c.dw_b, c.cm_ln2[0], c.cm_ln2[1], c.cm_ln2[2],
                                                weight_t=c.dw_wt, glu_done=True, lin_w=c.lin_packed, lin_b=c.lin_bf)
                     yl = g.view(-1, D) if c.lin_packed is not None else torch.addmm(c.lin_b, g.view(-1, D), c.lin_w.t())

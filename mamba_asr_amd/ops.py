@@ -1536,11 +1536,13 @@ class LnActDropFn(torch.autograd.Function):
         return (dx.view(shape) if dx is not None else None), dg.to(weight.dtype), db.to(weight.dtype), None, None, None, None
 
 
-def ln_pw_glu(x, y, alpha, norm, w, bias, x_out=None):
+def ln_pw_glu(x, y, alpha, norm, w, bias, x_out=None, ycat=None, out_w=None):
     """Mixer -> convolution-module seam (cm_ln_pw_glu): x_out = x + alpha*y; g = GLU(LayerNorm(x_out) @ W^T + bias).
     x (rows, 256) fp32 contiguous; y (rows, 256) bf16 or None; norm = (weight, bias, eps); w: PackedWeight of the
-    (512, 256) pointwise-conv weight; bias (512) fp32.  x_out defaults to x (in place).  Returns g (rows, 256) bf16."""
-    _dev_check(x, y, bias)
+    (512, 256) pointwise-conv weight; bias (512) fp32.  x_out defaults to x (in place).  Returns g (rows, 256) bf16.
+    With ``ycat`` (rows, K) bf16 contiguous and ``out_w`` (PackedWeight of a (256, K) matrix, K a multiple of 128) instead of
+    ``y``, y = ycat @ out_w^T is formed inside the kernel (cm_ln_pw_glu_mix) and never written."""
+    _dev_check(x, y, bias, ycat)
     rows, d = x.shape
     if x.dtype != torch.float32 or not x.is_contiguous() or d != 256:
         raise RuntimeError("ln_pw_glu: x must be a contiguous fp32 (rows, 256) tensor")
@@ -1551,6 +1553,19 @@ def ln_pw_glu(x, y, alpha, norm, w, bias, x_out=None):
     g_, b_, bs = _f32c(norm[0]), _f32c(norm[1]), _f32c(bias)
     xo = x if x_out is None else x_out
     out = torch.empty((rows, d), dtype=torch.bfloat16, device=x.device)
+    if (ycat is None) != (out_w is None) or (ycat is not None and y is not None):
+        raise RuntimeError("ln_pw_glu: give either y, or ycat together with out_w")
+    if ycat is not None:
+        if ycat.dtype != torch.bfloat16 or not ycat.is_contiguous() or ycat.dim() != 2 or ycat.shape[0] != rows:
+            raise RuntimeError("ln_pw_glu: ycat must be a contiguous bf16 (rows, K) tensor")
+        if not isinstance(out_w, PackedWeight) or out_w.layout != 16 or out_w.shape != (256, ycat.shape[1]):
+            raise RuntimeError("ln_pw_glu: out_w must be a PackedWeight (16-row tiles) of shape (256, K)")
+        m = N.LnPwGluMixArgs()
+        m.rows, m.dim, m.x, m.ln_g, m.ln_b, m.w, m.bias = rows, d, _ptr(x), _ptr(g_), _ptr(b_), _ptr(w.data), _ptr(bs)
+        m.x_out, m.out, m.alpha, m.eps, m.stream = _ptr(xo), _ptr(out), float(alpha), float(norm[2]), _stream()
+        m.ycat, m.proj_w, m.proj_k = _ptr(ycat), _ptr(out_w.data), ycat.shape[1]
+        _launch("cm_ln_pw_glu", N.lib().cm_ln_pw_glu_mix, m, units=rows)     # the same kernel with a phase in front
+        return out
     a = N.LnPwGluArgs()
     a.rows, a.dim, a.x, a.y, a.ln_g, a.ln_b, a.w, a.bias = rows, d, _ptr(x), _ptr(y), _ptr(g_), _ptr(b_), _ptr(w.data), _ptr(bs)
     a.x_out, a.out, a.alpha, a.eps, a.stream = _ptr(xo), _ptr(out), float(alpha), float(norm[2]), _stream()

@@ -290,8 +290,7 @@ def encoder_forward_seq_parallel_fused(encoder, src_shard, group):
                     redo.append(dd)
             if redo:
                 ops.scan_cl_fwd(redo, z=xz[:, :, E:], delta_softplus=True)                 # pass 2: from the carry
-            y = ycat.view(batch * T, 2 * E) @ c.out_cat.t()
-            gl = ops.ln_pw_glu(x, y, 1.0, c.cm_ln, c.pw_packed, c.pw_bf)
+            gl = fused.mixer_tail(c, x, ycat.view(batch * T, 2 * E))
             gl3 = gl.view(batch, T, D)
             left, right = exchange_halo(gl3, 15, 15, group, dim=1)
             g = ops.glu_dwconv_ln_gelu(torch.cat([left, gl3, right], dim=1), c.dw_w, c.dw_b, c.cm_ln2[0], c.cm_ln2[1], c.cm_ln2[2],
