@@ -1069,7 +1069,13 @@ typedef struct cm_ffn_args {
     int32_t tokens;                     /* layout 1: tokens per workgroup, 0 / 64 or 32 (32: for launches of fewer than ~400 64-token
                                            workgroups, which leave CUs idle) */
     const uint64_t *seed_epoch;         /* optional device word added into seed1 / seed2 (cm_ffn_elem_args.seed_epoch)       */
+    int32_t flags;                      /* CM_FFN_* bits                                                                  */
+    int32_t reserved_;
 } cm_ffn_args;
+/* cm_ffn_args.flags.  Without it, when alpha is a power of two, the inference forward (layout 0) fetches the residual rows once and
+   carries them in the second GEMM's accumulators (scaled by 1 / alpha, which is exact); with it, or any other alpha, the rows are
+   loaded a second time behind the last GEMM, as before.  The results differ in the order of the fp32 residual add only. */
+#define CM_FFN_RELOAD_RESIDUAL 1
 
 int cm_ffn_fused(const cm_ffn_args *args);
 /* row-major (rows, cols) bf16 -> the 32-row x 16-column fragment-tile image of cm_ffn_args.layout = 1 (rows % 32 == 0, cols % 16 == 0) */

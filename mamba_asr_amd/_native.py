@@ -270,6 +270,9 @@ class GemmArgs(C.Structure):
     ]
 
 
+CM_FFN_RELOAD_RESIDUAL = 1           # cm_ffn_args.flags
+
+
 class FfnArgs(C.Structure):
     _fields_ = [
         ("rows", i32), ("dim", i32), ("hidden", i32), ("h_dtype", i32),
@@ -279,6 +282,7 @@ class FfnArgs(C.Structure):
         ("proj_dim", i32), ("stream", vp), ("proj_w", vp), ("proj_b", fp), ("proj_out", vp),
         ("pre_out", vp), ("xn_out", vp), ("p1", C.c_float), ("p2", C.c_float), ("seed1", C.c_uint64), ("seed2", C.c_uint64),
         ("stats_out", fp), ("layout", i32), ("tokens", i32), ("seed_epoch", vp),
+        ("flags", i32), ("reserved_", i32),
     ]
 
 

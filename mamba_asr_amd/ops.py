@@ -1721,6 +1721,9 @@ FFN_LAYOUT = 32 if os.environ.get("CM_FFN_MFMA32", "0") == "1" else 16
 # images).  Off by default: alone it wins below ~12 k rows (8000 rows: 28.5 / 19.4 vs 34.4 / 24.4 us; 16000: 42.8 / 31.2 vs 40.5 / 28.8),
 # in the encoder at 16 x 40 s (two parts of 8000 rows whose kernels share the chip) it changes nothing (4.78 vs 4.78 ms)
 SMALL_FFN_ROWS = int(os.environ.get("CM_FFN_SMALL_ROWS", "0"))
+# cm_ffn_fused (16x16x32 kernel, inference, alpha a power of two) fetches the residual rows once and carries them in the second GEMM's
+# accumulators; CM_FFN_RESID_ACC=0 = the rows are loaded a second time behind the last GEMM (cm_ffn_args.flags, per launch)
+FFN_RESID_ACC = os.environ.get("CM_FFN_RESID_ACC", "1") == "1"
 
 
 class PackedWeight:
@@ -1751,7 +1754,8 @@ class PackedWeight:
 
 
 def ffn_fused(x, pre_norm, w1, b1, w2, b2, alpha=0.5, addend=None, add_scale=1.0, norm1=None, norm2=None,
-              x_out=None, want_h=True, h_dtype=torch.bfloat16, proj_w=None, proj_b=None, proj_out=None, train=None, tokens=None):
+              x_out=None, want_h=True, h_dtype=torch.bfloat16, proj_w=None, proj_b=None, proj_out=None, train=None, tokens=None,
+              resid_acc=None):
     """Whole feed-forward module on the fp32 residual stream (cm_ffn_fused):
         xin = x + add_scale*addend;  r = xin + alpha*(W2 gelu(W1 LN_pre(xin) + b1) + b2);  r = LN1(r) if norm1;
         x_out <- r (x itself when x_out is None);  returns h = LN2(r) (or r when norm2 is None) in h_dtype if want_h.
@@ -1761,7 +1765,9 @@ def ffn_fused(x, pre_norm, w1, b1, w2, b2, alpha=0.5, addend=None, add_scale=1.0
     same kernel and (rows, P) bf16 = h @ proj_w^T (+ proj_b) is returned in h's place; h itself is not stored.
     ``train`` = (p1, p2, seed1, seed2): the module's TRAINING forward, x_out = x + alpha * drop_p2(W2 drop_p1(gelu(bf16(W1 LN(x) + b1))) + b2)
     with the backward's inputs stored on the way -> (x_out, (pre, xn, stats)): pre (rows, hidden) bf16 = W1 LN(x) + b1, xn (rows, 256)
-    bf16 = LN(x), stats (2, rows) fp32 = the rows' mean and 1/std (layernorm_bwd's input); the dropout decisions are cm_dropout.h's function of (seed, element index) (no mask is stored)."""
+    bf16 = LN(x), stats (2, rows) fp32 = the rows' mean and 1/std (layernorm_bwd's input); the dropout decisions are cm_dropout.h's function of (seed, element index) (no mask is stored).
+    ``resid_acc`` (default: CM_FFN_RESID_ACC): False = the residual rows are loaded again behind the last GEMM instead of riding in the
+    accumulators (any alpha that is no power of two takes that path by itself)."""
     _dev_check(x, b1, b2, addend, proj_b)
     rows, d = x.shape
     if x.dtype != torch.float32 or not x.is_contiguous():
@@ -1781,6 +1787,9 @@ def ffn_fused(x, pre_norm, w1, b1, w2, b2, alpha=0.5, addend=None, add_scale=1.0
         if t.dtype != torch.float32:
             raise RuntimeError("ffn_fused: biases and LayerNorm parameters must be fp32")
     a = N.FfnArgs()
+    racc = FFN_RESID_ACC if resid_acc is None else bool(resid_acc)
+    if not racc:
+        a.flags = N.CM_FFN_RELOAD_RESIDUAL
     a.rows, a.dim, a.hidden = rows, d, w1.shape[0]
     a.x, a.pre_g, a.pre_b, a.pre_eps = _ptr(x), _ptr(pre_norm[0]), _ptr(pre_norm[1]), float(pre_norm[2])
     a.w1, a.b1, a.w2, a.b2, a.alpha = _ptr(w1.data), _ptr(b1), _ptr(w2.data), _ptr(b2), float(alpha)

@@ -16,7 +16,14 @@ def sep():
     torch.mm(h, win.t(), out=out)
 def fus():
     ops.ffn_fused(x, n1, w1, b1, w2, b2, alpha=0.5, norm2=n1, proj_w=wp, proj_out=out)
-for name, fn in (("ffn1 + library in_proj", sep), ("ffn1 with projection", fus)) * 2:
+# the residual rows reloaded behind the last GEMM (CM_FFN_RESID_ACC=0) against carried in the accumulators.  In-encoder numbers decide
+# (this loop flattered an FFN change by 10 %).
+def reload():
+    ops.ffn_fused(x, n1, w1, b1, w2, b2, alpha=0.5, norm2=n1, proj_w=wp, proj_out=out, resid_acc=False)
+def racc():
+    ops.ffn_fused(x, n1, w1, b1, w2, b2, alpha=0.5, norm2=n1, proj_w=wp, proj_out=out, resid_acc=True)
+for name, fn in (("ffn1 + library in_proj", sep), ("ffn1 with projection", fus), ("ffn1 with projection, rows reloaded", reload),
+                 ("ffn1 with projection, residual in accumulators", racc)) * 2:
     for _ in range(3): fn()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
