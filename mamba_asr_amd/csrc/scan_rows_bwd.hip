@@ -12,7 +12,7 @@
 //       delta' u, dout silu(z)) go to the recurrence lanes through a per-wave LDS patch;
 //   recurrence   (lane = (state quad q, channel cl of row g): 4 states of one channel, packed fp32): sweep 1 recomputes h_t
 //       from the checkpoint keeping a_t and h_t of the 8 steps in registers; sweep 2 runs the adjoint lambda_t = C_t g_t +
-//       a_{t+1} lambda_{t+1} backwards.  a_t h_{t-1} is h_t - w_t B_t, so no second copy of the state is kept.
+//       a_{t+1} lambda_{t+1} backwards.  a_t h_{t-1} is the kept a_t times the kept h_{t-1} (the entry state for the first step).
 //       Sums over the 16 states of a channel (-> du, ddelta) are two quad DPP adds; sums over channels (dB, dC) are two
 //       row DPP adds over the 4 channels of a 16-lane row, then the 4 rows and the 4 waves through LDS, then one fp32 row of
 //       48 partial sums per (workgroup, step) to the workspace;
@@ -301,6 +301,7 @@ __device__ __forceinline__ void scan_rows_bwd(const cm_scan_cl_bwd_args &p, cons
             const float4 hc = ch[REV ? 1 - hf : hf];                 // scan-order half hf covers the time half hf (forward) / 1 - hf (reverse)
             f32x2 h01 = {hc.x, hc.y}, h23 = {hc.z, hc.w};
             if (!ok) h01 = h23 = f32x2{0.f, 0.f};
+            const f32x2 he01 = h01, he23 = h23;                      // the state entering the half block
             f32x2 a01s[HB], a23s[HB], h01s[HB], h23s[HB];
 #pragma unroll
             for (int si = 0; si < HB; ++si) {                        // sweep 1: states of the half block
@@ -332,8 +333,11 @@ __device__ __forceinline__ void scan_rows_bwd(const cm_scan_cl_bwd_args &p, cons
                 const f32x2 aB01 = l01 * w2, aB23 = l23 * w2;                                  // dB terms
                 f32x2 sb = l01 * B01;
                 sb = __builtin_elementwise_fma(l23, B23, sb);
-                const f32x2 hb01 = __builtin_elementwise_fma(-w2, B01, h01s[si]);              // a_t h_{t-1}
-                const f32x2 hb23 = __builtin_elementwise_fma(-w2, B23, h23s[si]);
+                // a_t h_{t-1} from the kept decay and the previous step's state (the half block's entry state in front of its first
+                // step).  As h_t - w_t B_t it was the rounding residue of w_t B_t wherever the decay underflows (a_t = 0, or h_{t-1} = 0
+                // at the first step of a sequence): a dA of ~1e-8 |w B lambda delta| where the gradient is exactly 0
+                const f32x2 hb01 = a01s[si] * (si ? h01s[si - 1] : he01);
+                const f32x2 hb23 = a23s[si] * (si ? h23s[si - 1] : he23);
                 const f32x2 r01 = l01 * hb01, r23 = l23 * hb23;
                 dA01 = __builtin_elementwise_fma(r01, d2, dA01);
                 dA23 = __builtin_elementwise_fma(r23, d2, dA23);
@@ -412,7 +416,12 @@ __device__ __forceinline__ void scan_rows_bwd(const cm_scan_cl_bwd_args &p, cons
         // ddt_weight[c][r] += sum_t ddelta_raw[c][t] dt[t][r]                        (A: lane (m = c, k = t) from the transposition patch)
         if constexpr (S == 2) {
             const bf16x4 a4 = __builtin_convertvector(f32x4{ddr[0], ddr[1], ddr[2], ddr[3]}, bf16x4);
-            const bf16x4 at4 = __builtin_convertvector(f32x4{tr[s16 * TRS + 4 * g], tr[s16 * TRS + 4 * g + 1], tr[s16 * TRS + 4 * g + 2], tr[s16 * TRS + 4 * g + 3]}, bf16x4);
+            // ddt_weight's ddelta operand as bf16 head + bf16 tail (two products into the same accumulator): rounded to bf16 alone, a row
+            // of ddt_weight that is a cancelling sum over the steps (dt_rank 1: the whole row) kept 2^-9 of its TERMS as error, 0.3 - 0.9
+            // of the row itself in tests/test_scan_rows_bwd_edges.py::test_scan_bwd_bf16_ranks[1]; dt, the other operand, is bf16 as given
+            const f32x4 atf = {tr[s16 * TRS + 4 * g], tr[s16 * TRS + 4 * g + 1], tr[s16 * TRS + 4 * g + 2], tr[s16 * TRS + 4 * g + 3]};
+            const bf16x4 at4 = __builtin_convertvector(atf, bf16x4);
+            const bf16x4 at4l = __builtin_convertvector(atf - __builtin_convertvector(at4, f32x4), bf16x4);
             const uint16_t *xraw = reinterpret_cast<const uint16_t *>(xt);
 #pragma unroll
             for (int t2 = 0; t2 < DTR / 16; ++t2) {
@@ -423,6 +432,7 @@ __device__ __forceinline__ void scan_rows_bwd(const cm_scan_cl_bwd_args &p, cons
                 const u16x4 dtc = {xraw[(4 * g + 0) * XSB * 2 + 16 * t2 + s16], xraw[(4 * g + 1) * XSB * 2 + 16 * t2 + s16],
                                    xraw[(4 * g + 2) * XSB * 2 + 16 * t2 + s16], xraw[(4 * g + 3) * XSB * 2 + 16 * t2 + s16]};
                 dWacc[t2] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(at4, __builtin_bit_cast(bf16x4, dtc), dWacc[t2], 0, 0, 0);
+                dWacc[t2] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(at4l, __builtin_bit_cast(bf16x4, dtc), dWacc[t2], 0, 0, 0);
             }
         } else {
             f32x4 dd = {0.f, 0.f, 0.f, 0.f};

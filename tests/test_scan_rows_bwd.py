@@ -75,7 +75,7 @@ def test_scan_rows_bwd_two_directions(shape, dtype, rank):
         close(o["dxdbl"][:, :, P + 16:].float(), r["dC"].transpose(1, 2), rt, at)
         close(o["dxdbl"][:, :, :rank].float(), r["ddt"], rt, at)
         assert float(o["dxdbl"][:, :, rank:P].float().abs().max()) == 0.0 if rank < P else True
-        # parameter gradients are fp32 sums in both modes; bf16 mode rounds ddelta to bf16 in front of the ddt_weight product
+        # parameter gradients are fp32 sums in both modes; bf16 mode feeds ddelta to the ddt_weight product as a bf16 head + tail
         close(o["dA"], r["dA"], 3e-3 if f32 else 2e-2, 3e-4 if f32 else 5e-3)
         close(o["dD"], r["dD"], 3e-3 if f32 else 2e-2, 3e-4 if f32 else 5e-3)
         close(o["ddelta_bias"], r["ddelta_bias"], 3e-3 if f32 else 2e-2, 3e-4 if f32 else 5e-3)
