@@ -928,6 +928,7 @@ int cm_ln_pw_glu_mix(const cm_ln_pw_glu_mix_args *args);
  *   in : feats (batch, T, F) fp32
  *   out: (batch, T1 + 2*pad_out, F1 + 2*pad_out, C) io_dtype, T1 = ceil(T/2), F1 = ceil(F/2); with pad_out = 1 the
  *        reflect border the NEXT 3x3 stride-2 block needs is written as well, so that block runs unpadded.
+ *   T >= 5 and F >= 5 (that border reflects over three output rows / bins): fewer -> CM_EUNSUPPORTED.
  * ------------------------------------------------------------------------------------- */
 typedef struct cm_cnn_block1_args {
     int32_t batch, T, F, C;

@@ -653,12 +653,14 @@ __global__ __launch_bounds__(256) void cnn_block1_kernel(const cm_cnn_block1_arg
 extern "C" int cm_cnn_block1(const cm_cnn_block1_args *args) {
     CM_REQUIRE(args != nullptr, CM_EINVAL, "cnn_block1: args is NULL");
     const cm_cnn_block1_args &a = *args;
-    CM_REQUIRE(a.batch > 0 && a.T > 1 && a.F > 1 && a.C > 0 && a.feats && a.weight && a.ln_g && a.ln_b && a.out, CM_EINVAL,
+    CM_REQUIRE(a.batch > 0 && a.T > 0 && a.F > 0 && a.C > 0 && a.feats && a.weight && a.ln_g && a.ln_b && a.out, CM_EINVAL,
                "cnn_block1: bad sizes or NULL tensor");
     CM_REQUIRE(a.F <= 128 && a.C <= 128 && a.C % 2 == 0, CM_EUNSUPPORTED, "cnn_block1: F %d / C %d unsupported (<= 128, C even)", a.F, a.C);
     CM_REQUIRE(a.pad_out == 0 || a.pad_out == 1, CM_EINVAL, "cnn_block1: pad_out must be 0 or 1");
     const int T1 = (a.T + 1) / 2, F1 = (a.F + 1) / 2;
-    CM_REQUIRE(F1 * a.C <= 16 * 256 && T1 >= 3 && F1 >= 3, CM_EUNSUPPORTED, "cnn_block1: F1*C = %d unsupported (<= 4096)", F1 * a.C);
+    CM_REQUIRE(F1 * a.C <= 16 * 256, CM_EUNSUPPORTED, "cnn_block1: F1*C = %d unsupported (<= 4096)", F1 * a.C);
+    CM_REQUIRE(T1 >= 3 && F1 >= 3, CM_EUNSUPPORTED,
+               "cnn_block1: T %d / F %d too short: the next block's reflect border needs at least 5 frames and 5 bins", a.T, a.F);
     const int rpw = 8;                                              // output rows per workgroup
     dim3 grid((T1 + 2 * a.pad_out + rpw - 1) / rpw, a.batch);
     hipStream_t st = reinterpret_cast<hipStream_t>(a.stream);

@@ -54,7 +54,8 @@ __device__ __forceinline__ int rev4_8bit(int k) {                     // reverse
     return ((k & 3) << 6) | ((k & 12) << 2) | ((k >> 2) & 12) | (k >> 6);
 }
 
-__global__ __launch_bounds__(256) void fbank_wav_kernel(const cm_fbank_args p) {
+// floor_db = 10 log10(amin) rounded once from double on the host: log10f is an ulp or two off, and silence must sit ON the floor
+__global__ __launch_bounds__(256) void fbank_wav_kernel(const cm_fbank_args p, const float floor_db) {
     extern __shared__ float sm[];
     const int b = blockIdx.y, t0 = blockIdx.x * FT;
     const int F = NH + 1, T = p.frames, M = p.n_mels;
@@ -184,7 +185,7 @@ __global__ __launch_bounds__(256) void fbank_wav_kernel(const cm_fbank_args p) {
             const float *wm = p.band_w + band[2 * M + m] - lo;
             for (int f = lo; f < hi; ++f) acc = fmaf(pw[f * PWS + j], wm[f], acc);
         }
-        const float db = 10.f * log10f(fmaxf(acc, p.amin));
+        const float db = fmaxf(10.f * log10f(fmaxf(acc, p.amin)), floor_db);
         dbt[j * M + m] = db;
         if (t0 + j < T) local_max = fmaxf(local_max, db);
     }
@@ -217,6 +218,7 @@ extern "C" int cm_fbank_wav(const cm_fbank_args *args) {
     CM_REQUIRE(a.batch <= 65535 && a.n_mels <= 128, CM_EUNSUPPORTED, "fbank_wav: batch / n_mels too large");
     const size_t smem = (size_t)(NH + 1) * PWS * 4 + (size_t)(3 * a.n_mels + 1) * 4 + (size_t)BWCAP * 4 + (size_t)4 * ZN * 8 + 4;
     dim3 grid((a.frames + FT - 1) / FT, a.batch);
-    hipLaunchKernelGGL(fbank_wav_kernel, grid, dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), a);
+    hipLaunchKernelGGL(fbank_wav_kernel, grid, dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), a,
+                       (float)(10.0 * log10((double)a.amin)));
     return cm_launch_status("cm_fbank_wav");
 }

@@ -12,7 +12,8 @@ constexpr int FT = 16;
 constexpr int PWS = FT + 1;   // LDS row stride of the power tile: odd, so different bins of one frame sit in different banks
                               // (stride 16 put all bins of a frame in 4 banks: the mel loop ran 16-way conflicted)
 
-__global__ __launch_bounds__(256) void fbank_mel_db_kernel(const cm_fbank_args p) {
+// floor_db = 10 log10(amin) rounded once from double on the host (log10f is an ulp or two off; silence sits ON the floor)
+__global__ __launch_bounds__(256) void fbank_mel_db_kernel(const cm_fbank_args p, const float floor_db) {
     extern __shared__ float pw[];                                 // [n_freq][FT] then [2][n_mels] band limits
     const int b = blockIdx.y, t0 = blockIdx.x * FT;
     const int F = p.n_freq, T = p.frames, M = p.n_mels;
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(256) void fbank_mel_db_kernel(const cm_fbank_args p
         } else {
             for (int f = lo; f < hi; ++f) acc = fmaf(pw[f * PWS + j], p.fbank[f * M + m], acc);
         }
-        const float db = 10.f * log10f(fmaxf(acc, p.amin));
+        const float db = fmaxf(10.f * log10f(fmaxf(acc, p.amin)), floor_db);
         p.db[((int64_t)b * T + t0 + j) * M + m] = db;
         local_max = fmaxf(local_max, db);
     }
@@ -133,7 +134,8 @@ extern "C" int cm_fbank_mel_db(const cm_fbank_args *args) {
     const size_t smem = (size_t)a.n_freq * PWS * 4 + (size_t)(3 * a.n_mels + 1) * 4 + (a.band_w ? (size_t)4096 * 4 : 0);
     CM_REQUIRE(a.batch <= 65535 && smem <= 64 * 1024, CM_EUNSUPPORTED, "fbank_mel_db: n_freq %d too large", a.n_freq);
     dim3 grid((a.frames + FT - 1) / FT, a.batch);
-    hipLaunchKernelGGL(fbank_mel_db_kernel, grid, dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), a);
+    hipLaunchKernelGGL(fbank_mel_db_kernel, grid, dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), a,
+                       (float)(10.0 * log10((double)a.amin)));
     return cm_launch_status("cm_fbank_mel_db");
 }
 

@@ -1919,8 +1919,8 @@ def fbank_from_wav(wav, window, n_fft, hop, fbank, amin=1e-10, top_db=80.0, mean
     _dev_check(wav, window, fbank, mean, std)
     if wav.dtype != torch.float32 or wav.dim() != 2 or wav.stride(1) != 1:
         wav = wav.float().contiguous()
-    if wav.stride(0) % 2:
-        wav = wav.contiguous() if wav.shape[1] % 2 == 0 else torch.nn.functional.pad(wav, (0, 1))[:, :wav.shape[1]]
+    if wav.stride(0) % 2 or wav.data_ptr() % 8:           # the kernel's 8-byte sample loads: even rows from an aligned start
+        wav = wav.clone(memory_format=torch.contiguous_format) if wav.shape[1] % 2 == 0 else torch.nn.functional.pad(wav, (0, 1))[:, :wav.shape[1]]
     b, ns = wav.shape
     fb = _f32c(fbank)
     nf, m = fb.shape

@@ -355,7 +355,8 @@ def test_cnn_front_kernel(batch, frames):
     """cm_cnn_front (both CNN blocks, intermediate kept in LDS) against (a) a torch fp32 restatement of
     ConvolutionFrontEnd (reflect 'same' padding, stride 2, LayerNorm over (freq, channel), LeakyReLU) with the block-1
     output rounded to bf16 where the kernel rounds it, and (b) the two-kernel path cm_cnn_block1 + cm_cnn_block2.
-    Ragged step counts (last tile partial, chunk boundaries), more chunks than workgroups (batch 70)."""
+    Ragged step counts (last tile partial, chunk boundaries), many one-chunk utterances (batch 70: 70 chunks on 70 workgroups; the
+    persistent loop's second trip, more chunks than the 256 workgroups, is tests/test_front_end_edges.py's)."""
     from mamba_asr_amd import ops
     F = torch.nn.functional
     g = torch.Generator(device="cpu").manual_seed(batch * 1000 + frames)
