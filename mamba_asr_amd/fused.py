@@ -10,12 +10,23 @@ sequence:
   * both BiMamba directions share one conv launch (cm_conv_cl_fwd) and one scan launch (cm_scan_cl_fwd); the
     0.5*(fwd+bwd) average is folded into out_proj by K-concatenation: [y_f | y_b] @ (0.5*[W_out | W_out])^T;
   * GLU -> depthwise conv k=31 -> LayerNorm -> GELU of the convolution module is one kernel.
-GEMMs go to the vendor library through torch (hipBLASLt/rocBLAS): plain library GEMMs, not the product.
+
+A layer's launches are written down once, in three pieces cut where the routes differ -- in front of the selective scan
+and behind it:
+  _head  FFN1 + norm1 + in_proj (cm_ffn_fused), both causal convs + x_proj (cm_conv_xproj)       rows of whole utterances
+  _scan  cm_scan_cl_fwd, both directions                                                          any batch of utterances
+  _tail  out_proj + LN + pointwise conv + GLU (cm_ln_pw_glu), cm_glu_dwconv_ln_gelu (+ Linear),
+         FFN2 + norm2 (+ the encoder's final norm) (cm_ffn_fused)                                 rows of whole utterances
+_encoder_forward_joined composes them for one part (head, scan, tail on the whole batch) or several (head per part on
+its own stream, one scan, tail per part).  Each piece falls back to the library GEMM / seam kernel where a switch is off or
+a kernel does not cover the layer; layer_forward (library feed-forward GEMMs) and layer_forward_native (cm_gemm_bf16) are
+different sequences around the same conv + scan block.  Those GEMMs go to the vendor library through torch
+(hipBLASLt/rocBLAS): plain library GEMMs, not the product.
 """
 from __future__ import annotations
 
 import os
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 import torch.nn.functional as F
@@ -103,6 +114,18 @@ class _LayerCache:
             self.lin_packed = ops.PackedWeight(self.lin_w)
         self.kernel_size = cm.kernel_size
 
+    @property
+    def ffn_native(self) -> bool:
+        """Both feed-forward modules run on cm_ffn_fused (bf16, d_model 256, one hidden width)."""
+        w1 = self.ffn1["w1"]
+        return ops.ffn_supported(w1.shape[1], w1.shape[0], self.dtype) and self.ffn2["w1"].shape[0] == w1.shape[0]
+
+    @property
+    def all_native(self) -> bool:
+        """The all-native bf16 route covers the layer: six launches and, with every switch on, no library GEMM."""
+        return (self.ffn_native and self.rows_mode and self.wx_packed is not None and self.pw_packed is not None
+                and self.in_bias is None and self.out_bias is None and self.gamma is None)
+
 
 def _params_key(dtype, *modules):
     # (version, storage) per parameter: see ops.cast_cached / weight_cache.invalidate_caches
@@ -154,10 +177,11 @@ USE_CONV_XPROJ = os.environ.get("CM_CONV_XPROJ", "1") == "1"
 
 def _scan_dirs(c: _LayerCache, ucat, ycat, batch, seqlen, xdbl=None):
     """x_proj for both directions (one library GEMM, time-contiguous output rows), fp32 feature buffer, and the two
-    direction descriptors of cm_scan_cl_fwd."""
+    direction descriptors of cm_scan_cl_fwd.  ``xdbl``: x_proj's rows when cm_conv_xproj has formed them already (only the
+    row-group kernel reads them)."""
     E, R, N = c.d_inner, c.dt_rank, c.d_state
     rows, P = batch * seqlen, c.dt_rank + 2 * c.d_state
-    if c.rows_mode and USE_SCAN_ROWS:
+    if c.rows_mode and (USE_SCAN_ROWS or xdbl is not None):
         if xdbl is None:
             xdbl = (ucat.view(rows, 2 * E) @ c.x_proj_rows.t()).view(batch, seqlen, 2 * c.row_width)  # one library GEMM, rows as the scan reads them
         RW = c.row_width
@@ -203,31 +227,38 @@ def mixer_tail(c: _LayerCache, x, ycat):
     return ops.ln_pw_glu(x, _out_proj(c, ycat), 1.0, c.cm_ln, c.pw_packed, c.pw_bf)
 
 
-def bimamba_fused(c: _LayerCache, h, batch, seqlen, xz=None, want_ycat=False):
-    """h: LN'd input (rows, D) in the compute dtype -> mixer output (rows, D) (reference bimamba.py:192-253).
-    ``xz``: in_proj's output when the caller already has it (cm_ffn_fused's projection epilogue).
-    ``want_ycat``: stop in front of out_proj and return the scan's (rows, 2E) output (for mixer_tail)."""
-    E, R, N = c.d_inner, c.dt_rank, c.d_state
-    rows = batch * seqlen
-    if xz is None:
-        xz = h @ c.in_proj.t()                                           # (rows, 2E): [x | z], channels-last
-        if c.in_bias is not None:
-            xz = xz + c.in_bias
-    xz3 = xz.view(batch, seqlen, 2 * E)
-    ucat = torch.empty((batch, seqlen, 2 * E), dtype=xz.dtype, device=xz.device)
-    xdbl = None
-    if USE_CONV_XPROJ and USE_SCAN_ROWS and c.rows_mode and c.wx_packed is not None and xz.dtype == torch.bfloat16:
-        xdbl = ops.conv_xproj(xz3[:, :, :E], c.dirs[0]["conv_w"], c.dirs[0]["conv_b"], c.dirs[1]["conv_w"], c.dirs[1]["conv_b"],
-                              c.wx_packed[0], c.wx_packed[1], out_f=ucat[:, :, :E], out_b=ucat[:, :, E:])
-    else:
-        ops.conv_cl_fwd(xz3[:, :, :E], c.dirs[0]["conv_w"], c.dirs[0]["conv_b"], c.dirs[1]["conv_w"], c.dirs[1]["conv_b"],
-                        True, out_f=ucat[:, :, :E], out_b=ucat[:, :, E:])
-    ycat = torch.empty_like(ucat)
-    dirs = _scan_dirs(c, ucat, ycat, batch, seqlen, xdbl)
-    ops.scan_cl_fwd(dirs, z=xz3[:, :, E:], delta_softplus=True)
-    if want_ycat:
-        return ycat.view(rows, 2 * E)
-    return _out_proj(c, ycat.view(rows, 2 * E))
+def _in_proj(c: _LayerCache, h, out=None):
+    """h (rows, D) -> xz (rows, 2E) = [x | z], channels-last: one library GEMM (into ``out`` when given)."""
+    xz = torch.mm(h, c.in_proj.t(), out=out)
+    return xz if c.in_bias is None else xz.add_(c.in_bias)
+
+
+def _conv_forms_xdbl(c: _LayerCache) -> bool:
+    return USE_CONV_XPROJ and USE_SCAN_ROWS and c.rows_mode and c.wx_packed is not None and c.dtype == torch.bfloat16
+
+
+def _conv(c: _LayerCache, xz, ucat, xdbl=None, xproj=True):
+    """Both directions' causal conv + SiLU of xz's x half (batch, seqlen, 2E views) into ucat = [u_fwd | u_bwd].  With
+    cm_conv_xproj the same kernel forms x_proj's rows (into ``xdbl`` when given) and they are returned, else None."""
+    E = c.d_inner
+    w = (c.dirs[0]["conv_w"], c.dirs[0]["conv_b"], c.dirs[1]["conv_w"], c.dirs[1]["conv_b"])
+    if xproj and _conv_forms_xdbl(c):
+        return ops.conv_xproj(xz[:, :, :E], *w, c.wx_packed[0], c.wx_packed[1], out_f=ucat[:, :, :E], out_b=ucat[:, :, E:], xdbl=xdbl)
+    ops.conv_cl_fwd(xz[:, :, :E], *w, True, out_f=ucat[:, :, :E], out_b=ucat[:, :, E:])
+    return None
+
+
+def _scan(c: _LayerCache, xz, ucat, ycat, xdbl, batch, seqlen):
+    """Both directions' selective scan of ucat, gated by xz's z half, into ycat (all (batch, seqlen, 2E)): one launch."""
+    ops.scan_cl_fwd(_scan_dirs(c, ucat, ycat, batch, seqlen, xdbl), z=xz[:, :, c.d_inner:], delta_softplus=True)
+
+
+def bimamba_fused(c: _LayerCache, h, batch, seqlen):
+    """h: LN'd input (rows, D) in the compute dtype -> mixer output (rows, D) (reference bimamba.py:192-253)."""
+    xz = _in_proj(c, h).view(batch, seqlen, -1)
+    ucat, ycat = torch.empty_like(xz), torch.empty_like(xz)
+    _scan(c, xz, ucat, ycat, _conv(c, xz, ucat), batch, seqlen)
+    return _out_proj(c, ycat.view(batch * seqlen, -1))
 
 
 # cm_ffn_fused: the whole feed-forward module (LayerNorm, both Linears, GELU, scaled residual, the next LayerNorm) in
@@ -240,52 +271,61 @@ USE_FUSED_FFN = os.environ.get("CM_FUSED_FFN", "1") == "1"
 USE_LN_PW_GLU = os.environ.get("CM_LN_PW_GLU", "1") == "1"
 
 
-def _layer_forward_ffn_fused(c, x, batch, seqlen, dtype, final_ln=None):
-    """layer_forward with both feed-forward modules on cm_ffn_fused (bf16, d_model 256)."""
+def _ffn_call(x, f, **kw):
+    """cm_ffn_fused on the residual rows x with the cached feed-forward module f (c.ffn1 / c.ffn2), at the layer's alpha = 0.5."""
+    return ops.ffn_fused(x, f["ln"], f["w1p"], f["b1f"], f["w2p"], f["b2f"], alpha=0.5, **kw)
+
+
+def _ffn_images(c: _LayerCache, small: bool):
+    """(ffn1, ffn2, in_packed) as cm_ffn_fused streams them.  ``small``: a launch of at most CM_FFN_SMALL_ROWS rows leaves CUs
+    idle at 64 tokens per workgroup, so it takes the 32 x 16 tile images (the 32-token form of the 32x32x16 kernel)."""
+    if not (small and "w1s" in c.ffn1):
+        return c.ffn1, c.ffn2, c.in_packed
+    return (dict(c.ffn1, w1p=c.ffn1["w1s"], w2p=c.ffn1["w2s"]), dict(c.ffn2, w1p=c.ffn2["w1s"], w2p=c.ffn2["w2s"]),
+            getattr(c, "in_packed_s", None))
+
+
+def _head(c: _LayerCache, x, xz, ucat, xdbl=None, small=False):
+    """A layer in front of the scan, on the rows of whole utterances: x (rows, D) fp32 += 0.5 ffn1(x); norm1; in_proj -> xz;
+    both causal convs -> ucat; x_proj -> xdbl.  xz / ucat (batch, seqlen, 2E) and xdbl (batch, seqlen, 2 RW) or None are
+    these rows' slices of the forward's buffers.  Returns x_proj's rows when cm_conv_xproj formed them, else None."""
+    f1, _, inp = _ffn_images(c, small)
+    if c.in_packed is not None:
+        _ffn_call(x, f1, norm2=c.norm1, proj_w=inp, proj_out=xz.view(x.shape[0], -1))
+    else:
+        _in_proj(c, _ffn_call(x, f1, norm2=c.norm1)[1], out=xz.view(x.shape[0], -1))
+    return _conv(c, xz, ucat, xdbl)
+
+
+def _ffn2(c: _LayerCache, x, addend, final_ln=None, f2=None):
+    """A layer's closing step: x = norm2(x + addend + 0.5 ffn2(x + addend)) in place, one kernel.  On the last layer the
+    encoder's final norm rides along and its fp32 output rows are returned."""
+    return _ffn_call(x, f2 or c.ffn2, addend=addend, norm1=c.norm2, norm2=final_ln, want_h=final_ln is not None,
+                     h_dtype=torch.float32)[1]
+
+
+def _tail(c: _LayerCache, x, ycat, batch, seqlen, final_ln=None, small=False):
+    """A layer behind the scan, on the rows of whole utterances: x (rows, D) fp32 += out_proj(ycat (rows, 2E)); the
+    convolution module; FFN2 + norm2 (-> _ffn2)."""
     D = x.shape[-1]
-    f1, f2 = c.ffn1, c.ffn2
-    if 0 < x.shape[0] <= ops.SMALL_FFN_ROWS and "w1s" in f1:
-        # a launch this small leaves CUs idle at 64 tokens per workgroup: the 32-token form of the 32x32x16 kernel
-        f1 = dict(f1, w1p=f1["w1s"], w2p=f1["w2s"])
-        f2 = dict(f2, w1p=f2["w1s"], w2p=f2["w2s"])
-        inp = getattr(c, "in_packed_s", None)
-    else:
-        inp = c.in_packed
-    seam = USE_LN_PW_GLU and c.pw_packed is not None and dtype == torch.bfloat16
-    if c.in_packed is not None:                                                                                # x += 0.5 ffn1 ; norm1 ; in_proj
-        _, xz = ops.ffn_fused(x, f1["ln"], f1["w1p"], f1["b1f"], f1["w2p"], f1["b2f"], alpha=0.5, norm2=c.norm1, proj_w=inp)
-        y = bimamba_fused(c, None, batch, seqlen, xz=xz, want_ycat=seam)
-    else:
-        _, h = ops.ffn_fused(x, f1["ln"], f1["w1p"], f1["b1f"], f1["w2p"], f1["b2f"], alpha=0.5, norm2=c.norm1)   # x += 0.5 ffn1 ; norm1
-        y = bimamba_fused(c, h, batch, seqlen, want_ycat=seam)
-    if seam:
+    dw = (c.dw_w, c.dw_b, c.cm_ln2[0], c.cm_ln2[1], c.cm_ln2[2])
+    if USE_LN_PW_GLU and c.pw_packed is not None:
         # x += mamba ; conv-module LN ; pointwise conv ; GLU -- one kernel, the 2D-wide tensor never exists
-        gl = mixer_tail(c, x, y)
-        g = ops.glu_dwconv_ln_gelu(gl.view(batch, seqlen, D), c.dw_w, c.dw_b, c.cm_ln2[0], c.cm_ln2[1], c.cm_ln2[2],
-                                   weight_t=c.dw_wt, glu_done=True, lin_w=c.lin_packed, lin_b=c.lin_bf)
+        gl = mixer_tail(c, x, ycat)
+        g = ops.glu_dwconv_ln_gelu(gl.view(batch, seqlen, D), *dw, weight_t=c.dw_wt, glu_done=True, lin_w=c.lin_packed, lin_b=c.lin_bf)
     else:
-        _, h = ops.add_layernorm(x, y, 1.0, x_out=x, norm2=c.cm_ln, out_dtype=dtype)          # x += mamba ; conv-module LN
+        _, h = ops.add_layernorm(x, _out_proj(c, ycat), 1.0, x_out=x, norm2=c.cm_ln, out_dtype=c.dtype)   # x += mamba ; conv-module LN
         pw = torch.addmm(c.pw_b, h, c.pw_w.t()).view(batch, seqlen, 2 * D)
-        g = ops.glu_dwconv_ln_gelu(pw, c.dw_w, c.dw_b, c.cm_ln2[0], c.cm_ln2[1], c.cm_ln2[2], weight_t=c.dw_wt,
-                                   lin_w=c.lin_packed, lin_b=c.lin_bf)
-    y = g if c.lin_packed is not None else torch.addmm(c.lin_b, g.view(-1, D), c.lin_w.t())
-    # x = norm2(x + conv + 0.5 ffn2(x + conv)); the encoder's final norm rides along on the last layer
-    if final_ln is not None:
-        _, out = ops.ffn_fused(x, f2["ln"], f2["w1p"], f2["b1f"], f2["w2p"], f2["b2f"], alpha=0.5, addend=y.view(-1, D),
-                               norm1=c.norm2, norm2=final_ln, h_dtype=torch.float32)
-        return out, None
-    ops.ffn_fused(x, f2["ln"], f2["w1p"], f2["b1f"], f2["w2p"], f2["b2f"], alpha=0.5, addend=y.view(-1, D), norm1=c.norm2,
-                  want_h=False)
-    return x, None
+        g = ops.glu_dwconv_ln_gelu(pw, *dw, weight_t=c.dw_wt, lin_w=c.lin_packed, lin_b=c.lin_bf)
+    y = g.view(-1, D) if c.lin_packed is not None else torch.addmm(c.lin_b, g.view(-1, D), c.lin_w.t())
+    return _ffn2(c, x, y, final_ln, _ffn_images(c, small)[1])
 
 
-def layer_forward(layer, x, batch, seqlen, dtype, next_ln=None, final_ln=None):
-    """One ConmambaEncoderLayer on the fp32 residual stream x (rows, D), in place.
-    Returns (x, h) where h = next_ln(x) in the compute dtype if next_ln is given."""
+def layer_forward(layer, x, batch, seqlen, dtype, final_ln=None):
+    """One ConmambaEncoderLayer with its feed-forward GEMMs in the library (fp32, or cm_ffn_fused off / not covering it), on
+    the fp32 residual stream x (rows, D), in place.  Returns x, or the encoder's final norm of it under ``final_ln``."""
     c = _cache(layer, dtype)
     D = x.shape[-1]
-    if USE_FUSED_FFN and ops.ffn_supported(D, c.ffn1["w1"].shape[0], dtype) and c.ffn2["w1"].shape[0] == c.ffn1["w1"].shape[0]:
-        return _layer_forward_ffn_fused(c, x, batch, seqlen, dtype, final_ln)
     _, h = ops.add_layernorm(x, None, norm2=c.ffn1["ln"], out_dtype=dtype)                   # LN of ffn_module1
     y = _ffn(x, h, c.ffn1, dtype)
     _, h = ops.add_layernorm(x, y, 0.5, x_out=x, norm2=c.norm1, out_dtype=dtype)              # x += 0.5 ffn1 ; norm1
@@ -296,15 +336,10 @@ def layer_forward(layer, x, batch, seqlen, dtype, next_ln=None, final_ln=None):
     y = torch.addmm(c.lin_b, g.view(-1, D), c.lin_w.t())
     _, h = ops.add_layernorm(x, y, 1.0, x_out=x, norm2=c.ffn2["ln"], out_dtype=dtype)         # x += conv ; LN of ffn_module2
     y = _ffn(x, h, c.ffn2, dtype)
-    # x = norm2(x + 0.5 ffn2); optionally chain the encoder's final norm, and the next layer's first LN
-    n1 = c.norm2
-    if final_ln is not None:
-        ops.add_layernorm(x, y, 0.5, x_out=x, norm1=n1, want_out=False)
-        _, out = ops.add_layernorm(x, None, norm2=final_ln, out_dtype=torch.float32)
-        return out, None
-    ops.add_layernorm(x, y, 0.5, x_out=x, norm1=n1, want_out=False)
-    return x, None
-
+    ops.add_layernorm(x, y, 0.5, x_out=x, norm1=c.norm2, want_out=False)                      # x = norm2(x + 0.5 ffn2)
+    if final_ln is None:
+        return x
+    return ops.add_layernorm(x, None, norm2=final_ln, out_dtype=torch.float32)[1]             # the encoder's final norm
 
 
 # cm_gemm_bf16 (hand-written MFMA GEMM with fused bias/GELU/residual+LayerNorm epilogues) is correct but, in round 1,
@@ -324,19 +359,15 @@ def layer_forward_native(layer, x, h, batch, seqlen, next_ln):
     are GEMM epilogues.  x: fp32 residual (rows, 256), updated in place; h = LN_ffn1(x) in bf16.
     Returns the bf16 LayerNorm of the layer output under ``next_ln`` (next layer's first LN) or None."""
     c = _cache(layer, torch.bfloat16)
-    D, E, R, N = x.shape[-1], c.d_inner, c.dt_rank, c.d_state
-    rows = batch * seqlen
+    D, E, rows = x.shape[-1], c.d_inner, batch * seqlen
     g = ops.gemm_bf16
     u1 = g(h, c.ffn1["w1"], c.ffn1["b1f"], epilogue=1)                                        # Linear + GELU
     h = g(u1, c.ffn1["w2"], c.ffn1["b2f"], epilogue=2, x=x, alpha=0.5, norm2=c.norm1)        # x += 0.5 ffn1 ; norm1
     xz = g(h, c.in_proj, c.in_bias_f, epilogue=0)                                            # (rows, 2E) = [x | z]
-    xz3 = xz.view(batch, seqlen, 2 * E)
-    ucat = torch.empty((batch, seqlen, 2 * E), dtype=xz.dtype, device=xz.device)
-    ops.conv_cl_fwd(xz3[:, :, :E], c.dirs[0]["conv_w"], c.dirs[0]["conv_b"], c.dirs[1]["conv_w"], c.dirs[1]["conv_b"],
-                    True, out_f=ucat[:, :, :E], out_b=ucat[:, :, E:])
-    ycat = torch.empty_like(ucat)
-    dirs = _scan_dirs(c, ucat, ycat, batch, seqlen)
-    ops.scan_cl_fwd(dirs, z=xz3[:, :, E:], delta_softplus=True)
+    xz = xz.view(batch, seqlen, 2 * E)
+    ucat, ycat = torch.empty_like(xz), torch.empty_like(xz)
+    _conv(c, xz, ucat, xproj=False)                                                          # conv kernel; x_proj in the library
+    _scan(c, xz, ucat, ycat, None, batch, seqlen)
     h = g(ycat.view(rows, 2 * E), c.out_cat, c.out_bias_f, epilogue=2, x=x, alpha=1.0, norm2=c.cm_ln)   # x += mixer
     pw = g(h, c.pw_w, c.pw_bf, epilogue=0).view(batch, seqlen, 2 * D)
     gl = ops.glu_dwconv_ln_gelu(pw, c.dw_w, c.dw_b, c.cm_ln2[0], c.cm_ln2[1], c.cm_ln2[2], weight_t=c.dw_wt)
@@ -362,97 +393,94 @@ STREAM_MODE = os.environ.get("CM_STREAM_MODE", "join")
 _side_streams = {}
 
 
+def _side_pool(dev, n):
+    """``n`` side streams of the device's pool, which grows on demand."""
+    pool = _side_streams.setdefault(dev.index, [])
+    while len(pool) < n:
+        pool.append(torch.cuda.Stream(device=dev))
+    return pool[:n]
+
+
+def _final_norm(encoder):
+    """The encoder's closing LayerNorm as the kernels take one: (weight, bias, eps), fp32."""
+    ln = encoder.norm.norm
+    return ln.weight.detach().float(), ln.bias.detach().float(), ln.eps
+
+
+def _residual_rows(src):
+    """src (batch, seqlen, D) -> the fp32 residual stream (rows, D), a private copy: the layers update it in place."""
+    x = src.detach().float().reshape(-1, src.shape[-1]).contiguous()
+    return x.clone() if x.data_ptr() == src.data_ptr() else x
+
+
 def _encoder_forward_joined(encoder, src, dtype, ns, paired=False):
-    """The fused encoder with the batch as ``ns`` parts on ``ns`` HIP streams for everything EXCEPT the selective scan,
-    which runs once per layer on the whole batch between a join and a fork: the kernels whose load / compute / store
-    phases run in lock step (FFN, seam, conv, GEMMs) overlap across parts, while the dominant kernel keeps the chip to
-    itself (its launch duration is then its own, and its grid is the full batch).  Returns None when a layer is not
-    covered by the all-native bf16 path.
+    """The encoder with both feed-forward modules on cm_ffn_fused, every layer as _head, _scan, _tail, the batch as ``ns``
+    parts.  One part: the three pieces on the whole batch.  Several: the parts run on ``ns`` HIP streams for everything
+    EXCEPT the selective scan, which runs once per layer on the whole batch between a join and a fork: the kernels whose
+    load / compute / store phases run in lock step (FFN, seam, conv, GEMMs) overlap across parts, while the dominant kernel
+    keeps the chip to itself (its launch duration is then its own, and its grid is the full batch).  Returns None when
+    cm_ffn_fused does not cover a layer or, with several parts, a layer is not covered by the all-native bf16 path.
 
     ``paired`` (CM_STREAM_MODE=pair): the scan runs PER PART, and a part's scan waits for the end of the scan launched before
     it -- at most one scan is on the chip at any time, always beside the other parts' feed-forward / row kernels (VERDICT r2
     item 4: the vector-issue-bound scan leaves 80 % of HBM and the matrix pipe idle)."""
     batch, seqlen, D = src.shape
-    if dtype != torch.bfloat16 or not USE_FUSED_FFN or not (USE_CONV_XPROJ and USE_SCAN_ROWS and USE_LN_PW_GLU):
-        return None
     caches = [_cache(layer, dtype) for layer in encoder.layers]
-    for c in caches:
-        if not (ops.ffn_supported(D, c.ffn1["w1"].shape[0], dtype) and c.ffn2["w1"].shape[0] == c.ffn1["w1"].shape[0] and c.rows_mode
-                and c.wx_packed is not None and c.pw_packed is not None and c.in_bias is None and c.out_bias is None and c.gamma is None):
-            return None
+    if not (USE_FUSED_FFN and caches and all(c.ffn_native for c in caches)):
+        return None
+    if ns > 1 and not (USE_CONV_XPROJ and USE_SCAN_ROWS and USE_LN_PW_GLU and all(c.all_native for c in caches)):
+        return None
     dev = src.device
     cur = torch.cuda.current_stream(dev)
-    pool = _side_streams.setdefault(dev.index, [])
-    while len(pool) < ns - 1:
-        pool.append(torch.cuda.Stream(device=dev))
-    streams = [cur] + pool[:ns - 1]
     edges = [int(round(i * batch / ns)) for i in range(ns + 1)]
     parts = [(edges[i], edges[i + 1]) for i in range(ns) if edges[i + 1] > edges[i]]
-    E = caches[0].d_inner
-    n = len(encoder.layers)
-    fin = (encoder.norm.norm.weight.detach().float(), encoder.norm.norm.bias.detach().float(), encoder.norm.norm.eps)
+    streams = [cur] + _side_pool(dev, len(parts) - 1)
+    # CM_FFN_SMALL_ROWS is about the unsplit launch: parts share the chip with each other's kernels
+    small = len(parts) == 1 and 0 < batch * seqlen <= ops.SMALL_FFN_ROWS
+    fin = _final_norm(encoder)
     with torch.autocast("cuda", enabled=False):
-        x = src.detach().float().reshape(batch * seqlen, D).contiguous()
-        if x.data_ptr() == src.data_ptr():
-            x = x.clone()
-        xz = torch.empty((batch, seqlen, 2 * E), dtype=dtype, device=dev)
+        x = _residual_rows(src)
+        xz = torch.empty((batch, seqlen, 2 * caches[0].d_inner), dtype=dtype, device=dev)
         ucat, ycat = torch.empty_like(xz), torch.empty_like(xz)
-        xdbl = torch.empty((batch, seqlen, 96), dtype=dtype, device=dev)
+        xdbl = torch.empty((batch, seqlen, 2 * caches[0].row_width), dtype=dtype, device=dev) if _conv_forms_xdbl(caches[0]) else None
+        x3 = x.view(batch, seqlen, D)
+        rows = lambda t, b0, b1: t[b0:b1].view((b1 - b0) * seqlen, -1)      # a part's utterances of a (batch, seqlen, .) buffer as rows
         outs = [None] * len(parts)
 
         def fork():
-            for st in streams[1:len(parts)]:
+            for st in streams[1:]:
                 st.wait_stream(cur)
 
         def join():
-            for st in streams[1:len(parts)]:
+            for st in streams[1:]:
                 cur.wait_stream(st)
 
         fork()
         gate = None                                                                 # pair mode: end of the scan launched last
         for li, c in enumerate(caches):
-            f1, f2 = c.ffn1, c.ffn2
-            for pi, (b0, b1) in enumerate(parts):
-                with torch.cuda.stream(streams[pi]):
-                    xp = x[b0 * seqlen:b1 * seqlen]
-                    if c.in_packed is not None:
-                        ops.ffn_fused(xp, f1["ln"], f1["w1p"], f1["b1f"], f1["w2p"], f1["b2f"], alpha=0.5, norm2=c.norm1,
-                                      proj_w=c.in_packed, proj_out=xz[b0:b1].view(-1, 2 * E))
-                    else:
-                        _, h = ops.ffn_fused(xp, f1["ln"], f1["w1p"], f1["b1f"], f1["w2p"], f1["b2f"], alpha=0.5, norm2=c.norm1)
-                        torch.mm(h, c.in_proj.t(), out=xz[b0:b1].view(-1, 2 * E))
-                    ops.conv_xproj(xz[b0:b1, :, :E], c.dirs[0]["conv_w"], c.dirs[0]["conv_b"], c.dirs[1]["conv_w"], c.dirs[1]["conv_b"],
-                                   c.wx_packed[0], c.wx_packed[1], out_f=ucat[b0:b1, :, :E], out_b=ucat[b0:b1, :, E:], xdbl=xdbl[b0:b1])
+            for st, (b0, b1) in zip(streams, parts):
+                with torch.cuda.stream(st):
+                    _head(c, rows(x3, b0, b1), xz[b0:b1], ucat[b0:b1], None if xdbl is None else xdbl[b0:b1], small)
             if paired:
-                for pi, (b0, b1) in enumerate(parts):
-                    with torch.cuda.stream(streams[pi]):
+                for st, (b0, b1) in zip(streams, parts):
+                    with torch.cuda.stream(st):
                         if gate is not None:
-                            streams[pi].wait_event(gate)
-                        ops.scan_cl_fwd(_scan_dirs(c, ucat[b0:b1], ycat[b0:b1], b1 - b0, seqlen, xdbl[b0:b1]), z=xz[b0:b1, :, E:],
-                                        delta_softplus=True)
+                            st.wait_event(gate)
+                        _scan(c, xz[b0:b1], ucat[b0:b1], ycat[b0:b1], xdbl[b0:b1], b1 - b0, seqlen)
                         gate = torch.cuda.Event()
-                        gate.record(streams[pi])
+                        gate.record(st)
             else:
                 join()
-                ops.scan_cl_fwd(_scan_dirs(c, ucat, ycat, batch, seqlen, xdbl), z=xz[:, :, E:], delta_softplus=True)
+                _scan(c, xz, ucat, ycat, xdbl, batch, seqlen)
                 fork()
-            for pi, (b0, b1) in enumerate(parts):
-                with torch.cuda.stream(streams[pi]):
-                    xp = x[b0 * seqlen:b1 * seqlen]
-                    gl = mixer_tail(c, xp, ycat[b0:b1].view(-1, 2 * E))
-                    g = ops.glu_dwconv_ln_gelu(gl.view(b1 - b0, seqlen, D), c.dw_w, c.dw_b, c.cm_ln2[0], c.cm_ln2[1], c.cm_ln2[2],
-                                               weight_t=c.dw_wt, glu_done=True, lin_w=c.lin_packed, lin_b=c.lin_bf)
-                    yl = g.view(-1, D) if c.lin_packed is not None else torch.addmm(c.lin_b, g.view(-1, D), c.lin_w.t())
-                    if li == n - 1:
-                        _, outs[pi] = ops.ffn_fused(xp, f2["ln"], f2["w1p"], f2["b1f"], f2["w2p"], f2["b2f"], alpha=0.5, addend=yl,
-                                                    norm1=c.norm2, norm2=fin, h_dtype=torch.float32)
-                    else:
-                        ops.ffn_fused(xp, f2["ln"], f2["w1p"], f2["b1f"], f2["w2p"], f2["b2f"], alpha=0.5, addend=yl, norm1=c.norm2,
-                                      want_h=False)
+            for pi, (st, (b0, b1)) in enumerate(zip(streams, parts)):
+                with torch.cuda.stream(st):
+                    outs[pi] = _tail(c, rows(x3, b0, b1), rows(ycat, b0, b1), b1 - b0, seqlen,
+                                     fin if li == len(caches) - 1 else None, small)
         join()
         for o in outs[1:]:
             o.record_stream(cur)
-        return torch.cat(outs, dim=0).view(batch, seqlen, D)
+        return (outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)).view(batch, seqlen, D)
 
 
 @torch.no_grad()
@@ -463,15 +491,14 @@ def encoder_forward(encoder, src, dtype: Optional[torch.dtype] = None, streams: 
     # parts of at least 16 utterances (measured, join mode: 16 utterances 12.1 M frames/s as one part vs 10.6 M as four;
     # 32: 15.1 / 15.3 / 15.2 M with 1 / 2 / 4; 64: 16.6 / 17.0 / 17.7 M); an explicit ``streams`` argument is taken as is
     ns = min(N_STREAMS, max(1, src.shape[0] // 16)) if streams is None else streams
-    if ns > 1 and src.shape[0] >= 2 * 8 and STREAM_MODE in ("join", "pair"):
-        out = _encoder_forward_joined(encoder, src, dtype, ns, paired=STREAM_MODE == "pair")
-        if out is not None:
-            return out
     if ns > 1 and src.shape[0] >= 2 * 8:                       # split only batches large enough to keep each half busy
-        dev = src.device
-        cur = torch.cuda.current_stream(dev)
-        pool = _side_streams.setdefault(dev.index, [torch.cuda.Stream(device=dev) for _ in range(ns - 1)])
+        if STREAM_MODE in ("join", "pair"):
+            out = _encoder_forward_joined(encoder, src, dtype, ns, paired=STREAM_MODE == "pair")
+            if out is not None:
+                return out
+        cur = torch.cuda.current_stream(src.device)            # "free", or a layer the joined route does not cover
         chunks = list(torch.chunk(src, ns, dim=0))
+        pool = _side_pool(src.device, len(chunks) - 1)
         outs = [None] * len(chunks)
         for i in range(1, len(chunks)):
             pool[i - 1].wait_stream(cur)
@@ -483,22 +510,23 @@ def encoder_forward(encoder, src, dtype: Optional[torch.dtype] = None, streams: 
             outs[i].record_stream(cur)
         return torch.cat(outs, dim=0)
     batch, seqlen, D = src.shape
+    caches = [_cache(layer, dtype) for layer in encoder.layers]
+    n = len(caches)
+    native = all(_native_gemms_ok(c, D, dtype) for c in caches)
+    out = None if native else _encoder_forward_joined(encoder, src, dtype, 1)
+    if out is not None:
+        return out
     with torch.autocast("cuda", enabled=False):
-        x = src.detach().float().reshape(batch * seqlen, D).contiguous()
-        if x.data_ptr() == src.data_ptr():
-            x = x.clone()                                     # the residual stream is updated in place
-        n = len(encoder.layers)
-        fin = (encoder.norm.norm.weight.detach().float(), encoder.norm.norm.bias.detach().float(), encoder.norm.norm.eps)
-        caches = [_cache(layer, dtype) for layer in encoder.layers]
-        if all(_native_gemms_ok(c, D, dtype) for c in caches):
+        out = x = _residual_rows(src)
+        fin = _final_norm(encoder)
+        if native:
             _, h = ops.add_layernorm(x, None, norm2=caches[0].ffn1["ln"], out_dtype=dtype)      # first LN of layer 0
             for i, layer in enumerate(encoder.layers):
                 h = layer_forward_native(layer, x, h, batch, seqlen, caches[i + 1].ffn1["ln"] if i + 1 < n else None)
             _, out = ops.add_layernorm(x, None, norm2=fin, out_dtype=torch.float32)             # encoder's final norm
-            return out.view(batch, seqlen, D)
-        out = x
-        for i, layer in enumerate(encoder.layers):
-            out, _ = layer_forward(layer, x, batch, seqlen, dtype, final_ln=fin if i == n - 1 else None)
+        else:
+            for i, layer in enumerate(encoder.layers):
+                out = layer_forward(layer, x, batch, seqlen, dtype, final_ln=fin if i == n - 1 else None)
         return out.view(batch, seqlen, D)
 
 
@@ -530,9 +558,10 @@ def _frontend_cache(model, dtype):
 @torch.no_grad()
 def asr_encode(model, wavs, wav_lens, dtype: Optional[torch.dtype] = None):
     """ConMambaASR.encode in eval mode through native kernels: Fbank (torch.stft/rocFFT + mel GEMM) -> global
-    normalisation -> cm_cnn_block1 (conv+LN+LeakyReLU, next block's reflect border included) -> library conv
-    (64->32, 3x3, stride 2, channels-last, unpadded) -> cm_add_layernorm(LN + LeakyReLU) -> src Linear ->
-    fused encoder.  Returns (batch, ceil(T/4), d_model) fp32."""
+    normalisation -> the two CNN blocks -> src Linear -> fused encoder.  The CNN blocks (conv + LayerNorm + LeakyReLU
+    each) run as cm_cnn_front, both in one kernel (bf16, the recipes' shapes); else cm_cnn_block1 (the next block's
+    reflect border included) + cm_cnn_block2 (bf16); else cm_cnn_block1 + library conv (64->32, 3x3, stride 2,
+    channels-last, unpadded) + cm_add_layernorm (LN + LeakyReLU).  Returns (batch, ceil(T/4), d_model) fp32."""
     if dtype is None:
         dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.float32
     with torch.autocast("cuda", enabled=False):
@@ -540,28 +569,23 @@ def asr_encode(model, wavs, wav_lens, dtype: Optional[torch.dtype] = None):
         feats = model.compute_features(wavs, norm=(model.normalize.glob_mean, model.normalize.glob_std))
         c = _frontend_cache(model, dtype)
         b0 = model.CNN.blocks[0]
+        n0 = b0.norm.norm
         if (USE_CNN_FRONT and dtype == torch.bfloat16 and ops.cnn_front_supported(feats, b0.conv.weight, c["w2_ohwi"])
-                and b0.norm.norm.weight.numel() == 40 * 64):
+                and n0.weight.numel() == 40 * 64):
             # both CNN blocks in one kernel: the (B, T/2 + 2, 42, 64) intermediate never reaches memory
-            src = ops.cnn_front(feats, b0.conv.weight, b0.conv.bias, b0.norm.norm.weight, b0.norm.norm.bias, b0.norm.norm.eps,
-                                c["w2_ohwi"], c["b2f"], c["ln2"][0], c["ln2"][1], c["ln2"][2], 0.01)
-            batch, t2 = src.shape[0], src.shape[1]
-            x = torch.addmm(c["lin_b"], src.view(batch * t2, -1), c["lin_w"].t())
-            return encoder_forward(model.Transformer.encoder, x.view(batch, t2, -1), dtype)
-        y1 = ops.cnn_block1(feats, b0.conv.weight, b0.conv.bias, b0.norm.norm.weight, b0.norm.norm.bias,
-                            b0.norm.norm.eps, 0.01, out_dtype=dtype, pad_out=1)     # (B, T1+2, F1+2, 64) NHWC
-        if dtype == torch.bfloat16 and tuple(c["w2_ohwi"].shape) == (32, 3, 3, 64):
-            src = ops.cnn_block2(y1, c["w2_ohwi"], c["b2f"], c["ln2"][0], c["ln2"][1], c["ln2"][2], 0.01)   # (B, T2, 640)
-            batch, t2 = src.shape[0], src.shape[1]
-            x = torch.addmm(c["lin_b"], src.view(batch * t2, -1), c["lin_w"].t())
-            return encoder_forward(model.Transformer.encoder, x.view(batch, t2, -1), dtype)
-        y2 = F.conv2d(y1.permute(0, 3, 1, 2), c["w2"], c["b2"], stride=2)           # channels_last in / out
-        y2 = y2.permute(0, 2, 3, 1)                                                 # (B, T2, F2, 32)
-        if not y2.is_contiguous():
-            y2 = y2.contiguous()
-        batch, t2 = y2.shape[0], y2.shape[1]
-        _, src = ops.add_layernorm(None, y2.reshape(batch * t2, -1), norm2=c["ln2"], out_dtype=dtype, out_act=1)
-        x = torch.addmm(c["lin_b"], src, c["lin_w"].t())                            # (rows, D)
+            src = ops.cnn_front(feats, b0.conv.weight, b0.conv.bias, n0.weight, n0.bias, n0.eps,
+                                c["w2_ohwi"], c["b2f"], c["ln2"][0], c["ln2"][1], c["ln2"][2], 0.01)            # (B, T2, 640)
+        else:
+            y1 = ops.cnn_block1(feats, b0.conv.weight, b0.conv.bias, n0.weight, n0.bias, n0.eps, 0.01, out_dtype=dtype,
+                                pad_out=1)                                              # (B, T1+2, F1+2, 64) NHWC
+            if dtype == torch.bfloat16 and tuple(c["w2_ohwi"].shape) == (32, 3, 3, 64):
+                src = ops.cnn_block2(y1, c["w2_ohwi"], c["b2f"], c["ln2"][0], c["ln2"][1], c["ln2"][2], 0.01)   # (B, T2, 640)
+            else:
+                y2 = F.conv2d(y1.permute(0, 3, 1, 2), c["w2"], c["b2"], stride=2)       # channels_last in / out
+                y2 = y2.permute(0, 2, 3, 1).contiguous()                                # (B, T2, F2, 32)
+                _, src = ops.add_layernorm(None, y2.flatten(2), norm2=c["ln2"], out_dtype=dtype, out_act=1)
+        batch, t2 = src.shape[:2]
+        x = torch.addmm(c["lin_b"], src.view(batch * t2, -1), c["lin_w"].t())           # (rows, D)
         return encoder_forward(model.Transformer.encoder, x.view(batch, t2, -1), dtype)
 
 

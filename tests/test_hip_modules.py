@@ -463,10 +463,11 @@ def test_fused_ffn_layer_path_matches_library_path(monkeypatch):
     assert (got - ref32).abs().mean() <= 1.2 * (ref - ref32).abs().mean()
 
 
-@pytest.mark.parametrize("mode", ["join", "free"])
+@pytest.mark.parametrize("mode", ["join", "pair", "free"])
 def test_multi_stream_encoder_matches_single_stream(monkeypatch, mode):
     """CM_STREAMS=3: the batch as three parts on three HIP streams ('join': scan once per layer on the whole batch
-    between a join and a fork; 'free': independent parts) gives exactly the single-stream result (utterances are
+    between a join and a fork; 'pair': a scan per part, one at a time; 'free': independent parts) gives exactly the
+    single-stream result (utterances are
     independent through the encoder; every kernel is deterministic), eagerly and under hipGraph capture."""
     from mamba_asr_amd import fused
     from mamba_asr_amd.modules.Conmamba import ConmambaEncoder
