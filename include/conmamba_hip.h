@@ -884,6 +884,9 @@ int cm_layernorm_bwd(const cm_layernorm_args *args);
  * x (rows, 256) fp32; y (rows, 256) bf16 or NULL; w: the pointwise Conv1d weight (512, 256) bf16 packed with
  * cm_ffn_pack_weights; bias (512) fp32; x_out (rows, 256) fp32 (may alias x) or NULL; out (rows, 256) bf16, which
  * cm_glu_dwconv_ln_gelu takes with glu_done = 1.
+ * dim = 144 (the ConMamba-small recipes) is taken too, with 144 / 288 for 256 / 512: w is then the image of the (288, 144)
+ * weight padded with zero columns to (288, 160) -- whole 32-column tiles; the kernel zeroes the matching columns of its token
+ * tile itself, and the LayerNorm statistics are over the 144 features.  Any other dim: CM_EUNSUPPORTED.
  * ------------------------------------------------------------------------------------- */
 typedef struct cm_ln_pw_glu_args {
     int32_t rows, dim;
@@ -903,7 +906,7 @@ int cm_ln_pw_glu(const cm_ln_pw_glu_args *args);
 /* The same seam with the mixer's out_proj in front: y = ycat @ proj_w^T is formed inside the kernel (rounded to bf16 as a
  * GEMM's output would be) and never reaches memory.  ycat (rows, proj_k) bf16 contiguous; proj_w (256, proj_k) bf16 packed
  * with cm_ffn_pack_weights; proj_k a multiple of 128, at most 8192.  The other fields are cm_ln_pw_glu_args'.  out and
- * x_out may overlap no input, except x_out == x. */
+ * x_out may overlap no input, except x_out == x.  dim 256 only (CM_EUNSUPPORTED otherwise). */
 typedef struct cm_ln_pw_glu_mix_args {
     int32_t rows, dim;
     const float *x;
@@ -1028,6 +1031,14 @@ int cm_gemm_bf16(const cm_gemm_args *args);
  * w1 / w2 are passed in the PACKED layout produced by cm_ffn_pack_weights (once per weight update): the (R, K) matrix
  * cut into 16-row x 32-column tiles, each stored as the 1 KB register image of an MFMA operand fragment -- element
  * (r, k) of tile (r/16, k/32) sits at 16-bit index  tile*512 + ((k%32)/8*16 + r%16)*8 + k%8,  tile = (r/16)*(K/32) + k/32.
+ * cm_ffn_pack_weights needs rows % 16 == 0 and cols % 32 == 0; a matrix that is no whole number of tiles is padded with zeros
+ * by the caller first.
+ * dim = 144 (the ConMamba-small recipes; inference forward, layout 0 only -- layout 1, tokens = 32 or any training field:
+ * CM_EUNSUPPORTED) reads 144 for 256 above, with every image padded to whole tiles: w1 = image of (hidden, 144) padded with
+ * zero columns to (hidden, 160), w2 = image of (144, hidden) padded with zero rows to (160, hidden), proj_w = image of
+ * (proj_dim, 144) padded to (proj_dim, 160).  proj_dim is then a multiple of 64 (576 = 2 d_inner of the recipe) instead of 256.
+ * The kernel writes the pad columns of its token tiles as zeros itself; the padded output features are never stored and never
+ * enter a LayerNorm sum.  hidden stays a multiple of 256, at most 2048.  Any other dim: CM_EUNSUPPORTED.
  * ------------------------------------------------------------------------------------- */
 int cm_ffn_pack_weights(const void *w /* (rows, cols) bf16 row-major */, int32_t rows, int32_t cols,
                         void *out /* rows*cols bf16 */, void *stream);
@@ -1035,24 +1046,24 @@ int cm_ffn_pack_weights(const void *w /* (rows, cols) bf16 row-major */, int32_t
 typedef struct cm_ffn_args {
     int32_t rows, dim, hidden;
     int32_t h_dtype;                    /* CM_BF16 or CM_F32                                 */
-    const float *x;                     /* (rows, 256) fp32                                  */
-    const void  *addend;                /* (rows, 256) bf16 or NULL                          */
-    const float *pre_g, *pre_b;         /* (256) LayerNorm in front of the first Linear      */
-    const void  *w1;                    /* (hidden, 256) bf16, packed                        */
+    const float *x;                     /* (rows, dim) fp32; dim = 256 or 144                */
+    const void  *addend;                /* (rows, dim) bf16 or NULL                          */
+    const float *pre_g, *pre_b;         /* (dim) LayerNorm in front of the first Linear      */
+    const void  *w1;                    /* (hidden, dim) bf16, packed (144: 160 columns)     */
     const float *b1;                    /* (hidden) fp32                                     */
-    const void  *w2;                    /* (256, hidden) bf16, packed                        */
-    const float *b2;                    /* (256) fp32                                        */
+    const void  *w2;                    /* (dim, hidden) bf16, packed (144: 160 rows)        */
+    const float *b2;                    /* (dim) fp32                                        */
     const float *n1_g, *n1_b;           /* optional LayerNorm applied to the stream          */
     const float *n2_g, *n2_b;           /* optional LayerNorm producing h_out                */
-    float       *x_out;                 /* (rows, 256) fp32 or NULL                          */
-    void        *h_out;                 /* (rows, 256) h_dtype or NULL                       */
+    float       *x_out;                 /* (rows, dim) fp32 or NULL                          */
+    void        *h_out;                 /* (rows, dim) h_dtype or NULL                       */
     float add_scale, alpha, pre_eps, n1_eps, n2_eps;
-    int32_t proj_dim;                   /* rows of proj_w (a multiple of 256, <= 4096); 0 without a projection            */
+    int32_t proj_dim;                   /* rows of proj_w (a multiple of 256 -- of 64 at dim 144 --, <= 4096); 0 without a projection */
     void *stream;
     /* optional: the Linear that consumes h, applied to the tile in the same kernel -- the BiMamba in_proj behind the
        layer's first feed-forward module (reference bimamba.py:192-200):  proj_out = LN2(r) @ proj_w^T (+ proj_b), bf16;
        h_out must be NULL then (h is not stored) */
-    const void  *proj_w;                /* (proj_dim, 256) bf16, cm_ffn_pack_weights' image                                */
+    const void  *proj_w;                /* (proj_dim, dim) bf16, cm_ffn_pack_weights' image (144: 160 columns)             */
     const float *proj_b;                /* (proj_dim) fp32 or NULL                                                          */
     void        *proj_out;              /* (rows, proj_dim) bf16                                                            */
     /* optional, the TRAINING forward of the module (reference modules/Conmamba.py:597-617 with its two Dropouts live):

@@ -17,6 +17,7 @@
 //   * barriers wait on LDS traffic only (s_waitcnt lgkmcnt(0); s_barrier), so the weight ring is not drained.
 #include "cm_common.h"
 #include "cm_dropout.h"
+#include "ffn_tile.h"
 #include <type_traits>
 
 
@@ -35,32 +36,6 @@ constexpr int NT = 256 * TH;  // threads per workgroup
 constexpr int XS = 264;       // LDS row stride in bf16 elements (528 bytes)
 constexpr int CH = 256;       // hidden slab
 constexpr int PF = 4;         // weight-fragment ring depth (k-steps in flight)
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-__device__ __forceinline__ uint32_t pack2(float a, float b) {         // one v_cvt_pk_bf16_f32
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
-}
-
-// Sum over a row of 16 lanes with every DPP step fenced on BOTH sides: 5 wait states in front of it and behind it, inside one asm block,
-// so that no packed-FP32 instruction can be scheduled next to it.  cm_group_sum settles each DPP's source only; in the RACC phase 0 the
-// compiler then paired the last steps of two sums -- v_mov_b32_dpp into a register pair that a v_pk_fma_f32 had written two slots
-// earlier, v_pk_add_f32 right behind -- and lanes 48-63 of the last token round kept the packed result: rows 15 mod 16 of a tile
-// changed from run to run at 32000 rows (tests/test_bench_shapes.py), the packed-FP32 / DPP hazard of cm_common.h from the other side.
-#define FFN_DPP_ADD(CTRL)                                                                                                             \
-    asm volatile("s_nop 4\n\tv_add_f32_dpp %0, %1, %1 " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\ts_nop 4" : "=v"(r) : "v"(v)); \
-    v = r
-__device__ __forceinline__ float group_sum16_fenced(float v) {
-    float r;
-    FFN_DPP_ADD("quad_perm:[1,0,3,2]");
-    FFN_DPP_ADD("quad_perm:[2,3,0,1]");
-    FFN_DPP_ADD("row_half_mirror");
-    FFN_DPP_ADD("row_mirror");
-    return v;
-}
-#undef FFN_DPP_ADD
 
 // VAR (cm_debug_set, timing only): 1 = scalar GELU (cm_gelu_bf16 per element; 108-110 us vs 99-100 us packed at 64k rows), 2 = no GELU, 3 = no weight stream after the first fill,
 // 4 = no token-fragment reads after the first, 5 = 2 + 3 + 4.  (Starting the workgroups of the second occupancy slot
@@ -700,6 +675,7 @@ bool is_pow2(float a) {
 }  // namespace
 
 int cm_ffn_fused32_launch(const cm_ffn_args &a);                  // ffn_fused32.hip
+int cm_ffn_fused144_launch(const cm_ffn_args &a, bool racc);      // fused_d144.hip
 
 extern "C" int cm_ffn_pack_weights(const void *w, int32_t rows, int32_t cols, void *out, void *stream) {
     CM_REQUIRE(w && out && rows > 0 && cols > 0, CM_EINVAL, "ffn_pack_weights: bad sizes or NULL tensor");
@@ -716,14 +692,15 @@ extern "C" int cm_ffn_fused(const cm_ffn_args *args) {
     const cm_ffn_args &a = *args;
     CM_REQUIRE(a.rows > 0 && a.x && a.w1 && a.b1 && a.w2 && a.b2 && a.pre_g && a.pre_b, CM_EINVAL,
                "ffn_fused: bad sizes or NULL tensor");
-    CM_REQUIRE(a.dim == D, CM_EUNSUPPORTED, "ffn_fused: d_model must be 256 (got %d)", a.dim);
+    CM_REQUIRE(a.dim == D || a.dim == 144, CM_EUNSUPPORTED, "ffn_fused: d_model must be 256 or 144 (got %d)", a.dim);
+    const int pm = a.dim == D ? 256 : 64;                             // the projection's width: whole 256-wide slabs, or 16-row bands per wave at 144
     CM_REQUIRE(a.hidden >= CH && a.hidden % CH == 0 && a.hidden <= 2048, CM_EUNSUPPORTED,
                "ffn_fused: hidden must be a multiple of 256, at most 2048 (got %d)", a.hidden);
     CM_REQUIRE((!a.n1_g || a.n1_b) && (!a.n2_g || a.n2_b), CM_EINVAL, "ffn_fused: LayerNorm weight without bias");
     CM_REQUIRE(a.x_out || a.h_out || a.proj_w, CM_EINVAL, "ffn_fused: neither x_out nor h_out nor a projection given");
-    CM_REQUIRE(!a.proj_w || (a.proj_out && !a.h_out && a.proj_dim >= 256 && a.proj_dim % 256 == 0 && a.proj_dim <= 4096 &&
+    CM_REQUIRE(!a.proj_w || (a.proj_out && !a.h_out && a.proj_dim >= pm && a.proj_dim % pm == 0 && a.proj_dim <= 4096 &&
                               cm_aligned(a.proj_w, 16) && cm_aligned(a.proj_out, 16) && (!a.proj_b || cm_aligned(a.proj_b, 16))),
-               CM_EINVAL, "ffn_fused: the projection needs proj_out, no h_out, proj_dim a multiple of 256 (<= 4096), aligned tensors");
+               CM_EINVAL, "ffn_fused: the projection needs proj_out, no h_out, proj_dim a multiple of 256 (of 64 at d_model 144; <= 4096), aligned tensors");
     CM_REQUIRE(!a.h_out || a.h_dtype == CM_F32 || a.h_dtype == CM_BF16, CM_EINVAL, "ffn_fused: h_dtype must be f32 or bf16");
     CM_REQUIRE(cm_aligned(a.x, 16) && cm_aligned(a.w1, 16) && cm_aligned(a.w2, 16) && cm_aligned(a.b1, 16) && cm_aligned(a.b2, 16) &&
                    cm_aligned(a.pre_g, 16) && cm_aligned(a.pre_b, 16) && (!a.x_out || cm_aligned(a.x_out, 16)) &&
@@ -736,6 +713,8 @@ extern "C" int cm_ffn_fused(const cm_ffn_args *args) {
     CM_REQUIRE(a.layout == 0 || !train, CM_EUNSUPPORTED, "ffn_fused: the training forward takes layout 0 weights");
     CM_REQUIRE(a.tokens == 0 || a.tokens == 64 || (a.tokens == 32 && a.layout == 1), CM_EINVAL, "ffn_fused: tokens must be 0 / 64, or 32 with layout 1");
     const bool racc = !train && a.layout == 0 && !(a.flags & CM_FFN_RELOAD_RESIDUAL) && is_pow2(a.alpha);
+    CM_REQUIRE(a.dim == D || (a.layout == 0 && !train), CM_EUNSUPPORTED, "ffn_fused: d_model 144 runs the inference forward on layout 0 weights only");
+    if (a.dim != D) return cm_ffn_fused144_launch(a, racc);
     if (a.layout == 1) return cm_ffn_fused32_launch(a);
     if (train) {
         CM_REQUIRE(a.x_out && !a.addend && !a.n1_g && !a.n2_g && !a.proj_w && !a.h_out, CM_EINVAL,

@@ -293,14 +293,17 @@ __global__ __launch_bounds__(256, OCC) void ln_pw_glu_kernel(const cm_ln_pw_glu_
 
 }  // namespace
 
+int cm_ln_pw_glu144_launch(const cm_ln_pw_glu_args &a);           // fused_d144.hip
+
 extern "C" int cm_ln_pw_glu(const cm_ln_pw_glu_args *args) {
     CM_REQUIRE(args != nullptr, CM_EINVAL, "ln_pw_glu: args is NULL");
     const cm_ln_pw_glu_args &a = *args;
     CM_REQUIRE(a.rows > 0 && a.x && a.ln_g && a.ln_b && a.w && a.bias && a.out, CM_EINVAL, "ln_pw_glu: bad sizes or NULL tensor");
-    CM_REQUIRE(a.dim == D, CM_EUNSUPPORTED, "ln_pw_glu: d_model must be 256 (got %d)", a.dim);
+    CM_REQUIRE(a.dim == D || a.dim == 144, CM_EUNSUPPORTED, "ln_pw_glu: d_model must be 256 or 144 (got %d)", a.dim);
     CM_REQUIRE(cm_aligned(a.x, 16) && cm_aligned(a.ln_g, 16) && cm_aligned(a.ln_b, 16) && cm_aligned(a.w, 16) && cm_aligned(a.bias, 16) &&
                    cm_aligned(a.out, 16) && (!a.y || cm_aligned(a.y, 8)) && (!a.x_out || cm_aligned(a.x_out, 16)),
                CM_EALIGN, "ln_pw_glu: tensors must be 16-byte aligned (y / out 8)");
+    if (a.dim != D) return cm_ln_pw_glu144_launch(a);
     const dim3 grid((a.rows + TOK - 1) / TOK);
     hipStream_t st = reinterpret_cast<hipStream_t>(a.stream);
     // four workgroups per CU (128 VGPRs with a 2-deep weight ring): 64 k rows = 1000 workgroups run in ONE round of 1024 slots;

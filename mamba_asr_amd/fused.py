@@ -45,22 +45,29 @@ class _LayerCache:
                              w2=c(m[1].ffn[3].weight), b2=c(m[1].ffn[3].bias), b1f=f(m[1].ffn[0].bias),
                              b2f=f(m[1].ffn[3].bias))
         self.ffn1, self.ffn2 = ffn(layer.ffn_module1), ffn(layer.ffn_module2)
-        if ops.ffn_supported(self.ffn1["w1"].shape[1], self.ffn1["w1"].shape[0], dtype) and self.ffn1["w1"].is_cuda:
+        D = self.ffn1["w1"].shape[1]
+        # d_model 144 (csrc/fused_d144.hip): images padded to 160 columns / rows, 16x16x32 kernels only; CM_FUSED_D144=0 builds none
+        wide = D == 256
+        kp = ops._kpad(D)
+        d144 = D == 144 and USE_FUSED_D144 and ops.FFN_LAYOUT == 16
+        if ops.ffn_supported(D, self.ffn1["w1"].shape[0], dtype) and self.ffn1["w1"].is_cuda and (wide or d144):
             for q in (self.ffn1, self.ffn2):                       # cm_ffn_fused's fragment-tiled weight images
-                q["w1p"], q["w2p"] = ops.PackedWeight(q["w1"], ops.FFN_LAYOUT), ops.PackedWeight(q["w2"], ops.FFN_LAYOUT)
+                q["w1p"] = ops.PackedWeight(q["w1"], ops.FFN_LAYOUT, pad=(q["w1"].shape[0], kp))
+                q["w2p"] = ops.PackedWeight(q["w2"], ops.FFN_LAYOUT, pad=(kp, q["w2"].shape[1]))
                 # the 32 x 16 tile image for small launches (32-token workgroups exist on the 32x32x16 kernel only)
-                if ops.SMALL_FFN_ROWS > 0:
+                if ops.SMALL_FFN_ROWS > 0 and wide:
                     q["w1s"], q["w2s"] = (q["w1p"], q["w2p"]) if ops.FFN_LAYOUT == 32 else (ops.PackedWeight(q["w1"], 32), ops.PackedWeight(q["w2"], 32))
         self.norm1 = (f(layer.norm1.norm.weight), f(layer.norm1.norm.bias), layer.norm1.norm.eps)
         self.norm2 = (f(layer.norm2.norm.weight), f(layer.norm2.norm.bias), layer.norm2.norm.eps)
         m = layer.mamba
         self.d_inner, self.dt_rank, self.d_state = m.d_inner, m.dt_rank, m.d_state
         self.in_proj = c(m.in_proj.weight)
-        self.in_packed = None                                     # in_proj inside cm_ffn_fused (bf16, d_model 256, no bias)
-        if (USE_FFN_INPROJ and dtype == torch.bfloat16 and self.in_proj.is_cuda and self.in_proj.shape[1] == 256
-                and self.in_proj.shape[0] % 256 == 0 and self.in_proj.shape[0] <= 4096 and m.in_proj.bias is None):
-            self.in_packed = ops.PackedWeight(self.in_proj, ops.FFN_LAYOUT)   # streamed by cm_ffn_fused's projection epilogue only
-            if ops.SMALL_FFN_ROWS > 0:
+        self.in_packed = None                                     # in_proj inside cm_ffn_fused (bf16, d_model 256 / 144, no bias)
+        if (USE_FFN_INPROJ and dtype == torch.bfloat16 and self.in_proj.is_cuda and self.in_proj.shape[1] == D and (wide or d144)
+                and self.in_proj.shape[0] % (256 if wide else 64) == 0 and self.in_proj.shape[0] <= 4096 and m.in_proj.bias is None):
+            # streamed by cm_ffn_fused's projection epilogue only
+            self.in_packed = ops.PackedWeight(self.in_proj, ops.FFN_LAYOUT, pad=(self.in_proj.shape[0], kp))
+            if ops.SMALL_FFN_ROWS > 0 and wide:
                 self.in_packed_s = self.in_packed if ops.FFN_LAYOUT == 32 else ops.PackedWeight(self.in_proj, 32)
         self.in_bias = None if m.in_proj.bias is None else c(m.in_proj.bias)
         half = 0.5 if m.if_devide_out else 1.0
@@ -97,8 +104,8 @@ class _LayerCache:
         self.pw_w, self.pw_b = c(cm.bottleneck[0].weight.squeeze(-1)), c(cm.bottleneck[0].bias)
         self.pw_bf, self.lin_bf = f(cm.bottleneck[0].bias), f(cm.after_conv[2].bias)
         self.pw_packed = None                                     # cm_ln_pw_glu's fragment-tiled pointwise-conv weight
-        if dtype == torch.bfloat16 and self.pw_w.is_cuda and tuple(self.pw_w.shape) == (512, 256) and self.pw_bf is not None:
-            self.pw_packed = ops.PackedWeight(self.pw_w)
+        if dtype == torch.bfloat16 and self.pw_w.is_cuda and tuple(self.pw_w.shape) == (2 * D, D) and (wide or d144) and self.pw_bf is not None:
+            self.pw_packed = ops.PackedWeight(self.pw_w, pad=(2 * D, kp))
         self.out_packed = None                                    # out_proj inside cm_ln_pw_glu (mixer_tail): no bias, no layer scale
         if (self.pw_packed is not None and self.out_cat.is_cuda and self.out_cat.shape[0] == 256 and self.out_cat.shape[1] % 128 == 0
                 and self.out_cat.shape[1] <= 8192 and self.out_bias is None and self.gamma is None):
@@ -116,9 +123,8 @@ class _LayerCache:
 
     @property
     def ffn_native(self) -> bool:
-        """Both feed-forward modules run on cm_ffn_fused (bf16, d_model 256, one hidden width)."""
-        w1 = self.ffn1["w1"]
-        return ops.ffn_supported(w1.shape[1], w1.shape[0], self.dtype) and self.ffn2["w1"].shape[0] == w1.shape[0]
+        """Both feed-forward modules run on cm_ffn_fused (bf16, d_model 256, or 144 with CM_FUSED_D144 on; one hidden width)."""
+        return "w1p" in self.ffn1 and self.ffn2["w1"].shape[0] == self.ffn1["w1"].shape[0]     # the images exist: __init__ decided
 
     @property
     def all_native(self) -> bool:
@@ -157,6 +163,11 @@ def _ffn(x, y_in, p, dtype):
     else:
         h = F.gelu(torch.addmm(p["b1"], y_in, p["w1"].t()))
     return torch.addmm(p["b2"], h, p["w2"].t())
+
+
+# cm_ffn_fused and cm_ln_pw_glu at d_model 144 (the ConMamba-small recipes; csrc/fused_d144.hip); CM_FUSED_D144=0 = no 144-wide images
+# are built and those layers take layer_forward (library feed-forward GEMMs + cm_add_layernorm seams)
+USE_FUSED_D144 = os.environ.get("CM_FUSED_D144", "1") == "1"
 
 
 # BiMamba in_proj inside the first cm_ffn_fused of a layer; CM_FFN_INPROJ=0 = library GEMM after the kernel

@@ -32,7 +32,8 @@ FUSED_BWD = os.environ.get("CM_FFN_FUSED_BWD", "1") == "1"
 
 
 def _fused_ok(cdt, D, F_, rows):
-    return FUSED_TRAIN and cdt == torch.bfloat16 and ops.ffn_supported(D, F_, cdt) and F_ <= 2048 and rows * F_ * 2 < 2 ** 32
+    # (the training forward and cm_ffn_bwd_fused are d_model 256 only)
+    return FUSED_TRAIN and cdt == torch.bfloat16 and D == 256 and ops.ffn_supported(D, F_, cdt) and F_ <= 2048 and rows * F_ * 2 < 2 ** 32
 
 
 def supported(x, ln, lin1, act, lin2) -> bool:

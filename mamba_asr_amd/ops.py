@@ -1538,18 +1538,21 @@ class LnActDropFn(torch.autograd.Function):
 
 def ln_pw_glu(x, y, alpha, norm, w, bias, x_out=None, ycat=None, out_w=None):
     """Mixer -> convolution-module seam (cm_ln_pw_glu): x_out = x + alpha*y; g = GLU(LayerNorm(x_out) @ W^T + bias).
-    x (rows, 256) fp32 contiguous; y (rows, 256) bf16 or None; norm = (weight, bias, eps); w: PackedWeight of the
-    (512, 256) pointwise-conv weight; bias (512) fp32.  x_out defaults to x (in place).  Returns g (rows, 256) bf16.
+    x (rows, D) fp32 contiguous, D = 256 or 144; y (rows, D) bf16 or None; norm = (weight, bias, eps); w: PackedWeight of the
+    (2D, D) pointwise-conv weight (at D = 144 padded to 160 columns: PackedWeight(w, pad=(288, 160))); bias (2D) fp32.  x_out defaults
+    to x (in place).  Returns g (rows, D) bf16.
     With ``ycat`` (rows, K) bf16 contiguous and ``out_w`` (PackedWeight of a (256, K) matrix, K a multiple of 128) instead of
-    ``y``, y = ycat @ out_w^T is formed inside the kernel (cm_ln_pw_glu_mix) and never written."""
+    ``y``, y = ycat @ out_w^T is formed inside the kernel (cm_ln_pw_glu_mix, D = 256 only) and never written."""
     _dev_check(x, y, bias, ycat)
     rows, d = x.shape
-    if x.dtype != torch.float32 or not x.is_contiguous() or d != 256:
-        raise RuntimeError("ln_pw_glu: x must be a contiguous fp32 (rows, 256) tensor")
+    if x.dtype != torch.float32 or not x.is_contiguous() or d not in (256, 144):
+        raise RuntimeError("ln_pw_glu: x must be a contiguous fp32 (rows, 256) or (rows, 144) tensor")
     if y is not None and (y.dtype != torch.bfloat16 or not y.is_contiguous() or y.shape != x.shape):
-        raise RuntimeError("ln_pw_glu: y must be a contiguous bf16 (rows, 256) tensor")
-    if not isinstance(w, PackedWeight) or w.shape != (512, 256):
-        raise RuntimeError("ln_pw_glu: w must be a PackedWeight of shape (512, 256)")
+        raise RuntimeError("ln_pw_glu: y must be a contiguous bf16 tensor shaped like x")
+    if not isinstance(w, PackedWeight) or w.layout != 16 or w.shape != (2 * d, d) or w.padded != (2 * d, _kpad(d)):
+        raise RuntimeError("ln_pw_glu: w must be a PackedWeight (16-row tiles) of shape (2D, D), at D = 144 padded to (288, 160)")
+    if d != 256 and ycat is not None:
+        raise RuntimeError("ln_pw_glu: the projection in front (ycat, out_w) needs d_model 256")
     g_, b_, bs = _f32c(norm[0]), _f32c(norm[1]), _f32c(bias)
     xo = x if x_out is None else x_out
     out = torch.empty((rows, d), dtype=torch.bfloat16, device=x.device)
@@ -1711,7 +1714,8 @@ def gemm_bf16(a, w, bias=None, epilogue=0, x=None, alpha=1.0, norm1=None, norm2=
 
 
 def ffn_supported(d_model: int, hidden: int, dtype) -> bool:
-    return dtype == torch.bfloat16 and d_model == 256 and hidden >= 256 and hidden % 256 == 0
+    """cm_ffn_fused's inference forward covers the module: d_model 256, or 144 on the 16x16x32 kernel (csrc/fused_d144.hip)."""
+    return dtype == torch.bfloat16 and (d_model == 256 or (d_model == 144 and FFN_LAYOUT == 16)) and hidden >= 256 and hidden % 256 == 0
 
 
 # cm_ffn_fused's inference forward on v_mfma_f32_32x32x16_bf16 (csrc/ffn_fused32.hip, weights in the 32 x 16 tile image) instead of
@@ -1726,11 +1730,18 @@ SMALL_FFN_ROWS = int(os.environ.get("CM_FFN_SMALL_ROWS", "0"))
 FFN_RESID_ACC = os.environ.get("CM_FFN_RESID_ACC", "1") == "1"
 
 
+def _kpad(d: int) -> int:
+    """A width padded to whole 32-column k-tiles: 144 -> 160 (the d_model-144 kernels' weight images), 256 -> 256."""
+    return (d + 31) // 32 * 32
+
+
 class PackedWeight:
     """A bf16 (rows, cols) matrix in a fragment-tiled image: ``layout`` 16 = 16-row x 32-column tiles (cm_ffn_pack_weights: every
-    kernel that streams packed weights), 32 = 32 x 16 tiles (cm_ffn_pack_weights32: cm_ffn_fused with cm_ffn_args.layout = 1)."""
+    kernel that streams packed weights), 32 = 32 x 16 tiles (cm_ffn_pack_weights32: cm_ffn_fused with cm_ffn_args.layout = 1).
+    ``pad`` = (rows, cols) >= the matrix's: the image is that of the matrix padded with zeros at the bottom and on the right (the
+    d_model-144 kernels read 160-column / 160-row images); ``shape`` stays the matrix's own, ``padded`` is the image's."""
 
-    def __init__(self, w: torch.Tensor, layout: int = 16):
+    def __init__(self, w: torch.Tensor, layout: int = 16, pad=None):
         _dev_check(w)
         if w.dtype != torch.bfloat16 or w.dim() != 2:
             raise RuntimeError("PackedWeight: expected a 2-D bf16 tensor")
@@ -1738,8 +1749,11 @@ class PackedWeight:
             raise RuntimeError("PackedWeight: layout must be 16 or 32")
         w = w.contiguous()
         self.shape = tuple(w.shape)
+        self.padded = self.shape if pad is None else (int(pad[0]), int(pad[1]))
+        if self.padded[0] < self.shape[0] or self.padded[1] < self.shape[1]:
+            raise RuntimeError("PackedWeight: pad must be at least the matrix's shape")
         self.layout = layout
-        self.data = torch.empty(w.numel(), dtype=torch.bfloat16, device=w.device)
+        self.data = torch.empty(self.padded[0] * self.padded[1], dtype=torch.bfloat16, device=w.device)
         self.repack_(w)
 
     def repack_(self, w: torch.Tensor) -> "PackedWeight":
@@ -1747,6 +1761,8 @@ class PackedWeight:
         if w.dtype != torch.bfloat16 or tuple(w.shape) != self.shape or w.device != self.data.device:
             raise RuntimeError("PackedWeight.repack_: expected a bf16 tensor of the packed shape on the image's device")
         w = w.contiguous()
+        if self.padded != self.shape:
+            w = torch.nn.functional.pad(w, (0, self.padded[1] - self.shape[1], 0, self.padded[0] - self.shape[0]))
         fn = N.lib().cm_ffn_pack_weights if self.layout == 16 else N.lib().cm_ffn_pack_weights32
         rc = fn(_ptr(w), w.shape[0], w.shape[1], _ptr(self.data), _stream())
         N.check(rc, "cm_ffn_pack_weights")
@@ -1759,26 +1775,33 @@ def ffn_fused(x, pre_norm, w1, b1, w2, b2, alpha=0.5, addend=None, add_scale=1.0
     """Whole feed-forward module on the fp32 residual stream (cm_ffn_fused):
         xin = x + add_scale*addend;  r = xin + alpha*(W2 gelu(W1 LN_pre(xin) + b1) + b2);  r = LN1(r) if norm1;
         x_out <- r (x itself when x_out is None);  returns h = LN2(r) (or r when norm2 is None) in h_dtype if want_h.
-    x (rows, 256) fp32; w1 (hidden, 256) / w2 (256, hidden) bf16 tensors or PackedWeight (pack once, reuse); b1/b2 and
-    LayerNorm parameters fp32; addend (rows, 256) bf16; norm = (weight, bias, eps).
-    With ``proj_w`` (PackedWeight (P, 256), P % 256 == 0; ``proj_b`` fp32 (P) or None) the Linear that consumes h runs in the
+    x (rows, D) fp32, D = 256 or 144; w1 (hidden, D) / w2 (D, hidden) bf16 tensors or PackedWeight (pack once, reuse); b1/b2 and
+    LayerNorm parameters fp32; addend (rows, D) bf16; norm = (weight, bias, eps).
+    With ``proj_w`` (PackedWeight (P, D), P % 256 == 0; ``proj_b`` fp32 (P) or None) the Linear that consumes h runs in the
     same kernel and (rows, P) bf16 = h @ proj_w^T (+ proj_b) is returned in h's place; h itself is not stored.
+    D = 144 (inference, layout 16 only): P % 64 == 0, and the images are padded to whole tiles -- PackedWeight(w1, pad=(hidden, 160)),
+    PackedWeight(w2, pad=(160, hidden)), PackedWeight(proj_w, pad=(P, 160)); bf16 tensors given in their place are padded here.
     ``train`` = (p1, p2, seed1, seed2): the module's TRAINING forward, x_out = x + alpha * drop_p2(W2 drop_p1(gelu(bf16(W1 LN(x) + b1))) + b2)
-    with the backward's inputs stored on the way -> (x_out, (pre, xn, stats)): pre (rows, hidden) bf16 = W1 LN(x) + b1, xn (rows, 256)
+    with the backward's inputs stored on the way (D = 256 only) -> (x_out, (pre, xn, stats)): pre (rows, hidden) bf16 = W1 LN(x) + b1, xn (rows, 256)
     bf16 = LN(x), stats (2, rows) fp32 = the rows' mean and 1/std (layernorm_bwd's input); the dropout decisions are cm_dropout.h's function of (seed, element index) (no mask is stored).
     ``resid_acc`` (default: CM_FFN_RESID_ACC): False = the residual rows are loaded again behind the last GEMM instead of riding in the
     accumulators (any alpha that is no power of two takes that path by itself)."""
     _dev_check(x, b1, b2, addend, proj_b)
     rows, d = x.shape
     if x.dtype != torch.float32 or not x.is_contiguous():
-        raise RuntimeError("ffn_fused: x must be a contiguous fp32 (rows, 256) tensor")
-    if d != 256:
-        raise RuntimeError(f"ffn_fused: d_model must be 256 (got {d})")
-    lay = w1.layout if isinstance(w1, PackedWeight) else (w2.layout if isinstance(w2, PackedWeight) else (16 if train is not None else FFN_LAYOUT))
-    w1 = w1 if isinstance(w1, PackedWeight) else PackedWeight(w1, lay)
-    w2 = w2 if isinstance(w2, PackedWeight) else PackedWeight(w2, lay)
+        raise RuntimeError("ffn_fused: x must be a contiguous fp32 (rows, d_model) tensor")
+    if d != 256 and (d != 144 or train is not None):
+        raise RuntimeError(f"ffn_fused: d_model must be 256 (got {d}; 144 runs the inference forward only)")
+    lay = w1.layout if isinstance(w1, PackedWeight) else (w2.layout if isinstance(w2, PackedWeight) else (16 if train is not None or d != 256 else FFN_LAYOUT))
+    kp = _kpad(d)                                           # 144: images padded to 160 columns (w1, proj_w) / 160 rows (w2)
+    w1 = w1 if isinstance(w1, PackedWeight) else PackedWeight(w1, lay, pad=(w1.shape[0], kp))
+    w2 = w2 if isinstance(w2, PackedWeight) else PackedWeight(w2, lay, pad=(kp, w2.shape[1]))
     if w1.shape[1] != d or w2.shape != (d, w1.shape[0]):
         raise RuntimeError("ffn_fused: weight shapes do not match x")
+    if w1.padded != (w1.shape[0], kp) or w2.padded != (kp, w2.shape[1]):
+        raise RuntimeError("ffn_fused: at d_model 144 the images are padded: PackedWeight(w1, pad=(hidden, 160)), PackedWeight(w2, pad=(160, hidden))")
+    if d != 256 and w1.layout != 16:
+        raise RuntimeError("ffn_fused: d_model 144 takes layout-16 weights")
     if w1.layout != w2.layout or (proj_w is not None and isinstance(proj_w, PackedWeight) and proj_w.layout != w1.layout):
         raise RuntimeError("ffn_fused: w1, w2 and proj_w must be packed in the same layout")
     if train is not None and w1.layout != 16:
@@ -1821,8 +1844,10 @@ def ffn_fused(x, pre_norm, w1, b1, w2, b2, alpha=0.5, addend=None, add_scale=1.0
         _launch("cm_ffn_fused", N.lib().cm_ffn_fused, a, units=rows)
         return xo, (pre, xn, stats)
     if proj_w is not None:
-        if not isinstance(proj_w, PackedWeight) or proj_w.shape[1] != d or proj_w.shape[0] % 256 or proj_w.shape[0] > 4096:
-            raise RuntimeError("ffn_fused: proj_w must be a PackedWeight of shape (P, 256), P a multiple of 256 up to 4096")
+        if (not isinstance(proj_w, PackedWeight) or proj_w.shape[1] != d or proj_w.shape[0] % (256 if d == 256 else 64) or proj_w.shape[0] > 4096
+                or proj_w.padded != (proj_w.shape[0], kp)):
+            raise RuntimeError("ffn_fused: proj_w must be a PackedWeight of shape (P, d_model), P a multiple of 256 up to 4096 "
+                               "(d_model 144: padded to (P, 160), P a multiple of 64)")
         h = proj_out if proj_out is not None else torch.empty((rows, proj_w.shape[0]), dtype=torch.bfloat16, device=x.device)
         if h.shape != (rows, proj_w.shape[0]) or h.dtype != torch.bfloat16 or not h.is_contiguous():
             raise RuntimeError("ffn_fused: proj_out must be a contiguous bf16 (rows, P) tensor")
