@@ -651,6 +651,33 @@ typedef struct cm_conv_xproj_args {
 int cm_conv_xproj(const cm_conv_xproj_args *args);
 
 /* ---------------------------------------------------------------------------------------
+ * ONE causal direction of cm_conv_xproj with a history input (bf16 only): the UniMamba mixer of the causal encoder
+ * (reference modules/Conmamba.py:580-584), whole utterances or a stream of chunks.
+ *   y[b,t,:]    = SiLU(conv4([x_hist | x])[b,t,:])      xdbl[b,t, 0:dt_pad+32] = y[b,t,:] @ Wx^T
+ * x_hist (batch, 3, dim) contiguous holds the three rows in front of this chunk; NULL = zeros (the start of an
+ * utterance).  x_hist_out (batch, 3, dim) contiguous, optional, receives the last three rows of [x_hist | x] (right for
+ * seqlen 1 and 2 too): the next chunk's x_hist.  x_hist_out must not overlap x_hist -- other workgroups of the launch
+ * still read it -- so a caller keeps two buffers and swaps them (CM_EINVAL otherwise).  Chunked or whole, y and xdbl
+ * come out bit for bit the same.  dim, strides, alignment: as cm_conv_xproj; x_hist / x_hist_out 8-byte aligned.
+ * Every check is made before anything is launched.
+ * ------------------------------------------------------------------------------------- */
+typedef struct cm_conv_xproj_uni_args {
+    int32_t batch, seqlen, dim, width;
+    const void  *x;
+    const float *weight, *bias;                           /* (dim, 4) / (dim) or NULL             */
+    const void  *wx;                                      /* packed (dt_pad + 32, dim) bf16       */
+    void *y, *xdbl;                                       /* (batch, seqlen, dim) / (batch, seqlen, dt_pad + 32) */
+    const void *x_hist;                                   /* (batch, 3, dim) or NULL              */
+    void *x_hist_out;                                     /* (batch, 3, dim) or NULL              */
+    int64_t x_bs, x_ts, y_bs, y_ts, xdbl_bs, xdbl_ts;
+    void *stream;
+    int32_t dt_pad;                                       /* 0 / 16 or 32, as cm_conv_xproj_args.dt_pad */
+    int32_t variant;                                      /* as cm_conv_xproj_args.variant        */
+} cm_conv_xproj_uni_args;
+
+int cm_conv_xproj_uni(const cm_conv_xproj_uni_args *args);
+
+/* ---------------------------------------------------------------------------------------
  * Residual add + LayerNorm(s) over the last axis (rows x dim), fused:
  *   r   = x + alpha * y                       (y optional; x fp32 residual stream)
  *   if norm1: r1 = LN(r; g1, b1, eps1) else r1 = r
@@ -706,6 +733,39 @@ typedef struct cm_glu_dwconv_args {
 } cm_glu_dwconv_args;
 
 int cm_glu_dwconv_ln_gelu(const cm_glu_dwconv_args *args);
+
+/* ---------------------------------------------------------------------------------------
+ * The same core for ConvolutionModule(causal=True) (reference modules/Conmamba.py:230-238, :445-446: pad both sides by
+ * ksize - 1, chomp the tail = all ksize - 1 padding rows in front), with a history input for a stream of chunks.
+ * Fields as cm_glu_dwconv_args, and:
+ *   hist     (batch, ksize - 1, dim) contiguous, I/O dtype: the GATED rows (the GLU's outputs) in front of this chunk;
+ *            NULL = zeros (the start of an utterance);
+ *   hist_out (batch, ksize - 1, dim) contiguous, optional: the last ksize - 1 rows of [hist | this chunk's gated rows]
+ *            (right for seqlen < ksize - 1 too): the next chunk's hist.  It must not overlap hist -- other workgroups of
+ *            the launch still read it -- so a caller keeps two buffers and swaps them (CM_EINVAL otherwise).
+ * Chunked or whole, `out` comes out bit for bit the same.  hist: 16-byte aligned where rows are whole 16-byte pieces,
+ * else 4; hist_out: 4-byte aligned.  Every check is made before anything is launched.
+ * ------------------------------------------------------------------------------------- */
+typedef struct cm_glu_dwconv_causal_args {
+    int32_t batch, seqlen, dim, ksize;
+    int32_t io_dtype;
+    int32_t glu_done;
+    const void  *in;
+    const float *weight;
+    const float *bias;
+    const float *ln_g, *ln_b;
+    float eps;
+    int32_t variant;
+    void *out;
+    void *stream;
+    const float *weight_t;
+    const void  *lin_w;
+    const float *lin_b;
+    const void  *hist;
+    void        *hist_out;
+} cm_glu_dwconv_causal_args;
+
+int cm_glu_dwconv_ln_gelu_causal(const cm_glu_dwconv_causal_args *args);
 
 /* ---------------------------------------------------------------------------------------
  * Single-step (decode-time) updates of a Mamba mixer: the two calls of bimamba.Mamba.step (reference

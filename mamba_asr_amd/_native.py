@@ -155,6 +155,15 @@ class ConvXprojArgs(C.Structure):
     ]
 
 
+class ConvXprojUniArgs(C.Structure):
+    _fields_ = [
+        ("batch", i32), ("seqlen", i32), ("dim", i32), ("width", i32),
+        ("x", vp), ("weight", fp), ("bias", fp), ("wx", vp), ("y", vp), ("xdbl", vp), ("x_hist", vp), ("x_hist_out", vp),
+        ("x_bs", i64), ("x_ts", i64), ("y_bs", i64), ("y_ts", i64), ("xdbl_bs", i64), ("xdbl_ts", i64),
+        ("stream", vp), ("dt_pad", i32), ("variant", i32),
+    ]
+
+
 class ConvUpdateArgs(C.Structure):
     _fields_ = [
         ("batch", i32), ("dim", i32), ("width", i32), ("io_dtype", i32), ("silu", i32), ("pad_", i32),
@@ -243,6 +252,10 @@ class GluDwconvArgs(C.Structure):
         ("in_", vp), ("weight", fp), ("bias", fp), ("ln_g", fp), ("ln_b", fp), ("eps", C.c_float), ("variant", i32),
         ("out", vp), ("stream", vp), ("weight_t", fp), ("lin_w", vp), ("lin_b", fp),
     ]
+
+
+class GluDwconvCausalArgs(C.Structure):
+    _fields_ = GluDwconvArgs._fields_ + [("hist", vp), ("hist_out", vp)]
 
 
 class CnnBlock1Args(C.Structure):
@@ -398,8 +411,10 @@ SYMBOLS = [
     ("cm_conv_cl_bwd_workspace_floats", C.c_int64, [i32, i32, i32]),
     ("cm_conv_cl_bwd", C.c_int, [C.POINTER(ConvClBwdArgs)]),
     ("cm_conv_xproj", C.c_int, [C.POINTER(ConvXprojArgs)]),
+    ("cm_conv_xproj_uni", C.c_int, [C.POINTER(ConvXprojUniArgs)]),
     ("cm_add_layernorm", C.c_int, [C.POINTER(AddLnArgs)]),
     ("cm_glu_dwconv_ln_gelu", C.c_int, [C.POINTER(GluDwconvArgs)]),
+    ("cm_glu_dwconv_ln_gelu_causal", C.c_int, [C.POINTER(GluDwconvCausalArgs)]),
     ("cm_ln_pw_glu", C.c_int, [C.POINTER(LnPwGluArgs)]),
     ("cm_ln_pw_glu_mix", C.c_int, [C.POINTER(LnPwGluMixArgs)]),
     ("cm_causal_conv1d_update", C.c_int, [C.POINTER(ConvUpdateArgs)]),

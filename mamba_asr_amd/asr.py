@@ -39,6 +39,7 @@ class ASRConfig:
     max_decode_ratio: float = 1.0
     decoder_module: str = "mamba"   # "transformer": hparams/S2S/conmamba_{small,large}.yaml leave the default decoder
     nhead: int = 4                  # heads of the Transformer decoder (the ConMamba encoder and the Mamba decoder have none)
+    causal: bool = False            # True: UniMamba mixers + front-padded conv modules -- the encoder that can be streamed (encode_streaming)
 
 
 CONFIGS = {
@@ -80,7 +81,7 @@ class ConMambaASR(nn.Module):
             input_size=(cfg.n_mels // 4) * 32, tgt_vocab=cfg.output_neurons, d_model=cfg.d_model, nhead=cfg.nhead,
             num_encoder_layers=cfg.num_encoder_layers, num_decoder_layers=cfg.num_decoder_layers, d_ffn=cfg.d_ffn,
             dropout=cfg.transformer_dropout, activation=nn.GELU, encoder_module="conmamba",
-            decoder_module=cfg.decoder_module, attention_type="RelPosMHAXL", normalize_before=True, causal=False,
+            decoder_module=cfg.decoder_module, attention_type="RelPosMHAXL", normalize_before=True, causal=cfg.causal,
             mamba_config=mamba_config)
         self.ctc_lin = sb.Linear(input_size=cfg.d_model, n_neurons=cfg.output_neurons)
         if cfg.num_decoder_layers > 0:
@@ -115,6 +116,12 @@ class ConMambaASR(nn.Module):
                 return fused.asr_encode(self, wavs, wav_lens)                    # native inference path
         src = self.CNN(self.features(wavs, wav_lens, epoch, augment))
         return self.Transformer.encode(src, wav_lens)
+
+    def encode_streaming(self, src, context):
+        """The next chunk of the CNN front end's output rows (B, t, F, C) or (B, t, F * C) of the streams in ``context``
+        (self.Transformer.make_streaming_context(None, dict(batch_size=B))) -> encoder output (B, t, d_model).  Streaming starts behind the front end: the Fbank's top_db clamp and the CNN blocks' reflect padding
+        in time look at the future of the utterance."""
+        return self.Transformer.encode_streaming(src, context)
 
     def forward_ctc(self, wavs, wav_lens, epoch=0, augment=None, feats=None):
         """-> log-probabilities (B, T', vocab), train_CTC.py:296-302."""

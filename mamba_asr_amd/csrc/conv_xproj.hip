@@ -12,7 +12,13 @@
 //            straight from their packed image in L2 (cm_ffn_pack_weights layout, 1 KB per fragment), so a lane ends
 //            up with 4 consecutive features of one token = one 8-byte store into the x_dbl row.
 // HBM traffic: x once (+ a 6-row halo per 16, served by the XCD's L2), u twice E per step written, 192 B of x_dbl per step.
+//
+// cm_conv_xproj_uni is the same kernel with the backward direction compiled out (the causal encoder's UniMamba mixer) and a
+// history input: the three rows in front of the chunk come from x_hist instead of the zero padding, and the last three rows of
+// [x_hist | x] leave as x_hist_out, so a stream of chunks convolves exactly like the whole sequence.
 #include "cm_common.h"
+
+#include <type_traits>
 
 
 namespace {
@@ -44,9 +50,18 @@ __device__ __forceinline__ unsigned long long cx_now() {
     return t;
 }
 
+// the single-direction launch's arguments inside this file: cm_conv_xproj_args' fields (the backward ones unused) + the history rows
+struct cx_uni_args : cm_conv_xproj_args {
+    const void *x_hist;
+    void *x_hist_out;
+};
+
 // NB: 16-column bands of x_dbl per direction: 3 = [dt16 | B | C], 4 = [dt32 | B | C] (dt_rank 17..32: the S2S-large encoder)
-template <int TT, int NB>
-__global__ __launch_bounds__(256, (TT == 16 && NB == 3) ? 4 : 2) void conv_xproj_kernel(const cm_conv_xproj_args p, const int ntile, const int stamp_arg = 0) {
+template <int TT, int NB, typename P = cm_conv_xproj_args>
+__global__ __launch_bounds__(256, (TT == 16 && NB == 3) ? 4 : 2) void conv_xproj_kernel(const P p, const int ntile, const int stamp_arg = 0) {
+    constexpr bool UNI = std::is_same<P, cx_uni_args>::value;     // one direction, rows in front of the chunk from p.x_hist
+    constexpr int HR = UNI ? 0 : W - 1;                           // rows behind a step that its outputs read
+    constexpr int NR = (W - 1) + HR, NWIN = NR + 1;               // halo rows per run of steps; rows of the sliding window
 #ifdef CM_ABLATE
     const int stamp = stamp_arg;
 #else
@@ -77,16 +92,32 @@ __global__ __launch_bounds__(256, (TT == 16 && NB == 3) ? 4 : 2) void conv_xproj
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(reinterpret_cast<const uint16_t *>(base) + (int64_t)b * bs), 0,
                                                  bytes > 0x7fffffff ? 0x7fffffff : (int)bytes, 0x00020000);
     };
-    const __amdgpu_buffer_rsrc_t xr = rsrc(p.x, p.x_bs, x_ts), fr = rsrc(p.y_fwd, p.yf_bs, yf_ts), br = rsrc(p.y_bwd, p.yb_bs, yb_ts);
+    const __amdgpu_buffer_rsrc_t xr = rsrc(p.x, p.x_bs, x_ts), fr = rsrc(p.y_fwd, p.yf_bs, yf_ts), br = rsrc(UNI ? p.y_fwd : p.y_bwd, UNI ? p.yf_bs : p.yb_bs, UNI ? yf_ts : yb_ts);
+    __amdgpu_buffer_rsrc_t hr = xr;                               // UNI: this utterance's (3, E) history rows; NULL = an empty buffer (zeros)
+    if constexpr (UNI) {
+        hr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(reinterpret_cast<const uint16_t *>(p.x_hist) + (int64_t)b * (W - 1) * E), 0,
+                                               p.x_hist ? (W - 1) * E * 2 : 0, 0x00020000);
+        // the last W-1 rows of [x_hist | x], by the workgroup of the utterance's last tile (x_hist_out never aliases x_hist: checked at entry)
+        if (p.x_hist_out && id % ntile == ntile - 1) {
+            uint16_t *ho = reinterpret_cast<uint16_t *>(p.x_hist_out) + (int64_t)b * (W - 1) * E;
+            for (int idx = tid; idx < (W - 1) * (E / 4); idx += 256) {
+                const int j = idx / (E / 4), c0 = (idx % (E / 4)) * 4, t = T - (W - 1) + j;
+                const u32x2 v = t >= 0 ? __builtin_amdgcn_raw_buffer_load_b64(xr, c0 * 2, t * x_ts, 0)
+                                       : __builtin_amdgcn_raw_buffer_load_b64(hr, c0 * 2, (t + W - 1) * E * 2, 0);
+                *reinterpret_cast<u32x2 *>(ho + j * E + c0) = v;
+            }
+        }
+    }
 
     // ---- phase 2's operands, set up first: wave = (direction, K half); the 32-step build requests its weights now
     constexpr bool EARLY = TT == 32 || NB == 4;              // builds with a 256-VGPR budget
     constexpr int NTL = TT / 16;                                  // token tiles per workgroup
     const int l15 = lane & 15, lq = lane >> 4;
     const int nks = E / 32;
-    const int dir = wave & 1, kh = wave >> 1;
+    const int dir = UNI ? 0 : wave & 1, kh = UNI ? wave : wave >> 1;          // UNI: waves 0 and 1 split K, waves 2 and 3 only convolve
     const bool ksplit = (nks & 1) == 0 && cm_ksplit_ok(stamp);
-    const int ks_lo = ksplit ? kh * (nks / 2) : 0, ks_hi = ksplit ? ks_lo + nks / 2 : (kh == 0 ? nks : 0);
+    const bool idle = UNI && kh >= 2;
+    const int ks_lo = ksplit && !idle ? kh * (nks / 2) : 0, ks_hi = idle ? 0 : (ksplit ? ks_lo + nks / 2 : (kh == 0 ? nks : 0));
     const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void *>(dir ? p.wx_b : p.wx_f), 0, NP * E * 2, 0x00020000);
     const int vl = lane * 16;
@@ -103,10 +134,17 @@ __global__ __launch_bounds__(256, (TT == 16 && NB == 3) ? 4 : 2) void conv_xproj
     const int ts = t0 + TH * half;                                // first step of this thread (wave-uniform)
     for (int cg = tid & 127; cg < E / 4; cg += 128) {
         const int c0 = cg * 4;
-        u32x2 raw[TH + 2 * (W - 1)];                              // rows ts-3 .. ts+TH+2, all loads issued first
+        u32x2 raw[TH + NR];                                       // rows ts-3 .. ts+TH+2 (UNI: .. ts+TH-1), all loads issued first
 #pragma unroll
-        for (int r = 0; r < TH + 2 * (W - 1); ++r)
-            raw[r] = __builtin_amdgcn_raw_buffer_load_b64(xr, c0 * 2, (ts - (W - 1) + r) * x_ts, 0);
+        for (int r = 0; r < TH + NR; ++r) {
+            if constexpr (UNI) {
+                const int row = ts - (W - 1) + r;                 // wave-uniform
+                raw[r] = row < 0 ? __builtin_amdgcn_raw_buffer_load_b64(hr, c0 * 2, (row + W - 1) * E * 2, 0)
+                                 : __builtin_amdgcn_raw_buffer_load_b64(xr, c0 * 2, row * x_ts, 0);
+            } else {
+                raw[r] = __builtin_amdgcn_raw_buffer_load_b64(xr, c0 * 2, (ts - (W - 1) + r) * x_ts, 0);
+            }
+        }
         if (!wq_requested) {                                      // behind the rows (HBM) in the in-order return queue: phase 1 waits
             wq_requested = true;                                  // for the rows only, the L2-resident weights land during it
 #pragma unroll
@@ -122,12 +160,12 @@ __global__ __launch_bounds__(256, (TT == 16 && NB == 3) ? 4 : 2) void conv_xproj
         for (int pr = 0; pr < 2; ++pr) {
             const float4 f0 = *reinterpret_cast<const float4 *>(p.weight_f + (c0 + 2 * pr) * W);
             const float4 f1 = *reinterpret_cast<const float4 *>(p.weight_f + (c0 + 2 * pr + 1) * W);
-            const float4 g0 = *reinterpret_cast<const float4 *>(p.weight_b + (c0 + 2 * pr) * W);
-            const float4 g1 = *reinterpret_cast<const float4 *>(p.weight_b + (c0 + 2 * pr + 1) * W);
+            const float4 g0 = UNI ? f0 : *reinterpret_cast<const float4 *>(p.weight_b + (c0 + 2 * pr) * W);
+            const float4 g1 = UNI ? f1 : *reinterpret_cast<const float4 *>(p.weight_b + (c0 + 2 * pr + 1) * W);
             wf[pr][0] = f32x2{f0.x, f1.x}; wf[pr][1] = f32x2{f0.y, f1.y}; wf[pr][2] = f32x2{f0.z, f1.z}; wf[pr][3] = f32x2{f0.w, f1.w};
             wb[pr][0] = f32x2{g0.x, g1.x}; wb[pr][1] = f32x2{g0.y, g1.y}; wb[pr][2] = f32x2{g0.z, g1.z}; wb[pr][3] = f32x2{g0.w, g1.w};
             bf[pr] = p.bias_f ? f32x2{p.bias_f[c0 + 2 * pr], p.bias_f[c0 + 2 * pr + 1]} : f32x2{0.f, 0.f};
-            bb[pr] = p.bias_b ? f32x2{p.bias_b[c0 + 2 * pr], p.bias_b[c0 + 2 * pr + 1]} : f32x2{0.f, 0.f};
+            bb[pr] = !UNI && p.bias_b ? f32x2{p.bias_b[c0 + 2 * pr], p.bias_b[c0 + 2 * pr + 1]} : f32x2{0.f, 0.f};
         }
         auto widen = [&](int r, int pr) -> f32x2 { return f32x2{cm_bf16_lo(raw[r][pr]), cm_bf16_hi(raw[r][pr])}; };
         auto silu2 = [](f32x2 a) -> f32x2 {                       // a / (1 + 2^(-a log2 e))
@@ -135,13 +173,13 @@ __global__ __launch_bounds__(256, (TT == 16 && NB == 3) ? 4 : 2) void conv_xproj
             const f32x2 d = f32x2{cm_exp2(e.x), cm_exp2(e.y)} + f32x2{1.0f, 1.0f};
             return a * f32x2{cm_rcp(d.x), cm_rcp(d.y)};
         };
-        f32x2 xw[2 * (W - 1) + 1][2];                             // rows i .. i+6 of the window, [row][pair]
+        f32x2 xw[NWIN][2];                                        // rows i .. i+6 (UNI: i+3) of the window, [row][pair]
 #pragma unroll
-        for (int r = 0; r < 2 * (W - 1); ++r) { xw[r][0] = widen(r, 0); xw[r][1] = widen(r, 1); }
+        for (int r = 0; r < NR; ++r) { xw[r][0] = widen(r, 0); xw[r][1] = widen(r, 1); }
 #pragma unroll
         for (int i = 0; i < TH; ++i) {
-            xw[2 * (W - 1)][0] = widen(i + 2 * (W - 1), 0);
-            xw[2 * (W - 1)][1] = widen(i + 2 * (W - 1), 1);
+            xw[NR][0] = widen(i + NR, 0);
+            xw[NR][1] = widen(i + NR, 1);
             u32x2 pf, pb;
 #pragma unroll
             for (int pr = 0; pr < 2; ++pr) {
@@ -149,19 +187,19 @@ __global__ __launch_bounds__(256, (TT == 16 && NB == 3) ? 4 : 2) void conv_xproj
 #pragma unroll
                 for (int k = 0; k < W; ++k) {
                     af = __builtin_elementwise_fma(wf[pr][k], xw[k][pr], af);                     // x[t-(W-1)+k]
-                    ab = __builtin_elementwise_fma(wb[pr][k], xw[2 * (W - 1) - k][pr], ab);       // x[t+(W-1)-k]
+                    if constexpr (!UNI) ab = __builtin_elementwise_fma(wb[pr][k], xw[NR - k][pr], ab);   // x[t+(W-1)-k]
                 }
-                const f32x2 of = silu2(af), ob = silu2(ab);
+                const f32x2 of = silu2(af), ob = UNI ? of : silu2(ab);
                 pf[pr] = pack2(of.x, of.y);
                 pb[pr] = pack2(ob.x, ob.y);
             }
             const int tl = TH * half + i;
             *reinterpret_cast<u32x2 *>(ut[0] + tl * XS + c0) = pf;
-            *reinterpret_cast<u32x2 *>(ut[1] + tl * XS + c0) = pb;
+            if constexpr (!UNI) *reinterpret_cast<u32x2 *>(ut[1] + tl * XS + c0) = pb;
             __builtin_amdgcn_raw_buffer_store_b64(pf, fr, c0 * 2, (ts + i) * yf_ts, 0);     // steps >= T: out of range, dropped
-            __builtin_amdgcn_raw_buffer_store_b64(pb, br, c0 * 2, (ts + i) * yb_ts, 0);
+            if constexpr (!UNI) __builtin_amdgcn_raw_buffer_store_b64(pb, br, c0 * 2, (ts + i) * yb_ts, 0);
 #pragma unroll
-            for (int r = 0; r < 2 * (W - 1); ++r) { xw[r][0] = xw[r + 1][0]; xw[r][1] = xw[r + 1][1]; }   // slide (register renaming)
+            for (int r = 0; r < NR; ++r) { xw[r][0] = xw[r + 1][0]; xw[r][1] = xw[r + 1][1]; }   // slide (register renaming)
         }
     }
     if (!wq_requested) {                                          // lanes without a channel group (dim < 512) skipped the loop
@@ -230,12 +268,12 @@ __global__ __launch_bounds__(256, (TT == 16 && NB == 3) ? 4 : 2) void conv_xproj
                 for (int mt = 0; mt < NB; ++mt) *reinterpret_cast<f32x4 *>(xch + (nt * NB + mt) * 4) = acc[nt][mt];
         }
         cm_lds_barrier();
-        if (kh == 1) return;
+        if (UNI ? kh != 0 : kh == 1) return;
 #pragma unroll
         for (int nt = 0; nt < NTL; ++nt)
 #pragma unroll
             for (int mt = 0; mt < NB; ++mt) acc[nt][mt] += *reinterpret_cast<const f32x4 *>(xch + (nt * NB + mt) * 4);
-    } else if (kh == 1) {
+    } else if (UNI ? kh != 0 : kh == 1) {
         return;
     }
 #pragma unroll
@@ -254,12 +292,15 @@ __global__ __launch_bounds__(256, (TT == 16 && NB == 3) ? 4 : 2) void conv_xproj
     }
 }
 
-template <int TT, int NB>
-int launch_cx(const cm_conv_xproj_args &a) {
-    const size_t smem = (size_t)2 * TT * (a.dim + 16) * sizeof(uint16_t);
+template <int TT, int NB, typename P>
+int launch_cx(const P &a) {
+    constexpr int ND = std::is_same<P, cx_uni_args>::value ? 1 : 2;
+    // the token tiles, and at least the K halves' exchange area that overlays them (64 lanes x TT / 16 x NB accumulators per direction)
+    const size_t tiles = (size_t)ND * TT * (a.dim + 16) * sizeof(uint16_t), xch = (size_t)ND * 64 * (TT / 16) * NB * 16;
+    const size_t smem = tiles > xch ? tiles : xch;
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_xproj_kernel<TT, NB>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_xproj_kernel<TT, NB, P>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            160 * 1024);
         if (e != hipSuccess) {
             cm_set_error("conv_xproj: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
@@ -269,8 +310,8 @@ int launch_cx(const cm_conv_xproj_args &a) {
     }
     const int ntile = (a.seqlen + TT - 1) / TT;
     CM_REQUIRE((long)ntile * a.batch < (1L << 31), CM_EINVAL, "conv_xproj: grid too large");
-    hipLaunchKernelGGL((conv_xproj_kernel<TT, NB>), dim3((unsigned)(ntile * a.batch)), dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), a, ntile, cm_debug_get() == 18 ? 1 : (cm_debug_get() == 19 ? 2 : 0));
-    return cm_launch_status("cm_conv_xproj");
+    hipLaunchKernelGGL((conv_xproj_kernel<TT, NB, P>), dim3((unsigned)(ntile * a.batch)), dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), a, ntile, cm_debug_get() == 18 ? 1 : (cm_debug_get() == 19 ? 2 : 0));
+    return cm_launch_status(ND == 1 ? "cm_conv_xproj_uni" : "cm_conv_xproj");
 }
 
 }  // namespace
@@ -300,5 +341,34 @@ extern "C" int cm_conv_xproj(const cm_conv_xproj_args *args) {
         CM_REQUIRE((size_t)2 * 16 * (a.dim + 16) * 2 <= 80 * 1024, CM_EUNSUPPORTED, "conv_xproj: dim %d too wide for 64-column rows", a.dim);
         return wide ? launch_cx<32, 4>(a) : launch_cx<16, 4>(a);
     }
+    return wide ? launch_cx<32, 3>(a) : launch_cx<16, 3>(a);
+}
+
+extern "C" int cm_conv_xproj_uni(const cm_conv_xproj_uni_args *args) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "conv_xproj_uni: args is NULL");
+    const cm_conv_xproj_uni_args &u = *args;
+    CM_REQUIRE(u.batch > 0 && u.seqlen > 0 && u.dim > 0 && u.x && u.weight && u.wx && u.y && u.xdbl, CM_EINVAL,
+               "conv_xproj_uni: bad sizes or NULL tensor");
+    CM_REQUIRE(u.width == W, CM_EUNSUPPORTED, "conv_xproj_uni: conv width %d unsupported (4 only)", u.width);
+    CM_REQUIRE(u.dim % 32 == 0 && u.dim <= 2048, CM_EUNSUPPORTED, "conv_xproj_uni: dim %d must be a multiple of 32, at most 2048", u.dim);
+    CM_REQUIRE(cm_aligned(u.x, 8) && cm_aligned(u.y, 8) && cm_aligned(u.xdbl, 8) && cm_aligned(u.weight, 16) && cm_aligned(u.wx, 16) &&
+                   (!u.x_hist || cm_aligned(u.x_hist, 8)) && (!u.x_hist_out || cm_aligned(u.x_hist_out, 8)) && u.x_bs % 4 == 0 &&
+                   u.x_ts % 4 == 0 && u.y_bs % 4 == 0 && u.y_ts % 4 == 0 && u.xdbl_bs % 4 == 0 && u.xdbl_ts % 4 == 0,
+               CM_EALIGN, "conv_xproj_uni: tensors must be 8-byte aligned (weights 16) with strides that are multiples of 4 elements");
+    CM_REQUIRE(u.dt_pad == 0 || u.dt_pad == 16 || u.dt_pad == 32, CM_EUNSUPPORTED, "conv_xproj_uni: dt_pad %d (16 or 32)", u.dt_pad);
+    if (u.x_hist && u.x_hist_out) {                               // other workgroups of the launch still read x_hist when the last one writes
+        const char *hi = reinterpret_cast<const char *>(u.x_hist), *ho = reinterpret_cast<const char *>(u.x_hist_out);
+        const int64_t bytes = (int64_t)u.batch * (W - 1) * u.dim * 2;
+        CM_REQUIRE(ho + bytes <= hi || hi + bytes <= ho, CM_EINVAL, "conv_xproj_uni: x_hist_out must not overlap x_hist");
+    }
+    cx_uni_args a{};
+    a.batch = u.batch, a.seqlen = u.seqlen, a.dim = u.dim, a.width = u.width;
+    a.x = u.x, a.weight_f = u.weight, a.bias_f = u.bias, a.wx_f = u.wx, a.y_fwd = u.y, a.xdbl = u.xdbl;
+    a.x_bs = u.x_bs, a.x_ts = u.x_ts, a.yf_bs = u.y_bs, a.yf_ts = u.y_ts, a.xdbl_bs = u.xdbl_bs, a.xdbl_ts = u.xdbl_ts;
+    a.stream = u.stream, a.dt_pad = u.dt_pad, a.variant = u.variant;
+    a.x_hist = u.x_hist, a.x_hist_out = u.x_hist_out;
+    // tile shape by cm_conv_xproj's rule, on one direction's LDS tile
+    const bool wide = a.variant != 1 && (size_t)32 * (a.dim + 16) * 2 <= 36 * 1024 && (long)a.batch * ((a.seqlen + 31) / 32) >= 512;
+    if (a.dt_pad == 32) return wide ? launch_cx<32, 4>(a) : launch_cx<16, 4>(a);
     return wide ? launch_cx<32, 3>(a) : launch_cx<16, 3>(a);
 }

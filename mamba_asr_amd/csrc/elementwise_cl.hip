@@ -5,6 +5,8 @@
 // All are HBM-bound: 16-byte vectors along the contiguous channel axis, every input read once.
 #include "cm_common.h"
 
+#include <type_traits>
+
 
 namespace {
 
@@ -188,35 +190,64 @@ __global__ __launch_bounds__(256) void add_ln_kernel(const cm_add_ln_args p) {
 // from LDS (conflict-free: consecutive threads, consecutive addresses) and writes the result back to LDS.
 // Phase 3: one wave per output row does LayerNorm + GELU and the coalesced store.
 // ------------------------------------------------------------------------------------------------
-template <typename IO, int K, int TT>
-__global__ __launch_bounds__(256) void glu_dwconv_kernel(const cm_glu_dwconv_args p) {
+// The causal launch's arguments inside this file (cm_glu_dwconv_ln_gelu_causal): all K - 1 padding rows in front, taken from
+// `hist` (gated rows, (batch, K - 1, dim); NULL = zeros), and the last K - 1 rows of [hist | gated rows] written to `hist_out`.
+struct dw_causal_args : cm_glu_dwconv_args {
+    const void *hist;
+    void *hist_out;
+};
+
+// hist_out <- the staged rows T - (K - 1) .. T - 1 (history rows where T < K - 1) of the utterance's LAST tile, which holds rows
+// t0 - (K - 1) .. t0 + TT - 1 in LDS at g (row stride D elements): row j of hist_out is staged row T - t0 + j.
+template <typename EL, int K>
+__device__ __forceinline__ void dw_store_hist(const EL *g, EL *hist_out, int b, int D, int T, int t0) {
+    EL *ho = hist_out + (int64_t)b * (K - 1) * D;
+    const int words = D * (int)sizeof(EL) / 4;                    // dim is even: whole 4-byte words
+    for (int idx = threadIdx.x; idx < (K - 1) * words; idx += blockDim.x) {
+        const int j = idx / words, w = idx % words;
+        reinterpret_cast<uint32_t *>(ho + j * D)[w] = reinterpret_cast<const uint32_t *>(g + (T - t0 + j) * D)[w];
+    }
+}
+
+template <typename IO, int K, int TT, typename P = cm_glu_dwconv_args>
+__global__ __launch_bounds__(256) void glu_dwconv_kernel(const P p) {
+    constexpr bool CAUSAL = std::is_same<P, dw_causal_args>::value;
+    constexpr int PL = CAUSAL ? K - 1 : K / 2;                    // padding rows in front
     constexpr int tt = TT;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int D = p.dim, T = p.seqlen;
     const int b = blockIdx.y, t0 = blockIdx.x * tt;
-    const int nin = tt + K - 1;                                   // input rows t0-K/2 .. t0+tt-1+K/2
+    const int nin = tt + K - 1;                                   // input rows t0-K/2 .. t0+tt-1+K/2 (causal: t0-(K-1) .. t0+tt-1)
     const int CS = D + 16;                                        // co row stride: rows of one wave land in different banks
     float *co = sm;                                               // [tt][CS] fp32 conv outputs
     IO *g = reinterpret_cast<IO *>(sm + (size_t)tt * CS);         // [nin][D] GLU outputs in the I/O dtype
     const bool pre = p.glu_done != 0;                              // input already gated: D-wide rows, plain copy
     const int IW = pre ? D : 2 * D;
     const IO *in = reinterpret_cast<const IO *>(p.in) + (int64_t)b * T * IW;
+    // causal: the gated row in front of the sequence at step t < 0, or NULL (zeros)
+    auto hist_row = [&](int t) -> const IO * {
+        if constexpr (CAUSAL) return p.hist && t < 0 ? reinterpret_cast<const IO *>(p.hist) + ((int64_t)b * (K - 1) + (K - 1 + t)) * D : nullptr;
+        else return nullptr;
+    };
     // phase 1: GLU rows -> LDS  (a = in[:, :D], gate = in[:, D:])
     constexpr int NV = cm_elem<IO>::kVec;
     if (pre && D % NV == 0) {
         for (int idx = threadIdx.x; idx < nin * (D / NV); idx += blockDim.x) {
             const int r = idx / (D / NV), c = (idx % (D / NV)) * NV;
-            const int t = t0 - K / 2 + r;
+            const int t = t0 - PL + r;
             uint4 v4 = {0u, 0u, 0u, 0u};
             if (t >= 0 && t < T) v4 = *reinterpret_cast<const uint4 *>(in + (int64_t)t * D + c);
+            else if (const IO *h = hist_row(t)) v4 = *reinterpret_cast<const uint4 *>(h + c);
             *reinterpret_cast<uint4 *>(g + r * D + c) = v4;
         }
     } else if (D % NV == 0) {
         for (int idx = threadIdx.x; idx < nin * (D / NV); idx += blockDim.x) {
             const int r = idx / (D / NV), c = (idx % (D / NV)) * NV;
-            const int t = t0 - K / 2 + r;
+            const int t = t0 - PL + r;
             float av[NV], gv[NV];
-            if (t >= 0 && t < T) {
+            if (const IO *h = hist_row(t)) {
+                vec8<IO>::load(h + c, av);
+            } else if (t >= 0 && t < T) {
                 const IO *row = in + (int64_t)t * 2 * D;
                 vec8<IO>::load(row + c, av);
                 vec8<IO>::load(row + D + c, gv);
@@ -231,16 +262,21 @@ __global__ __launch_bounds__(256) void glu_dwconv_kernel(const cm_glu_dwconv_arg
     } else {
         for (int idx = threadIdx.x; idx < nin * D; idx += blockDim.x) {
             const int r = idx / D, c = idx % D;
-            const int t = t0 - K / 2 + r;
+            const int t = t0 - PL + r;
             float v0 = 0.f;
             if (t >= 0 && t < T) {
                 const IO *row = in + (int64_t)t * IW;
                 v0 = pre ? cm_elem<IO>::load(row + c) : cm_elem<IO>::load(row + c) * cm_sigmoid(cm_elem<IO>::load(row + D + c));
+            } else if (const IO *h = hist_row(t)) {
+                v0 = cm_elem<IO>::load(h + c);
             }
             cm_elem<IO>::store(g + r * D + c, v0);
         }
     }
     __syncthreads();
+    if constexpr (CAUSAL) {
+        if (p.hist_out && blockIdx.x == gridDim.x - 1) dw_store_hist<IO, K>(g, reinterpret_cast<IO *>(p.hist_out), b, D, T, t0);
+    }
     // phase 2: depthwise conv along time
     for (int c = threadIdx.x; c < D; c += blockDim.x) {
         float w[K];
@@ -339,8 +375,10 @@ typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef __attribute__((ext_vector_type(8))) __bf16 dw_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float dw_f32x4;
 
-template <int K, int TT, int DV, bool LIN = false>
-__global__ __launch_bounds__(256, DV == 4 ? 4 : 2) void dwconv_rows_kernel(const cm_glu_dwconv_args p) {
+template <int K, int TT, int DV, bool LIN = false, typename P = cm_glu_dwconv_args>
+__global__ __launch_bounds__(256, DV == 4 ? 4 : 2) void dwconv_rows_kernel(const P p) {
+    constexpr bool CAUSAL = std::is_same<P, dw_causal_args>::value;
+    constexpr int PL = CAUSAL ? K - 1 : K / 2;                    // padding rows in front
     constexpr int D = DV * 64, NIN = TT + K - 1, TH = TT / 2, CS = D + 16, NIT = (D / 2 + 127) / 128;
     constexpr int XS = D + 8;                                     // LIN: activation row stride in bf16 elements
     static_assert(!LIN || (D == 256 && TT == 32), "the Linear epilogue is built for dim 256, 32-step tiles");
@@ -353,7 +391,13 @@ __global__ __launch_bounds__(256, DV == 4 ? 4 : 2) void dwconv_rows_kernel(const
     const bool pre = p.glu_done != 0;
     const int IW = pre ? D : 2 * D;
     const uint16_t *in = reinterpret_cast<const uint16_t *>(p.in) + (int64_t)b * T * IW;
-    // phase 1: rows t0 - K/2 .. t0 + TT - 1 + K/2 -> LDS, zero outside the sequence ('same' padding).
+    // causal: the gated row in front of the sequence at step t < 0, or NULL (zeros)
+    auto hist_row = [&](int t) -> const uint16_t * {
+        if constexpr (CAUSAL) return p.hist && t < 0 ? reinterpret_cast<const uint16_t *>(p.hist) + ((int64_t)b * (K - 1) + (K - 1 + t)) * D : nullptr;
+        else return nullptr;
+    };
+    // phase 1: rows t0 - K/2 .. t0 + TT - 1 + K/2 -> LDS, zero outside the sequence ('same' padding; causal: rows t0 - (K-1) .. t0 + TT - 1,
+    // those in front of the sequence from the history).
     // Already-gated rows (the encoder's call: cm_ln_pw_glu did the GLU): every 16-byte piece of the thread is requested before the
     // first one is waited for.  As a rolled loop (below, kept for the GLU form) the compiler emitted load -> s_waitcnt vmcnt(0) ->
     // ds_write per piece: eight dependent round trips per thread, "39 % of the workgroup's life waiting for its rows" in the stamps.
@@ -363,9 +407,10 @@ __global__ __launch_bounds__(256, DV == 4 ? 4 : 2) void dwconv_rows_kernel(const
 #pragma unroll
         for (int i = 0; i < NPC; ++i) {
             const int idx = tid + 256 * i, r = idx / (D / 8), c = (idx % (D / 8)) * 8;
-            const int t = t0 - K / 2 + r;
+            const int t = t0 - PL + r;
             v[i] = uint4{0u, 0u, 0u, 0u};
             if (idx < NCH && t >= 0 && t < T) v[i] = *reinterpret_cast<const uint4 *>(in + (int64_t)t * IW + c);
+            else if (const uint16_t *h = idx < NCH ? hist_row(t) : nullptr) v[i] = *reinterpret_cast<const uint4 *>(h + c);
         }
 #pragma unroll
         for (int i = 0; i < NPC; ++i) {
@@ -375,9 +420,11 @@ __global__ __launch_bounds__(256, DV == 4 ? 4 : 2) void dwconv_rows_kernel(const
     } else
     for (int idx = tid; idx < NIN * (D / 8); idx += 256) {
         const int r = idx / (D / 8), c = (idx % (D / 8)) * 8;
-        const int t = t0 - K / 2 + r;
+        const int t = t0 - PL + r;
         uint4 v = {0u, 0u, 0u, 0u};
-        if (t >= 0 && t < T) {
+        if (const uint16_t *h = hist_row(t)) {
+            v = *reinterpret_cast<const uint4 *>(h + c);
+        } else if (t >= 0 && t < T) {
             v = *reinterpret_cast<const uint4 *>(in + (int64_t)t * IW + c);
             if (!pre) {                                           // GLU: a * sigmoid(gate), gate = the row's second half
                 const uint4 q = *reinterpret_cast<const uint4 *>(in + (int64_t)t * IW + D + c);
@@ -392,6 +439,9 @@ __global__ __launch_bounds__(256, DV == 4 ? 4 : 2) void dwconv_rows_kernel(const
         *reinterpret_cast<uint4 *>(g + r * D + c) = v;
     }
     __syncthreads();
+    if constexpr (CAUSAL) {                                       // g is read only until the barrier behind phase 2
+        if (p.hist_out && blockIdx.x == gridDim.x - 1) dw_store_hist<uint16_t, K>(g, reinterpret_cast<uint16_t *>(p.hist_out), b, D, T, t0);
+    }
     // phase 2: depthwise conv, two channels x TH steps per thread, accumulated by input row
     const int rh = tid >> 7;                                      // wave-uniform
     f32x2_t acc[NIT][TH];
@@ -726,15 +776,31 @@ extern "C" int cm_add_layernorm(const cm_add_ln_args *args) {
     return cm_launch_status("cm_add_layernorm");
 }
 
-extern "C" int cm_glu_dwconv_ln_gelu(const cm_glu_dwconv_args *args) {
-    CM_REQUIRE(args != nullptr, CM_EINVAL, "glu_dwconv: args is NULL");
-    const cm_glu_dwconv_args &a = *args;
+namespace {
+
+// cm_glu_dwconv_ln_gelu (P = cm_glu_dwconv_args) and cm_glu_dwconv_ln_gelu_causal (P = dw_causal_args): one selection of kernels
+template <typename P>
+int glu_dwconv_dispatch(const P &a) {
+    constexpr bool CAUSAL = std::is_same<P, dw_causal_args>::value;
     CM_REQUIRE(a.batch > 0 && a.seqlen > 0 && a.dim > 0 && a.in && a.out && a.weight && a.ln_g && a.ln_b, CM_EINVAL,
                "glu_dwconv: bad sizes or NULL tensor");
     CM_REQUIRE(a.ksize == 31, CM_EUNSUPPORTED, "glu_dwconv: kernel size %d unsupported (31 only)", a.ksize);
     CM_REQUIRE(a.dim % 2 == 0, CM_EUNSUPPORTED, "glu_dwconv: dim must be even");
+    CM_REQUIRE(a.io_dtype == CM_BF16 || a.io_dtype == CM_F32, CM_EUNSUPPORTED, "glu_dwconv: unsupported dtype %d", a.io_dtype);
+    bool hist16 = true;                                           // the history rows allow the row kernel's 16-byte accesses
+    if constexpr (CAUSAL) {
+        CM_REQUIRE(cm_aligned(a.hist, 4) && cm_aligned(a.hist_out, 4), CM_EALIGN, "glu_dwconv: hist / hist_out must be 4-byte aligned");
+        if (a.hist && a.hist_out) {                               // other workgroups of the launch still read hist when the last one writes
+            const char *hi = reinterpret_cast<const char *>(a.hist), *ho = reinterpret_cast<const char *>(a.hist_out);
+            const int64_t bytes = (int64_t)a.batch * (a.ksize - 1) * a.dim * (a.io_dtype == CM_F32 ? 4 : 2);
+            CM_REQUIRE(ho + bytes <= hi || hi + bytes <= ho, CM_EINVAL, "glu_dwconv: hist_out must not overlap hist");
+        }
+        hist16 = cm_aligned(a.hist, 16);
+        if (a.dim % (a.io_dtype == CM_F32 ? 4 : 8) == 0)          // the generic kernel's 16-byte row pieces
+            CM_REQUIRE(hist16, CM_EALIGN, "glu_dwconv: hist must be 16-byte aligned at this dim");
+    }
     hipStream_t st0 = reinterpret_cast<hipStream_t>(a.stream);
-    if (a.io_dtype == CM_BF16 && (a.dim == 256 || a.dim == 512) && a.variant != 1 && cm_aligned(a.in, 16) && cm_aligned(a.out, 16) &&
+    if (a.io_dtype == CM_BF16 && (a.dim == 256 || a.dim == 512) && a.variant != 1 && cm_aligned(a.in, 16) && cm_aligned(a.out, 16) && hist16 &&
         (!a.weight_t || cm_aligned(a.weight_t, 8)) && (!a.bias || cm_aligned(a.bias, 8)) && cm_aligned(a.ln_g, 16) && cm_aligned(a.ln_b, 16)) {
         constexpr int TT = 32;
         const dim3 grid((a.seqlen + TT - 1) / TT, a.batch);
@@ -749,10 +815,10 @@ extern "C" int cm_glu_dwconv_ln_gelu(const cm_glu_dwconv_args *args) {
                 if (e != hipSuccess) { cm_set_error("glu_dwconv: LDS attribute failed: %s", hipGetErrorString(e)); return (int)e; }
             }
             hipLaunchKernelGGL(kern, grid, dim3(256), smem, st0, a);
-            return cm_launch_status("cm_glu_dwconv_ln_gelu(rows)");
+            return cm_launch_status(CAUSAL ? "cm_glu_dwconv_ln_gelu_causal(rows)" : "cm_glu_dwconv_ln_gelu(rows)");
         };
-        if (lin) return run(dwconv_rows_kernel<31, TT, 4, true>);
-        return a.dim == 256 ? run(dwconv_rows_kernel<31, TT, 4>) : run(dwconv_rows_kernel<31, TT, 8>);
+        if (lin) return run(dwconv_rows_kernel<31, TT, 4, true, P>);
+        return a.dim == 256 ? run(dwconv_rows_kernel<31, TT, 4, false, P>) : run(dwconv_rows_kernel<31, TT, 8, false, P>);
     }
     CM_REQUIRE(!a.lin_w, CM_EUNSUPPORTED, "glu_dwconv: the Linear epilogue is built for bf16 rows of dim 256 (16-byte aligned) only");
     // time tile: LDS holds (tt + K - 1 + tt) rows of dim floats; keep it under 64 KB so 2 workgroups share a CU
@@ -770,18 +836,32 @@ extern "C" int cm_glu_dwconv_ln_gelu(const cm_glu_dwconv_args *args) {
             if (e != hipSuccess) { cm_set_error("glu_dwconv: LDS attribute failed: %s", hipGetErrorString(e)); return (int)e; }
         }
         hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, a);
-        return cm_launch_status("cm_glu_dwconv_ln_gelu");
+        return cm_launch_status(CAUSAL ? "cm_glu_dwconv_ln_gelu_causal" : "cm_glu_dwconv_ln_gelu");
     };
     if (a.io_dtype == CM_BF16) {
-        if (tt == 16) return go(glu_dwconv_kernel<cm_bf16, 31, 16>);
-        if (tt == 8) return go(glu_dwconv_kernel<cm_bf16, 31, 8>);
-        return go(glu_dwconv_kernel<cm_bf16, 31, 4>);
+        if (tt == 16) return go(glu_dwconv_kernel<cm_bf16, 31, 16, P>);
+        if (tt == 8) return go(glu_dwconv_kernel<cm_bf16, 31, 8, P>);
+        return go(glu_dwconv_kernel<cm_bf16, 31, 4, P>);
     }
-    if (a.io_dtype == CM_F32) {
-        if (tt == 16) return go(glu_dwconv_kernel<float, 31, 16>);
-        if (tt == 8) return go(glu_dwconv_kernel<float, 31, 8>);
-        return go(glu_dwconv_kernel<float, 31, 4>);
-    }
-    cm_set_error("glu_dwconv: unsupported dtype %d", a.io_dtype);
-    return CM_EUNSUPPORTED;
+    if (tt == 16) return go(glu_dwconv_kernel<float, 31, 16, P>);
+    if (tt == 8) return go(glu_dwconv_kernel<float, 31, 8, P>);
+    return go(glu_dwconv_kernel<float, 31, 4, P>);
+}
+
+}  // namespace
+
+extern "C" int cm_glu_dwconv_ln_gelu(const cm_glu_dwconv_args *args) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "glu_dwconv: args is NULL");
+    return glu_dwconv_dispatch(*args);
+}
+
+extern "C" int cm_glu_dwconv_ln_gelu_causal(const cm_glu_dwconv_causal_args *args) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "glu_dwconv: args is NULL");
+    const cm_glu_dwconv_causal_args &u = *args;
+    dw_causal_args a{};
+    a.batch = u.batch, a.seqlen = u.seqlen, a.dim = u.dim, a.ksize = u.ksize, a.io_dtype = u.io_dtype, a.glu_done = u.glu_done;
+    a.in = u.in, a.weight = u.weight, a.bias = u.bias, a.ln_g = u.ln_g, a.ln_b = u.ln_b, a.eps = u.eps, a.variant = u.variant;
+    a.out = u.out, a.stream = u.stream, a.weight_t = u.weight_t, a.lin_w = u.lin_w, a.lin_b = u.lin_b;
+    a.hist = u.hist, a.hist_out = u.hist_out;
+    return glu_dwconv_dispatch(a);
 }

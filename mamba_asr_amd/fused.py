@@ -10,6 +10,9 @@ sequence:
   * both BiMamba directions share one conv launch (cm_conv_cl_fwd) and one scan launch (cm_scan_cl_fwd); the
     0.5*(fwd+bwd) average is folded into out_proj by K-concatenation: [y_f | y_b] @ (0.5*[W_out | W_out])^T;
   * GLU -> depthwise conv k=31 -> LayerNorm -> GELU of the convolution module is one kernel.
+The causal layer (UniMamba mixer, front-padded depthwise conv) takes the same sequence with one scan direction
+(cm_conv_xproj_uni, cm_glu_dwconv_ln_gelu_causal); those kernels and the scan carry state from one chunk of frames to the next,
+which is how forward_streaming (at the end of this file) streams a causal encoder.
 
 A layer's launches are written down once, in three pieces cut where the routes differ -- in front of the selective scan
 and behind it:
@@ -70,12 +73,17 @@ class _LayerCache:
             if ops.SMALL_FFN_ROWS > 0 and wide:
                 self.in_packed_s = self.in_packed if ops.FFN_LAYOUT == 32 else ops.PackedWeight(self.in_proj, 32)
         self.in_bias = None if m.in_proj.bias is None else c(m.in_proj.bias)
-        half = 0.5 if m.if_devide_out else 1.0
-        self.out_cat = c(torch.cat([m.out_proj.weight, m.out_proj.weight], dim=1) * half)      # (D, 2E)
+        self.uni = not hasattr(m, "conv1d_b")                     # UniMamba (the causal layer): one direction, nothing to average
+        sfxs = ("",) if self.uni else ("", "_b")
+        if self.uni:
+            self.out_cat = c(m.out_proj.weight)                                                    # (D, E)
+        else:
+            half = 0.5 if m.if_devide_out else 1.0
+            self.out_cat = c(torch.cat([m.out_proj.weight, m.out_proj.weight], dim=1) * half)      # (D, 2E)
         self.out_bias = None if m.out_proj.bias is None else c(m.out_proj.bias)
-        self.gamma = None if m.init_layer_scale is None else f(m.gamma)
+        self.gamma = None if getattr(m, "init_layer_scale", None) is None else f(m.gamma)
         self.dirs = []
-        for sfx in ("", "_b"):
+        for sfx in sfxs:
             conv, xp, dtp = getattr(m, "conv1d" + sfx), getattr(m, "x_proj" + sfx), getattr(m, "dt_proj" + sfx)
             A_log = getattr(m, "A_b_log" if sfx else "A_log")
             self.dirs.append(dict(conv_w=f(conv.weight).reshape(m.d_inner, -1), conv_b=f(conv.bias), x_proj=c(xp.weight),
@@ -83,7 +91,8 @@ class _LayerCache:
                                   D=f(getattr(m, "D_b" if sfx else "D"))))
         cm = layer.convolution_module
         # both directions' x_proj as ONE GEMM over [u_fwd | u_bwd]: block-diagonal (2*(R+2N), 2E) weight
-        self.x_proj_bd = torch.block_diag(m.x_proj.weight.detach().to(dtype), m.x_proj_b.weight.detach().to(dtype))
+        xps = [getattr(m, "x_proj" + sfx) for sfx in sfxs]
+        self.x_proj_bd = torch.block_diag(*[xp.weight.detach().to(dtype) for xp in xps])
         # row-major variant for cm_scan_cl_fwd's xdbl mode: output columns per direction are
         # [dt (zero padded to 16, or to 32 in bf16 when 16 < dt_rank <= 32) | B (16) | C (16)], so the scan reads the
         # GEMM's rows as written
@@ -92,13 +101,13 @@ class _LayerCache:
         if self.rows_mode:
             pad = ops.rows_dt_pad(R)
             self.row_width = pad + 32
-            rows = [ops.xproj_rows(xp.weight, R, pad, dtype) for xp in (m.x_proj, m.x_proj_b)]
+            rows = [ops.xproj_rows(xp.weight, R, pad, dtype) for xp in xps]
             self.x_proj_rows = torch.block_diag(*rows)            # (2 RW, 2 E)
             # per-direction (RW, E) images for cm_conv_xproj (conv + x_proj in one kernel, bf16)
             self.wx_packed = None
             if dtype == torch.bfloat16 and m.d_inner % 32 == 0 and m.d_inner <= 2048 and rows[0].is_cuda and m.d_conv == 4:
                 self.wx_packed = [ops.PackedWeight(r) for r in rows]
-            for d_, dtp in zip(self.dirs, (m.dt_proj, m.dt_proj_b)):
+            for d_, dtp in zip(self.dirs, [getattr(m, "dt_proj" + sfx) for sfx in sfxs]):
                 d_["dt_w16"] = ops.pad_dt_weight(dtp.weight.detach().to(dtype))      # dtype-rounded like the reference's GEMM operand
         self.cm_ln = (f(cm.layer_norm.weight), f(cm.layer_norm.bias), cm.layer_norm.eps)
         self.pw_w, self.pw_b = c(cm.bottleneck[0].weight.squeeze(-1)), c(cm.bottleneck[0].bias)
@@ -119,7 +128,7 @@ class _LayerCache:
         self.lin_packed = None                                    # the same Linear inside cm_glu_dwconv_ln_gelu (bf16, d_model 256)
         if USE_DWCONV_LIN and dtype == torch.bfloat16 and self.lin_w.is_cuda and tuple(self.lin_w.shape) == (256, 256) and self.lin_bf is not None:
             self.lin_packed = ops.PackedWeight(self.lin_w)
-        self.kernel_size = cm.kernel_size
+        self.kernel_size, self.causal = cm.kernel_size, bool(cm.causal)
 
     @property
     def ffn_native(self) -> bool:
@@ -147,11 +156,13 @@ def _cache(layer, dtype) -> _LayerCache:
 
 
 def supports(layer) -> bool:
-    """The fused path covers the non-causal bidirectional (BiMamba v2) layer the ASR recipes build."""
-    from .modules.mamba.bimamba import Mamba as BiMamba
+    """The fused path covers the two layers the ASR recipes build: non-causal with the bidirectional (BiMamba v2) mixer, and causal
+    (ConmambaEncoderLayer(causal=True)) with the unidirectional mixer and the front-padded convolution module."""
+    from .modules.mamba.bimamba import Mamba as BiMamba, UniMamba
     cm = layer.convolution_module
     act_ok = isinstance(cm.after_conv[1], torch.nn.GELU) and isinstance(layer.ffn_module1[1].ffn[1], torch.nn.GELU)
-    return (isinstance(layer.mamba, BiMamba) and not cm.causal and cm.kernel_size == 31 and cm.dilation == 1 and act_ok
+    mixer_ok = isinstance(layer.mamba, UniMamba) if cm.causal else isinstance(layer.mamba, BiMamba)
+    return (mixer_ok and cm.kernel_size == 31 and cm.dilation == 1 and act_ok
             and layer.mamba.d_state == 16 and layer.mamba.d_conv == 4)
 
 
@@ -188,20 +199,20 @@ USE_CONV_XPROJ = os.environ.get("CM_CONV_XPROJ", "1") == "1"
 
 def _scan_dirs(c: _LayerCache, ucat, ycat, batch, seqlen, xdbl=None):
     """x_proj for both directions (one library GEMM, time-contiguous output rows), fp32 feature buffer, and the two
-    direction descriptors of cm_scan_cl_fwd.  ``xdbl``: x_proj's rows when cm_conv_xproj has formed them already (only the
-    row-group kernel reads them)."""
-    E, R, N = c.d_inner, c.dt_rank, c.d_state
+    direction descriptors of cm_scan_cl_fwd (one of each for the unidirectional mixer: ucat / ycat are E wide then).
+    ``xdbl``: x_proj's rows when cm_conv_xproj has formed them already (only the row-group kernel reads them)."""
+    E, R, N, nd = c.d_inner, c.dt_rank, c.d_state, len(c.dirs)
     rows, P = batch * seqlen, c.dt_rank + 2 * c.d_state
     if c.rows_mode and (USE_SCAN_ROWS or xdbl is not None):
         if xdbl is None:
-            xdbl = (ucat.view(rows, 2 * E) @ c.x_proj_rows.t()).view(batch, seqlen, 2 * c.row_width)  # one library GEMM, rows as the scan reads them
+            xdbl = (ucat.view(rows, nd * E) @ c.x_proj_rows.t()).view(batch, seqlen, nd * c.row_width)  # one library GEMM, rows as the scan reads them
         RW = c.row_width
         return [dict(u=ucat[:, :, i * E:(i + 1) * E], A=d["A"], D=d["D"], delta_bias=d["dt_bias"], dt_weight=d["dt_w16"],
                      xdbl=xdbl[:, :, RW * i:RW * (i + 1)], out=ycat[:, :, i * E:(i + 1) * E], reverse=bool(i))
                 for i, d in enumerate(c.dirs)]
-    xdblT = c.x_proj_bd @ ucat.view(rows, 2 * E).t()                      # (2P, rows): [dt | B | C] fwd, then bwd
-    feat = ops.alloc_bc(2 * P, batch, seqlen, ucat.device)
-    feat.view(2 * P, rows).copy_(xdblT)                                   # one bf16 -> fp32 conversion
+    xdblT = c.x_proj_bd @ ucat.view(rows, nd * E).t()                     # (2P, rows): [dt | B | C] fwd, then bwd
+    feat = ops.alloc_bc(nd * P, batch, seqlen, ucat.device)
+    feat.view(nd * P, rows).copy_(xdblT)                                  # one bf16 -> fp32 conversion
     dirs = []
     for i, d in enumerate(c.dirs):
         f = feat[i * P:(i + 1) * P]
@@ -248,10 +259,20 @@ def _conv_forms_xdbl(c: _LayerCache) -> bool:
     return USE_CONV_XPROJ and USE_SCAN_ROWS and c.rows_mode and c.wx_packed is not None and c.dtype == torch.bfloat16
 
 
-def _conv(c: _LayerCache, xz, ucat, xdbl=None, xproj=True):
+def _conv(c: _LayerCache, xz, ucat, xdbl=None, xproj=True, hist=None):
     """Both directions' causal conv + SiLU of xz's x half (batch, seqlen, 2E views) into ucat = [u_fwd | u_bwd].  With
-    cm_conv_xproj the same kernel forms x_proj's rows (into ``xdbl`` when given) and they are returned, else None."""
+    cm_conv_xproj the same kernel forms x_proj's rows (into ``xdbl`` when given) and they are returned, else None.
+    The unidirectional mixer: one direction into ucat (E wide); ``hist`` = (x_hist, x_hist_out) of cm_conv_xproj_uni, the
+    native streaming route's carry."""
     E = c.d_inner
+    if c.uni:
+        w0 = (c.dirs[0]["conv_w"], c.dirs[0]["conv_b"])
+        if xproj and _conv_forms_xdbl(c):
+            x_hist, x_hist_out = hist or (None, None)
+            return ops.conv_xproj_uni(xz[:, :, :E], *w0, c.wx_packed[0], out=ucat, xdbl=xdbl, x_hist=x_hist, x_hist_out=x_hist_out)
+        assert hist is None
+        ops.conv_cl_fwd(xz[:, :, :E], *w0, silu=True, out_f=ucat)
+        return None
     w = (c.dirs[0]["conv_w"], c.dirs[0]["conv_b"], c.dirs[1]["conv_w"], c.dirs[1]["conv_b"])
     if xproj and _conv_forms_xdbl(c):
         return ops.conv_xproj(xz[:, :, :E], *w, c.wx_packed[0], c.wx_packed[1], out_f=ucat[:, :, :E], out_b=ucat[:, :, E:], xdbl=xdbl)
@@ -259,15 +280,25 @@ def _conv(c: _LayerCache, xz, ucat, xdbl=None, xproj=True):
     return None
 
 
-def _scan(c: _LayerCache, xz, ucat, ycat, xdbl, batch, seqlen):
-    """Both directions' selective scan of ucat, gated by xz's z half, into ycat (all (batch, seqlen, 2E)): one launch."""
-    ops.scan_cl_fwd(_scan_dirs(c, ucat, ycat, batch, seqlen, xdbl), z=xz[:, :, c.d_inner:], delta_softplus=True)
+def _scan(c: _LayerCache, xz, ucat, ycat, xdbl, batch, seqlen, state=None):
+    """Both directions' selective scan of ucat, gated by xz's z half, into ycat (all (batch, seqlen, 2E)): one launch.
+    ``state`` (batch, E, 16) fp32, streaming: the unidirectional scan starts from it and leaves its last state there (each workgroup
+    reads its channels' entry state before it writes them), unchunked -- the recurrence then visits the same values in the same
+    order as over the whole sequence."""
+    dirs = _scan_dirs(c, ucat, ycat, batch, seqlen, xdbl)
+    if state is None:
+        ops.scan_cl_fwd(dirs, z=xz[:, :, c.d_inner:], delta_softplus=True)
+        return
+    if len(dirs) != 1 or "xdbl" not in dirs[0]:
+        raise NotImplementedError("streaming needs the row-group scan (dt_rank <= 16, or <= 32 in bf16) of a unidirectional mixer")
+    ops.scan_cl_fwd([dict(dirs[0], h0=state, h_last=state)], z=xz[:, :, c.d_inner:], delta_softplus=True, time_chunks=1)
 
 
 def bimamba_fused(c: _LayerCache, h, batch, seqlen):
     """h: LN'd input (rows, D) in the compute dtype -> mixer output (rows, D) (reference bimamba.py:192-253)."""
     xz = _in_proj(c, h).view(batch, seqlen, -1)
-    ucat, ycat = torch.empty_like(xz), torch.empty_like(xz)
+    ucat = torch.empty((batch, seqlen, len(c.dirs) * c.d_inner), dtype=xz.dtype, device=xz.device)
+    ycat = torch.empty_like(ucat)
     _scan(c, xz, ucat, ycat, _conv(c, xz, ucat), batch, seqlen)
     return _out_proj(c, ycat.view(batch * seqlen, -1))
 
@@ -296,7 +327,7 @@ def _ffn_images(c: _LayerCache, small: bool):
             getattr(c, "in_packed_s", None))
 
 
-def _head(c: _LayerCache, x, xz, ucat, xdbl=None, small=False):
+def _head(c: _LayerCache, x, xz, ucat, xdbl=None, small=False, hist=None):
     """A layer in front of the scan, on the rows of whole utterances: x (rows, D) fp32 += 0.5 ffn1(x); norm1; in_proj -> xz;
     both causal convs -> ucat; x_proj -> xdbl.  xz / ucat (batch, seqlen, 2E) and xdbl (batch, seqlen, 2 RW) or None are
     these rows' slices of the forward's buffers.  Returns x_proj's rows when cm_conv_xproj formed them, else None."""
@@ -305,7 +336,7 @@ def _head(c: _LayerCache, x, xz, ucat, xdbl=None, small=False):
         _ffn_call(x, f1, norm2=c.norm1, proj_w=inp, proj_out=xz.view(x.shape[0], -1))
     else:
         _in_proj(c, _ffn_call(x, f1, norm2=c.norm1)[1], out=xz.view(x.shape[0], -1))
-    return _conv(c, xz, ucat, xdbl)
+    return _conv(c, xz, ucat, xdbl, hist=hist)
 
 
 def _ffn2(c: _LayerCache, x, addend, final_ln=None, f2=None):
@@ -315,19 +346,22 @@ def _ffn2(c: _LayerCache, x, addend, final_ln=None, f2=None):
                      h_dtype=torch.float32)[1]
 
 
-def _tail(c: _LayerCache, x, ycat, batch, seqlen, final_ln=None, small=False):
+def _tail(c: _LayerCache, x, ycat, batch, seqlen, final_ln=None, small=False, hist=None):
     """A layer behind the scan, on the rows of whole utterances: x (rows, D) fp32 += out_proj(ycat (rows, 2E)); the
-    convolution module; FFN2 + norm2 (-> _ffn2)."""
+    convolution module; FFN2 + norm2 (-> _ffn2).  ``hist`` = (hist, hist_out) of cm_glu_dwconv_ln_gelu_causal, the native
+    streaming route's carry."""
     D = x.shape[-1]
     dw = (c.dw_w, c.dw_b, c.cm_ln2[0], c.cm_ln2[1], c.cm_ln2[2])
+    kw = dict(causal=True, hist=hist[0], hist_out=hist[1]) if hist is not None else dict(causal=c.causal)
     if USE_LN_PW_GLU and c.pw_packed is not None:
         # x += mamba ; conv-module LN ; pointwise conv ; GLU -- one kernel, the 2D-wide tensor never exists
         gl = mixer_tail(c, x, ycat)
-        g = ops.glu_dwconv_ln_gelu(gl.view(batch, seqlen, D), *dw, weight_t=c.dw_wt, glu_done=True, lin_w=c.lin_packed, lin_b=c.lin_bf)
+        g = ops.glu_dwconv_ln_gelu(gl.view(batch, seqlen, D), *dw, weight_t=c.dw_wt, glu_done=True, lin_w=c.lin_packed, lin_b=c.lin_bf, **kw)
     else:
+        assert hist is None                                      # the carried rows are the gated ones
         _, h = ops.add_layernorm(x, _out_proj(c, ycat), 1.0, x_out=x, norm2=c.cm_ln, out_dtype=c.dtype)   # x += mamba ; conv-module LN
         pw = torch.addmm(c.pw_b, h, c.pw_w.t()).view(batch, seqlen, 2 * D)
-        g = ops.glu_dwconv_ln_gelu(pw, *dw, weight_t=c.dw_wt, lin_w=c.lin_packed, lin_b=c.lin_bf)
+        g = ops.glu_dwconv_ln_gelu(pw, *dw, weight_t=c.dw_wt, lin_w=c.lin_packed, lin_b=c.lin_bf, **kw)
     y = g.view(-1, D) if c.lin_packed is not None else torch.addmm(c.lin_b, g.view(-1, D), c.lin_w.t())
     return _ffn2(c, x, y, final_ln, _ffn_images(c, small)[1])
 
@@ -343,7 +377,7 @@ def layer_forward(layer, x, batch, seqlen, dtype, final_ln=None):
     y = bimamba_fused(c, h, batch, seqlen)
     _, h = ops.add_layernorm(x, y, 1.0, x_out=x, norm2=c.cm_ln, out_dtype=dtype)              # x += mamba ; conv-module LN
     pw = torch.addmm(c.pw_b, h, c.pw_w.t()).view(batch, seqlen, 2 * D)                       # pointwise conv D -> 2D
-    g = ops.glu_dwconv_ln_gelu(pw, c.dw_w, c.dw_b, c.cm_ln2[0], c.cm_ln2[1], c.cm_ln2[2], weight_t=c.dw_wt)
+    g = ops.glu_dwconv_ln_gelu(pw, c.dw_w, c.dw_b, c.cm_ln2[0], c.cm_ln2[1], c.cm_ln2[2], weight_t=c.dw_wt, causal=c.causal)
     y = torch.addmm(c.lin_b, g.view(-1, D), c.lin_w.t())
     _, h = ops.add_layernorm(x, y, 1.0, x_out=x, norm2=c.ffn2["ln"], out_dtype=dtype)         # x += conv ; LN of ffn_module2
     y = _ffn(x, h, c.ffn2, dtype)
@@ -362,7 +396,7 @@ def _native_gemms_ok(c: _LayerCache, D: int, dtype) -> bool:
     """cm_gemm_bf16 covers the layer when d_model == 256 (one workgroup owns whole residual rows) in bf16."""
     F_ = c.ffn1["w1"].shape[0]
     return (USE_NATIVE_GEMM and dtype == torch.bfloat16 and D == 256 and F_ % 256 == 0 and F_ % 64 == 0 and (2 * c.d_inner) % 256 == 0
-            and c.gamma is None)
+            and c.gamma is None and not c.uni)
 
 
 def layer_forward_native(layer, x, h, batch, seqlen, next_ln):
@@ -439,7 +473,7 @@ def _encoder_forward_joined(encoder, src, dtype, ns, paired=False):
     caches = [_cache(layer, dtype) for layer in encoder.layers]
     if not (USE_FUSED_FFN and caches and all(c.ffn_native for c in caches)):
         return None
-    if ns > 1 and not (USE_CONV_XPROJ and USE_SCAN_ROWS and USE_LN_PW_GLU and all(c.all_native for c in caches)):
+    if ns > 1 and not (USE_CONV_XPROJ and USE_SCAN_ROWS and USE_LN_PW_GLU and all(c.all_native and not c.uni for c in caches)):
         return None
     dev = src.device
     cur = torch.cuda.current_stream(dev)
@@ -451,9 +485,11 @@ def _encoder_forward_joined(encoder, src, dtype, ns, paired=False):
     fin = _final_norm(encoder)
     with torch.autocast("cuda", enabled=False):
         x = _residual_rows(src)
+        nd = len(caches[0].dirs)
         xz = torch.empty((batch, seqlen, 2 * caches[0].d_inner), dtype=dtype, device=dev)
-        ucat, ycat = torch.empty_like(xz), torch.empty_like(xz)
-        xdbl = torch.empty((batch, seqlen, 2 * caches[0].row_width), dtype=dtype, device=dev) if _conv_forms_xdbl(caches[0]) else None
+        ucat = torch.empty((batch, seqlen, nd * caches[0].d_inner), dtype=dtype, device=dev)
+        ycat = torch.empty_like(ucat)
+        xdbl = torch.empty((batch, seqlen, nd * caches[0].row_width), dtype=dtype, device=dev) if _conv_forms_xdbl(caches[0]) else None
         x3 = x.view(batch, seqlen, D)
         rows = lambda t, b0, b1: t[b0:b1].view((b1 - b0) * seqlen, -1)      # a part's utterances of a (batch, seqlen, .) buffer as rows
         outs = [None] * len(parts)
@@ -502,6 +538,8 @@ def encoder_forward(encoder, src, dtype: Optional[torch.dtype] = None, streams: 
     # parts of at least 16 utterances (measured, join mode: 16 utterances 12.1 M frames/s as one part vs 10.6 M as four;
     # 32: 15.1 / 15.3 / 15.2 M with 1 / 2 / 4; 64: 16.6 / 17.0 / 17.7 M); an explicit ``streams`` argument is taken as is
     ns = min(N_STREAMS, max(1, src.shape[0] // 16)) if streams is None else streams
+    if any(layer.convolution_module.causal for layer in encoder.layers):
+        ns = 1                                                   # the multi-stream modes are built around the two-direction scan
     if ns > 1 and src.shape[0] >= 2 * 8:                       # split only batches large enough to keep each half busy
         if STREAM_MODE in ("join", "pair"):
             out = _encoder_forward_joined(encoder, src, dtype, ns, paired=STREAM_MODE == "pair")
@@ -539,6 +577,84 @@ def encoder_forward(encoder, src, dtype: Optional[torch.dtype] = None, streams: 
             for i, layer in enumerate(encoder.layers):
                 out = layer_forward(layer, x, batch, seqlen, dtype, final_ln=fin if i == n - 1 else None)
         return out.view(batch, seqlen, D)
+
+
+# ------------------------------------------------------------------------------------------------
+# streaming: the causal encoder one chunk of frames at a time (ConmambaEncoder.forward_streaming)
+# ------------------------------------------------------------------------------------------------
+# Per layer and stream the context carries what the three time-mixing steps have seen: the scan's state (E, 16) fp32, the last
+# 3 inputs of the mixer's width-4 conv, the last 30 gated rows in front of the k = 31 depthwise conv.  Everything else is row-local.
+# Native route (bf16, d_model 256, every layer all_native): a layer is the six launches of the whole-utterance route --
+#   cm_ffn_fused (FFN1 + norm1 + in_proj), cm_conv_xproj_uni (reads / writes the conv rows), cm_scan_cl_fwd (h0 = h_last = the state),
+#   cm_ln_pw_glu_mix, cm_glu_dwconv_ln_gelu_causal (+ Linear; reads / writes the gated rows), cm_ffn_fused (FFN2 + norm2 [+ final norm])
+# -- no library GEMM, no copy of history rows.  The two row histories are double-buffered (a launch may not write the rows its
+# other workgroups still read) and swapped after each layer.  CM_STREAM_NATIVE=0 = the generic route for A/B runs.
+# Generic route (fp32, other widths): layer_forward's sequence, the history rows prepended in torch and their outputs dropped.
+USE_STREAM_NATIVE = os.environ.get("CM_STREAM_NATIVE", "1") == "1"
+
+
+def _stream_layer_generic(c: _LayerCache, st, x, batch, t, dtype, final_ln=None):
+    """layer_forward for one chunk: the convs run on [history | chunk] rows, the scan from the carried state."""
+    D, E = x.shape[-1], c.d_inner
+    _, h = ops.add_layernorm(x, None, norm2=c.ffn1["ln"], out_dtype=dtype)
+    y = _ffn(x, h, c.ffn1, dtype)
+    _, h = ops.add_layernorm(x, y, 0.5, x_out=x, norm2=c.norm1, out_dtype=dtype)
+    xz = _in_proj(c, h).view(batch, t, 2 * E)
+    xe = torch.cat([st.conv_state, xz[:, :, :E]], dim=1)                                    # (batch, 3 + t, E)
+    st.conv_state.copy_(xe[:, t:])
+    ue = torch.empty_like(xe)
+    ops.conv_cl_fwd(xe, c.dirs[0]["conv_w"], c.dirs[0]["conv_b"], silu=True, out_f=ue)
+    u = ue[:, 3:].contiguous()
+    ycat = torch.empty_like(u)
+    _scan(c, xz, u, ycat, None, batch, t, state=st.ssm_state)
+    _, h = ops.add_layernorm(x, _out_proj(c, ycat.view(batch * t, E)), 1.0, x_out=x, norm2=c.cm_ln, out_dtype=dtype)
+    gl = F.glu(torch.addmm(c.pw_b, h, c.pw_w.t()), dim=-1).view(batch, t, D)
+    ge = torch.cat([st.dw_state, gl], dim=1)                                                # (batch, 30 + t, D)
+    st.dw_state.copy_(ge[:, t:])
+    g = ops.glu_dwconv_ln_gelu(ge, c.dw_w, c.dw_b, c.cm_ln2[0], c.cm_ln2[1], c.cm_ln2[2], weight_t=c.dw_wt, glu_done=True,
+                               causal=True)[:, c.kernel_size - 1:]
+    y = torch.addmm(c.lin_b, g.reshape(-1, D), c.lin_w.t())
+    _, h = ops.add_layernorm(x, y, 1.0, x_out=x, norm2=c.ffn2["ln"], out_dtype=dtype)
+    y = _ffn(x, h, c.ffn2, dtype)
+    ops.add_layernorm(x, y, 0.5, x_out=x, norm1=c.norm2, want_out=False)
+    if final_ln is None:
+        return x
+    return ops.add_layernorm(x, None, norm2=final_ln, out_dtype=torch.float32)[1]
+
+
+@torch.no_grad()
+def forward_streaming(encoder, src, context):
+    """ConmambaEncoder.forward_streaming: src (B, t, D), any t >= 1, continues the B streams whose state ``context`` holds ->
+    (B, t, D) fp32; the context is updated in place.  The outputs over the chunks of an utterance, concatenated, are the causal
+    whole-utterance forward.  The compute dtype is the context's.  No host synchronisation and no data-dependent allocation: a
+    fixed (B, t) step can be captured in a hipGraph."""
+    batch, t, D = src.shape
+    dtype = context.layers[0].conv_state.dtype
+    caches = [_cache(layer, dtype) for layer in encoder.layers]
+    if not all(c.uni and c.causal and c.rows_mode and c.kernel_size == 31 for c in caches):
+        raise NotImplementedError("forward_streaming: a layer is outside the streamed routes (causal layer, dt_rank <= 16, or <= 32 in bf16)")
+    native = (USE_STREAM_NATIVE and USE_FUSED_FFN and USE_LN_PW_GLU and dtype == torch.bfloat16 and D == 256
+              and all(c.all_native and _conv_forms_xdbl(c) for c in caches))
+    fin = _final_norm(encoder)
+    n = len(caches)
+    with torch.autocast("cuda", enabled=False):
+        out = x = _residual_rows(src)
+        if not native:
+            for i, (c, st) in enumerate(zip(caches, context.layers)):
+                out = _stream_layer_generic(c, st, x, batch, t, dtype, fin if i == n - 1 else None)
+            return out.view(batch, t, D)
+        E, dev = caches[0].d_inner, src.device
+        xz = torch.empty((batch, t, 2 * E), dtype=dtype, device=dev)
+        ucat = torch.empty((batch, t, E), dtype=dtype, device=dev)
+        ycat = torch.empty_like(ucat)
+        xdbl = torch.empty((batch, t, caches[0].row_width), dtype=dtype, device=dev)
+        small = 0 < batch * t <= ops.SMALL_FFN_ROWS
+        for i, (c, st) in enumerate(zip(caches, context.layers)):
+            _head(c, x, xz, ucat, xdbl, small, hist=(st.conv_state, st.conv_spare))
+            _scan(c, xz, ucat, ycat, xdbl, batch, t, state=st.ssm_state)
+            out = _tail(c, x, ycat.view(batch * t, E), batch, t, fin if i == n - 1 else None, small, hist=(st.dw_state, st.dw_spare))
+            st.swap()
+        return out.view(batch, t, D)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -134,6 +134,46 @@ class ConmambaEncoderLayer(nn.Module):
         return self.norm2(self._ffn(self.ffn_module2, x))
 
 
+class ConmambaEncoderLayerStreamingContext:
+    """What one causal ConmambaEncoderLayer carries from one chunk of frames to the next, per stream (batch slot):
+    ssm_state (B, E, 16) fp32, the selective scan's state; conv_state (B, 3, E), the mixer conv's last three input rows;
+    dw_state (B, 30, D), the last 30 GLU output rows in front of the k = 31 depthwise conv -- the two row histories in the
+    compute dtype.  Constant size.  conv_spare / dw_spare are the second buffers the native kernels write the new history
+    into (a launch may not overwrite rows its other workgroups still read); ``swap`` makes them current."""
+
+    def __init__(self, ssm_state, conv_state, dw_state):
+        self.ssm_state, self.conv_state, self.dw_state = ssm_state, conv_state, dw_state
+        self.conv_spare, self.dw_spare = torch.zeros_like(conv_state), torch.zeros_like(dw_state)
+
+    def swap(self):
+        self.conv_state, self.conv_spare = self.conv_spare, self.conv_state
+        self.dw_state, self.dw_spare = self.dw_spare, self.dw_state
+
+    def reset(self, rows=None):
+        for t in (self.ssm_state, self.conv_state, self.dw_state):
+            if rows is None:
+                t.zero_()
+            else:
+                t.index_fill_(0, torch.as_tensor(rows, dtype=torch.long, device=t.device), 0)
+
+
+class ConmambaEncoderStreamingContext:
+    """Streaming state of a ConmambaEncoder: one ConmambaEncoderLayerStreamingContext per layer (the reference's
+    ConformerEncoderStreamingContext shape: a ``layers`` list)."""
+
+    def __init__(self, layers):
+        self.layers = list(layers)
+
+    @property
+    def batch_size(self):
+        return self.layers[0].ssm_state.shape[0]
+
+    def reset(self, rows=None):
+        """Zero the state of every batch slot, or of the slots ``rows`` (indices): the start of a new utterance there."""
+        for layer in self.layers:
+            layer.reset(rows)
+
+
 class ConmambaEncoder(nn.Module):
     def __init__(self, num_layers, d_model, d_ffn, kernel_size=31, activation=Swish, bias=True, dropout=0.0,
                  causal=False, mamba_config=None):
@@ -154,6 +194,41 @@ class ConmambaEncoder(nn.Module):
             out = layer(out, src_mask=src_mask, src_key_padding_mask=src_key_padding_mask, pos_embs=pos_embs,
                         dynchunktrain_config=dynchunktrain_config)
         return self.norm(out), None
+
+    def _require_causal(self, what):
+        if not all(layer.convolution_module.causal and isinstance(layer.mamba, Mamba) for layer in self.layers):
+            raise ValueError(f"{what}: a bidirectional encoder cannot be streamed (build it with causal=True)")
+
+    def make_streaming_context(self, dynchunktrain_config=None, *, batch_size, device=None, dtype=None):
+        """A zero ConmambaEncoderStreamingContext for ``batch_size`` streams.  ``dynchunktrain_config`` is accepted and ignored
+        (the reference's TransformerASR.make_streaming_context hands it over; a state-space encoder has no chunk size).  ``dtype``:
+        the compute dtype of the streamed forward (default: the autocast dtype when enabled, else the parameters')."""
+        self._require_causal("make_streaming_context")
+        p = self.norm.norm.weight
+        device = p.device if device is None else device
+        if dtype is None:
+            dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else p.dtype
+        z = lambda *shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        return ConmambaEncoderStreamingContext(
+            [ConmambaEncoderLayerStreamingContext(z(batch_size, l.mamba.d_inner, l.mamba.d_state, dt=torch.float32),
+                                                  z(batch_size, l.mamba.d_conv - 1, l.mamba.d_inner, dt=dtype),
+                                                  z(batch_size, l.convolution_module.kernel_size - 1, l.mamba.d_model, dt=dtype))
+             for l in self.layers])
+
+    def forward_streaming(self, src, context, pos_embs=None):
+        """src (B, t, D), the next t >= 1 frames of B streams -> (out (B, t, D) fp32, None); ``context`` (make_streaming_context)
+        is updated in place.  Concatenating the outputs over an utterance's chunks gives ``forward`` on the whole utterance.
+        Eval mode, no grad, GPU (fused.forward_streaming).  ``pos_embs`` is ignored, as in ``forward``."""
+        self._require_causal("forward_streaming")
+        if len(context.layers) != len(self.layers) or context.batch_size != src.shape[0]:
+            raise ValueError(f"forward_streaming: the context holds {context.batch_size} streams of {len(context.layers)} layers, "
+                             f"src has {src.shape[0]} of {len(self.layers)}")
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("forward_streaming is the inference path: call eval() and run it under torch.no_grad()")
+        from .. import fused
+        if not all(fused.supports(layer) for layer in self.layers):
+            raise NotImplementedError("forward_streaming: a layer is outside the fused path (fused.supports)")
+        return fused.forward_streaming(self, src, context), None
 
 
 class MambaDecoderLayer(nn.Module):

@@ -70,6 +70,13 @@ def lookahead_mask(padded_input):
     return torch.ones(L, L, dtype=torch.bool, device=padded_input.device).triu(1)
 
 
+class TransformerASRStreamingContext:
+    """Streaming state of a TransformerASR (reference :151-336): the configuration it was made with and the encoder's context."""
+
+    def __init__(self, dynchunktrain_config, encoder_context):
+        self.dynchunktrain_config, self.encoder_context = dynchunktrain_config, encoder_context
+
+
 class TransformerASR(nn.Module):
     def __init__(self, tgt_vocab, input_size, d_model=512, nhead=8, num_encoder_layers=6, num_decoder_layers=6,
                  d_ffn=2048, dropout=0.1, activation=nn.ReLU, positional_encoding="fixed_abs_sine",
@@ -131,6 +138,18 @@ class TransformerASR(nn.Module):
         out, _ = self.encoder(src=self._prep_src(src), src_mask=None, src_key_padding_mask=None, pos_embs=None,
                               dynchunktrain_config=dynchunktrain_config)
         return out
+
+    def encode_streaming(self, src, context: TransformerASRStreamingContext):
+        """The next chunk of frames (B, t, F[, C]) of the streams in ``context`` -> encoder_out (B, t, D) (reference :931-1022);
+        ``context`` is updated in place.  Causal ConMamba encoders only (ConmambaEncoder.forward_streaming)."""
+        out, _ = self.encoder.forward_streaming(src=self._prep_src(src), pos_embs=None, context=context.encoder_context)
+        return out
+
+    def make_streaming_context(self, dynchunktrain_config=None, encoder_kwargs={}):
+        """A blank streaming context (reference :1024-1049).  ``encoder_kwargs`` go to the encoder's make_streaming_context:
+        batch_size (required), device, dtype."""
+        return TransformerASRStreamingContext(dynchunktrain_config=dynchunktrain_config,
+                                              encoder_context=self.encoder.make_streaming_context(dynchunktrain_config, **encoder_kwargs))
 
     def forward(self, src, tgt, wav_len=None, pad_idx=0):
         encoder_out = self.encode(src, wav_len, pad_idx)
@@ -195,3 +214,9 @@ class EncoderWrapper(nn.Module):
 
     def forward(self, x, wav_lens=None, pad_idx=0, **kwargs):
         return self.transformer.encode(x, wav_lens, pad_idx, **kwargs)
+
+    def forward_streaming(self, x, context):
+        return self.transformer.encode_streaming(x, context)
+
+    def make_streaming_context(self, *args, **kwargs):
+        return self.transformer.make_streaming_context(*args, **kwargs)

@@ -1159,6 +1159,44 @@ def conv_xproj(x, weight_f, bias_f, weight_b, bias_b, wx_f, wx_b, out_f, out_b, 
     return xdbl
 
 
+def _hist_rows(t, shape, dtype, what):
+    if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()):
+        raise RuntimeError(f"{what} must be a contiguous {dtype} tensor of shape {shape}")
+    return t
+
+
+def conv_xproj_uni(x, weight, bias, wx, out, xdbl=None, x_hist=None, x_hist_out=None, variant: int = 0):
+    """One causal direction's depthwise conv + SiLU and x_proj GEMM in one kernel (cm_conv_xproj_uni, bf16), whole sequences
+    or a stream of chunks.  x (batch, seqlen, dim) view; weight (dim, 4) fp32; wx PackedWeight of the (P + 32, dim) re-rowed
+    x_proj weight; out (batch, seqlen, dim) view.  x_hist (batch, 3, dim) bf16: the rows in front of x, None = zeros;
+    x_hist_out (batch, 3, dim): receives the last three rows of [x_hist | x], and must be another buffer than x_hist.
+    Returns xdbl (batch, seqlen, P + 32) bf16."""
+    _dev_check(x, weight, bias, out, x_hist, x_hist_out)
+    _rows_ok(x, "x"), _rows_ok(out, "out")
+    b, l, d = x.shape
+    if x.dtype != torch.bfloat16 or out.dtype != torch.bfloat16:
+        raise RuntimeError("conv_xproj_uni: bf16 only")
+    rw = wx.shape[0]
+    if rw not in (48, 64) or wx.shape != (rw, d):
+        raise RuntimeError("conv_xproj_uni: wx must be PackedWeight of shape (48 | 64, dim)")
+    w, bs = _f32c(weight), _f32c(bias)
+    if xdbl is None:
+        xdbl = torch.empty((b, l, rw), dtype=torch.bfloat16, device=x.device)
+    elif xdbl.shape != (b, l, rw) or xdbl.dtype != torch.bfloat16:
+        raise RuntimeError(f"conv_xproj_uni: xdbl must be bf16 (batch, seqlen, {rw})")
+    _hist_rows(x_hist, (b, 3, d), torch.bfloat16, "conv_xproj_uni: x_hist")
+    _hist_rows(x_hist_out, (b, 3, d), torch.bfloat16, "conv_xproj_uni: x_hist_out")
+    a = N.ConvXprojUniArgs()
+    a.batch, a.seqlen, a.dim, a.width = b, l, d, w.shape[1]
+    a.x, a.weight, a.bias, a.wx, a.y, a.xdbl = _ptr(x), _ptr(w), _ptr(bs), _ptr(wx.data), _ptr(out), _ptr(xdbl)
+    a.x_hist, a.x_hist_out = _ptr(x_hist), _ptr(x_hist_out)
+    a.x_bs, a.x_ts, a.y_bs, a.y_ts = x.stride(0), x.stride(1), out.stride(0), out.stride(1)
+    a.xdbl_bs, a.xdbl_ts = xdbl.stride(0), xdbl.stride(1)
+    a.stream, a.dt_pad, a.variant = _stream(), rw - 32, int(variant)     # variant 1: always the 16-step tiles
+    _launch("cm_conv_xproj_uni", N.lib().cm_conv_xproj_uni, a, units=b * l)
+    return xdbl
+
+
 def conv_cl_fwd(x, weight_f, bias_f, weight_b=None, bias_b=None, silu=True, out_f=None, out_b=None):
     """Channels-last depthwise conv (+SiLU) for one or both BiMamba directions in one pass (cm_conv_cl_fwd).
     x (batch, seqlen, dim) view; weights (dim, 4); returns (y_fwd, y_bwd or None)."""
@@ -1577,11 +1615,16 @@ def ln_pw_glu(x, y, alpha, norm, w, bias, x_out=None, ycat=None, out_w=None):
 
 
 def glu_dwconv_ln_gelu(inp, weight, bias, ln_weight, ln_bias, eps=1e-5, weight_t=None, glu_done=False, lin_w=None, lin_b=None,
-                       variant: int = 0):
+                       variant: int = 0, causal: bool = False, hist=None, hist_out=None):
     """(batch, seqlen, 2*dim) -> (batch, seqlen, dim): GLU, depthwise conv (k=31, same padding), LayerNorm, GELU
     (cm_glu_dwconv_ln_gelu).  weight (dim, 1, k) or (dim, k); weight_t: optional precomputed fp32 (k, dim) copy of the
-    taps (made here per call otherwise) so that the kernel's per-channel tap reads are coalesced."""
-    _dev_check(inp, weight, bias, ln_weight, ln_bias)
+    taps (made here per call otherwise) so that the kernel's per-channel tap reads are coalesced.
+    ``causal`` (cm_glu_dwconv_ln_gelu_causal): all k - 1 padding rows in front; hist (batch, k - 1, dim) in inp's dtype are
+    the gated rows in front of inp (None = zeros), hist_out (another buffer than hist) receives the last k - 1 gated rows of
+    [hist | inp]."""
+    _dev_check(inp, weight, bias, ln_weight, ln_bias, hist, hist_out)
+    if (hist is not None or hist_out is not None) and not causal:
+        raise RuntimeError("glu_dwconv_ln_gelu: hist / hist_out belong to the causal form")
     if not inp.is_contiguous():
         inp = inp.contiguous()
     b, l, d2 = inp.shape
@@ -1589,7 +1632,10 @@ def glu_dwconv_ln_gelu(inp, weight, bias, ln_weight, ln_bias, eps=1e-5, weight_t
     w = _f32c(weight).reshape(d, -1)
     bs, g, bt = _f32c(bias), _f32c(ln_weight), _f32c(ln_bias)
     out = torch.empty((b, l, d), dtype=inp.dtype, device=inp.device)
-    a = N.GluDwconvArgs()
+    a = N.GluDwconvCausalArgs() if causal else N.GluDwconvArgs()
+    if causal:
+        hs = (b, w.shape[1] - 1, d)
+        a.hist, a.hist_out = _ptr(_hist_rows(hist, hs, inp.dtype, "glu_dwconv_ln_gelu: hist")), _ptr(_hist_rows(hist_out, hs, inp.dtype, "glu_dwconv_ln_gelu: hist_out"))
     a.batch, a.seqlen, a.dim, a.ksize, a.io_dtype, a.glu_done = b, l, d, w.shape[1], _DT[inp.dtype], int(bool(glu_done))
     a.in_, a.weight, a.bias, a.ln_g, a.ln_b, a.eps, a.out = _ptr(inp), _ptr(w), _ptr(bs), _ptr(g), _ptr(bt), float(eps), _ptr(out)
     wt = w.t().contiguous() if weight_t is None else weight_t
@@ -1602,7 +1648,10 @@ def glu_dwconv_ln_gelu(inp, weight, bias, ln_weight, ln_bias, eps=1e-5, weight_t
         lb = _f32c(lin_b)
         a.lin_w, a.lin_b = _ptr(lin_w.data), _ptr(lb)
     a.stream, a.variant = _stream(), int(variant)        # variant 1: always the generic 16-step kernel
-    _launch("cm_glu_dwconv_ln_gelu", N.lib().cm_glu_dwconv_ln_gelu, a, units=b * l)
+    if causal:
+        _launch("cm_glu_dwconv_ln_gelu_causal", N.lib().cm_glu_dwconv_ln_gelu_causal, a, units=b * l)
+    else:
+        _launch("cm_glu_dwconv_ln_gelu", N.lib().cm_glu_dwconv_ln_gelu, a, units=b * l)
     return out
 
 

@@ -254,8 +254,8 @@ def encoder_forward_seq_parallel_fused(encoder, src_shard, group):
     batch, T, D = src_shard.shape
     caches = [fused._cache(layer, dtype) for layer in encoder.layers]
     for layer, c in zip(encoder.layers, caches):
-        if not (fused.supports(layer) and c.all_native and c.row_width == 48):
-            raise NotImplementedError("layer outside the fused bf16 route (d_model 256, dt_rank <= 16): use encoder_forward_seq_parallel")
+        if not (fused.supports(layer) and c.all_native and c.row_width == 48 and not c.uni):
+            raise NotImplementedError("layer outside the fused bf16 route (bidirectional, d_model 256, dt_rank <= 16): use encoder_forward_seq_parallel")
     dev = src_shard.device
     fin = fused._final_norm(encoder)
     E = caches[0].d_inner
