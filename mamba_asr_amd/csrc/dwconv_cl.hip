@@ -284,6 +284,13 @@ inline bool tiled_ok(const cm_dwconv_cl_args &a) {
     return a.dim % vec == 0 && al(a.x, a.x_bs, a.x_ts) && al(a.y, a.y_bs, a.y_ts) && al(a.dy, a.dy_bs, a.dy_ts) && al(a.dx, a.dx_bs, a.dx_ts);
 }
 
+// dynamic LDS of a tiled kernel: its tile(s), or the CB x KMAX floats load_taps stages in the same region first -- at k = 32 and 256
+// live channels 32768 bytes, more than the forward's one bf16 tile (ROWS2 x CB x 2 = 32256)
+inline size_t tiled_lds_bytes(int ntiles, int io_dtype) {
+    const size_t tiles = (size_t)ntiles * ROWS2 * CB * (io_dtype == CM_BF16 ? 2 : 4), taps = (size_t)CB * KMAX * sizeof(float);
+    return tiles > taps ? tiles : taps;
+}
+
 template <typename K> int set_lds(K kern, size_t smem, const char *what) {
     if (smem > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
@@ -342,7 +349,7 @@ extern "C" int cm_dwconv_cl_fwd(const cm_dwconv_cl_args *args) {
     if (tiled_ok(a)) {
         const int ntile = (a.seqlen + TT2 - 1) / TT2;
         const dim3 tg((unsigned)(a.batch * ntile), (unsigned)((a.dim + CB - 1) / CB));
-        const size_t smem = (size_t)ROWS2 * CB * (a.io_dtype == CM_BF16 ? 2 : 4);
+        const size_t smem = tiled_lds_bytes(1, a.io_dtype);
         if (a.io_dtype == CM_BF16) {
             if (int rc = set_lds(dwconv_cl_fwd_tiled_kernel<cm_bf16>, smem, "dwconv_cl_fwd")) return rc;
             hipLaunchKernelGGL(dwconv_cl_fwd_tiled_kernel<cm_bf16>, tg, dim3(256), smem, st, a, ntile);
@@ -370,7 +377,7 @@ extern "C" int cm_dwconv_cl_bwd(const cm_dwconv_cl_args *args) {
     dim3 grid((unsigned)nwg), block(a.dim >= 256 ? 256 : ((a.dim + 63) / 64) * 64);
     if (tiled_ok(a)) {
         const dim3 tg((unsigned)nwg, (unsigned)((a.dim + CB - 1) / CB));
-        const size_t smem = (size_t)2 * ROWS2 * CB * (a.io_dtype == CM_BF16 ? 2 : 4);
+        const size_t smem = tiled_lds_bytes(2, a.io_dtype);
         if (a.io_dtype == CM_BF16) {
             if (int rc = set_lds(dwconv_cl_bwd_tiled_kernel<cm_bf16>, smem, "dwconv_cl_bwd")) return rc;
             hipLaunchKernelGGL(dwconv_cl_bwd_tiled_kernel<cm_bf16>, tg, dim3(256), smem, st, a, nrun);

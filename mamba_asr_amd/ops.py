@@ -1159,6 +1159,15 @@ def conv_xproj(x, weight_f, bias_f, weight_b, bias_b, wx_f, wx_b, out_f, out_b, 
     return xdbl
 
 
+def _out_rows(t, shape, dtype, device, what):
+    """A caller-supplied contiguous output of the given shape and dtype (the guard-band tests place it), or a fresh one."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or t.device != device:
+        raise RuntimeError(f"{what} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}")
+    return t
+
+
 def _hist_rows(t, shape, dtype, what):
     if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()):
         raise RuntimeError(f"{what} must be a contiguous {dtype} tensor of shape {shape}")
@@ -1221,9 +1230,10 @@ def conv_cl_fwd(x, weight_f, bias_f, weight_b=None, bias_b=None, silu=True, out_
 
 
 def add_layernorm(x, y=None, alpha=1.0, norm1=None, norm2=None, x_out=None, out_dtype=None, want_out=True,
-                  out_act=0):
+                  out_act=0, out=None):
     """r = x + alpha*y; r1 = LN1(r) if norm1 else r; x_out <- r1 (fp32, may alias x); out = LN2(r1) if norm2 else r1.
-    x (rows.., dim) fp32 contiguous; norm = (weight, bias, eps).  Returns (x_out or None, out or None)."""
+    x (rows.., dim) fp32 contiguous; norm = (weight, bias, eps); ``out``: optional contiguous tensor of x's shape in out_dtype
+    to receive the result.  Returns (x_out or None, out or None)."""
     _dev_check(x, y)
     ref = x if x is not None else y
     if x is not None and (x.dtype != torch.float32 or not x.is_contiguous()):
@@ -1252,9 +1262,10 @@ def add_layernorm(x, y=None, alpha=1.0, norm1=None, norm2=None, x_out=None, out_
         g, bt = _f32c(norm2[0]), _f32c(norm2[1])
         keep += [g, bt]
         a.g2, a.b2, a.eps2 = _ptr(g), _ptr(bt), float(norm2[2])
-    out = None
+    if out is not None and not want_out:
+        raise RuntimeError("add_layernorm: out given with want_out=False")
     if want_out:
-        out = torch.empty(ref.shape, dtype=od, device=ref.device)
+        out = _out_rows(out, ref.shape, od, ref.device, "add_layernorm: out")
         a.out, a.out_dtype = _ptr(out), _DT[od]
     a.x = _ptr(x)
     a.x_out = _ptr(x_out)
@@ -1574,11 +1585,11 @@ class LnActDropFn(torch.autograd.Function):
         return (dx.view(shape) if dx is not None else None), dg.to(weight.dtype), db.to(weight.dtype), None, None, None, None
 
 
-def ln_pw_glu(x, y, alpha, norm, w, bias, x_out=None, ycat=None, out_w=None):
+def ln_pw_glu(x, y, alpha, norm, w, bias, x_out=None, ycat=None, out_w=None, out=None):
     """Mixer -> convolution-module seam (cm_ln_pw_glu): x_out = x + alpha*y; g = GLU(LayerNorm(x_out) @ W^T + bias).
     x (rows, D) fp32 contiguous, D = 256 or 144; y (rows, D) bf16 or None; norm = (weight, bias, eps); w: PackedWeight of the
     (2D, D) pointwise-conv weight (at D = 144 padded to 160 columns: PackedWeight(w, pad=(288, 160))); bias (2D) fp32.  x_out defaults
-    to x (in place).  Returns g (rows, D) bf16.
+    to x (in place).  Returns g (rows, D) bf16 (``out`` if given: a contiguous bf16 (rows, D) tensor).
     With ``ycat`` (rows, K) bf16 contiguous and ``out_w`` (PackedWeight of a (256, K) matrix, K a multiple of 128) instead of
     ``y``, y = ycat @ out_w^T is formed inside the kernel (cm_ln_pw_glu_mix, D = 256 only) and never written."""
     _dev_check(x, y, bias, ycat)
@@ -1593,7 +1604,7 @@ def ln_pw_glu(x, y, alpha, norm, w, bias, x_out=None, ycat=None, out_w=None):
         raise RuntimeError("ln_pw_glu: the projection in front (ycat, out_w) needs d_model 256")
     g_, b_, bs = _f32c(norm[0]), _f32c(norm[1]), _f32c(bias)
     xo = x if x_out is None else x_out
-    out = torch.empty((rows, d), dtype=torch.bfloat16, device=x.device)
+    out = _out_rows(out, (rows, d), torch.bfloat16, x.device, "ln_pw_glu: out")
     if (ycat is None) != (out_w is None) or (ycat is not None and y is not None):
         raise RuntimeError("ln_pw_glu: give either y, or ycat together with out_w")
     if ycat is not None:
@@ -1615,13 +1626,13 @@ def ln_pw_glu(x, y, alpha, norm, w, bias, x_out=None, ycat=None, out_w=None):
 
 
 def glu_dwconv_ln_gelu(inp, weight, bias, ln_weight, ln_bias, eps=1e-5, weight_t=None, glu_done=False, lin_w=None, lin_b=None,
-                       variant: int = 0, causal: bool = False, hist=None, hist_out=None):
+                       variant: int = 0, causal: bool = False, hist=None, hist_out=None, out=None):
     """(batch, seqlen, 2*dim) -> (batch, seqlen, dim): GLU, depthwise conv (k=31, same padding), LayerNorm, GELU
     (cm_glu_dwconv_ln_gelu).  weight (dim, 1, k) or (dim, k); weight_t: optional precomputed fp32 (k, dim) copy of the
     taps (made here per call otherwise) so that the kernel's per-channel tap reads are coalesced.
     ``causal`` (cm_glu_dwconv_ln_gelu_causal): all k - 1 padding rows in front; hist (batch, k - 1, dim) in inp's dtype are
     the gated rows in front of inp (None = zeros), hist_out (another buffer than hist) receives the last k - 1 gated rows of
-    [hist | inp]."""
+    [hist | inp].  ``out``: optional contiguous (batch, seqlen, dim) tensor in inp's dtype to receive the result."""
     _dev_check(inp, weight, bias, ln_weight, ln_bias, hist, hist_out)
     if (hist is not None or hist_out is not None) and not causal:
         raise RuntimeError("glu_dwconv_ln_gelu: hist / hist_out belong to the causal form")
@@ -1631,7 +1642,7 @@ def glu_dwconv_ln_gelu(inp, weight, bias, ln_weight, ln_bias, eps=1e-5, weight_t
     d = d2 if glu_done else d2 // 2                       # glu_done: the input is already gated (cm_ln_pw_glu), dim wide
     w = _f32c(weight).reshape(d, -1)
     bs, g, bt = _f32c(bias), _f32c(ln_weight), _f32c(ln_bias)
-    out = torch.empty((b, l, d), dtype=inp.dtype, device=inp.device)
+    out = _out_rows(out, (b, l, d), inp.dtype, inp.device, "glu_dwconv_ln_gelu: out")
     a = N.GluDwconvCausalArgs() if causal else N.GluDwconvArgs()
     if causal:
         hs = (b, w.shape[1] - 1, d)
@@ -1733,10 +1744,11 @@ def gemm_supported(m: int, n: int, k: int, epilogue: int) -> bool:
     return k % 64 == 0 and n % 256 == 0 and (epilogue != 2 or n == 256)
 
 
-def gemm_bf16(a, w, bias=None, epilogue=0, x=None, alpha=1.0, norm1=None, norm2=None, want_out=True):
+def gemm_bf16(a, w, bias=None, epilogue=0, x=None, alpha=1.0, norm1=None, norm2=None, want_out=True, out=None):
     """acc = a @ w.T (a (M, K) bf16 row view, w (N, K) bf16) with a fused epilogue (cm_gemm_bf16):
     0: + bias -> bf16;  1: gelu(+ bias) -> bf16;  2: x += alpha*(acc + bias) [optional LN1 into x], out = LN2(x) bf16.
-    bias / LayerNorm parameters are fp32 tensors; norm = (weight, bias, eps).  Returns out (or None)."""
+    bias / LayerNorm parameters are fp32 tensors; norm = (weight, bias, eps); ``out``: optional contiguous bf16 (M, N) tensor to
+    receive the result.  Returns out (or None)."""
     _dev_check(a, w, bias, x)
     if a.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or a.dim() != 2 or a.stride(1) != 1 or not w.is_contiguous():
         raise RuntimeError("gemm_bf16: a must be a (M, K) bf16 row-major view and w a contiguous (N, K) bf16 tensor")
@@ -1745,10 +1757,11 @@ def gemm_bf16(a, w, bias=None, epilogue=0, x=None, alpha=1.0, norm1=None, norm2=
     g = N.GemmArgs()
     g.M, g.N, g.K, g.epilogue = m, n, k, epilogue
     g.A, g.lda, g.W, g.ldw, g.bias = _ptr(a), a.stride(0), _ptr(w), w.stride(0), _ptr(bias)
-    out = None
     if epilogue != 2 or want_out:
-        out = torch.empty((m, n), dtype=torch.bfloat16, device=a.device)
+        out = _out_rows(out, (m, n), torch.bfloat16, a.device, "gemm_bf16: out")
         g.out, g.ldo = _ptr(out), n
+    elif out is not None:
+        raise RuntimeError("gemm_bf16: out given with want_out=False")
     if epilogue == 2:
         if x is None or x.dtype != torch.float32 or not x.is_contiguous() or x.shape != (m, n):
             raise RuntimeError("gemm_bf16: epilogue 2 needs a contiguous fp32 residual x of shape (M, N)")
@@ -1820,7 +1833,7 @@ class PackedWeight:
 
 def ffn_fused(x, pre_norm, w1, b1, w2, b2, alpha=0.5, addend=None, add_scale=1.0, norm1=None, norm2=None,
               x_out=None, want_h=True, h_dtype=torch.bfloat16, proj_w=None, proj_b=None, proj_out=None, train=None, tokens=None,
-              resid_acc=None):
+              resid_acc=None, h_out=None, train_out=None):
     """Whole feed-forward module on the fp32 residual stream (cm_ffn_fused):
         xin = x + add_scale*addend;  r = xin + alpha*(W2 gelu(W1 LN_pre(xin) + b1) + b2);  r = LN1(r) if norm1;
         x_out <- r (x itself when x_out is None);  returns h = LN2(r) (or r when norm2 is None) in h_dtype if want_h.
@@ -1834,7 +1847,9 @@ def ffn_fused(x, pre_norm, w1, b1, w2, b2, alpha=0.5, addend=None, add_scale=1.0
     with the backward's inputs stored on the way (D = 256 only) -> (x_out, (pre, xn, stats)): pre (rows, hidden) bf16 = W1 LN(x) + b1, xn (rows, 256)
     bf16 = LN(x), stats (2, rows) fp32 = the rows' mean and 1/std (layernorm_bwd's input); the dropout decisions are cm_dropout.h's function of (seed, element index) (no mask is stored).
     ``resid_acc`` (default: CM_FFN_RESID_ACC): False = the residual rows are loaded again behind the last GEMM instead of riding in the
-    accumulators (any alpha that is no power of two takes that path by itself)."""
+    accumulators (any alpha that is no power of two takes that path by itself).
+    ``h_out`` (contiguous (rows, D) in h_dtype) / ``train_out`` = (pre, xn, stats) (contiguous, shaped and typed as above): optional
+    tensors to receive h / the training forward's stored outputs instead of fresh ones."""
     _dev_check(x, b1, b2, addend, proj_b)
     rows, d = x.shape
     if x.dtype != torch.float32 or not x.is_contiguous():
@@ -1883,15 +1898,22 @@ def ffn_fused(x, pre_norm, w1, b1, w2, b2, alpha=0.5, addend=None, add_scale=1.0
     if train is not None:
         if addend is not None or norm1 is not None or norm2 is not None or proj_w is not None:
             raise RuntimeError("ffn_fused: the training forward takes no addend / norm1 / norm2 / projection")
-        pre = torch.empty((rows, w1.shape[0]), dtype=torch.bfloat16, device=x.device)
-        xn = torch.empty((rows, d), dtype=torch.bfloat16, device=x.device)
-        stats = torch.empty((2, rows), dtype=torch.float32, device=x.device)
+        if h_out is not None:
+            raise RuntimeError("ffn_fused: the training forward returns no h")
+        pre, xn, stats = train_out if train_out is not None else (None, None, None)
+        pre = _out_rows(pre, (rows, w1.shape[0]), torch.bfloat16, x.device, "ffn_fused: train_out[0] (pre)")
+        xn = _out_rows(xn, (rows, d), torch.bfloat16, x.device, "ffn_fused: train_out[1] (xn)")
+        stats = _out_rows(stats, (2, rows), torch.float32, x.device, "ffn_fused: train_out[2] (stats)")
         a.pre_out, a.xn_out, a.stats_out = _ptr(pre), _ptr(xn), _ptr(stats)
         a.p1, a.p2, a.seed1, a.seed2 = float(train[0]), float(train[1]), int(train[2]), int(train[3])
         a.seed_epoch = _seed_epoch_ptr()
         a.stream = _stream()
         _launch("cm_ffn_fused", N.lib().cm_ffn_fused, a, units=rows)
         return xo, (pre, xn, stats)
+    if train_out is not None:
+        raise RuntimeError("ffn_fused: train_out belongs to the training forward")
+    if h_out is not None and (proj_w is not None or not want_h):
+        raise RuntimeError("ffn_fused: h_out given, but h is not stored (projection epilogue or want_h=False)")
     if proj_w is not None:
         if (not isinstance(proj_w, PackedWeight) or proj_w.shape[1] != d or proj_w.shape[0] % (256 if d == 256 else 64) or proj_w.shape[0] > 4096
                 or proj_w.padded != (proj_w.shape[0], kp)):
@@ -1904,7 +1926,7 @@ def ffn_fused(x, pre_norm, w1, b1, w2, b2, alpha=0.5, addend=None, add_scale=1.0
         pb = _f32c(proj_b)
         a.proj_w, a.proj_b, a.proj_out, a.proj_dim = _ptr(proj_w.data), _ptr(pb), _ptr(h), proj_w.shape[0]
     elif want_h:
-        h = torch.empty((rows, d), dtype=h_dtype, device=x.device)
+        h = _out_rows(h_out, (rows, d), h_dtype, x.device, "ffn_fused: h_out")
         a.h_out, a.h_dtype = _ptr(h), _DT[h_dtype]
     a.stream = _stream()
     _launch("cm_ffn_fused", N.lib().cm_ffn_fused, a, units=rows)

@@ -1,0 +1,114 @@
+"""Guard bands inside ONE allocation, for kernels that no address sanitizer watches: an output is a view of a sentinel-filled buffer,
+an input a view of a NaN-filled one.  A store outside the output view turns a sentinel into something else (assert_untouched), a load
+from outside an input view that reaches a result turns it into NaN, so the result no longer has the bits of the plain launch
+(assert_same_bits) and is not finite (assert_finite).  Every check stays inside memory the test allocated: the guards are at least
+one workgroup tile of the kernel under test, so a whole-tile overrun still lands in them.
+
+Geometry.  A 3-D (batch, seqlen, width) view of a (batch + 2, seqlen + rows, left + width + right) buffer: ``left`` / ``right`` guard
+columns beside every row, ``rows`` guard rows behind every utterance, one whole guard utterance in front of the batch and one behind.
+Everything else (2-D (rows, D) tensors the kernels want contiguous; 3-D with contiguous=True; any other rank) stays contiguous: a flat
+buffer with ``rows`` x shape[-1] guard elements in front and behind.
+
+Plain module (as tests/ctc_beam_ref.py), any torch.device.
+"""
+import math
+
+import torch
+
+SENTINEL = -65536.0            # exact in bf16 (-2^16); the cases' results stay far from it (assert_far_from_sentinel on the reference)
+ROW_TILE = 64                  # rows per workgroup of the row kernels (cm_ffn_fused, cm_ln_pw_glu, cm_gemm_bf16, cm_add_layernorm)
+TIME_TILE = 32                 # time steps per workgroup of the time-tiled kernels (conv_xproj, scan, dwconv rows)
+LEFT, RIGHT = 8, 16            # guard columns: 16 / 32 bytes in bf16, 32 / 64 in fp32 -- views stay 16-byte aligned
+
+
+def _geometry(shape, rows, left, right, contiguous):
+    """-> (buffer shape, function buffer -> view)."""
+    shape = tuple(int(s) for s in shape)
+    assert len(shape) >= 1 and all(s > 0 for s in shape) and rows >= 0 and left >= 0 and right >= 0, (shape, rows, left, right)
+    if len(shape) == 3 and not contiguous:
+        b, l, w = shape
+        return (b + 2, l + rows, left + w + right), lambda buf: buf[1:b + 1, :l, left:left + w]
+    assert left == 0 and right == 0, "a contiguous view has no room for guard columns"
+    n, pad = math.prod(shape), rows * shape[-1]
+    return (pad + n + pad,), lambda buf: buf[pad:pad + n].view(shape)
+
+
+def guarded(shape, dtype, device, rows=ROW_TILE, left=0, right=0, contiguous=False, align=16):
+    """-> (sentinel-filled buffer, its view of ``shape``, bool mask of the buffer's elements outside the view).  ``align``: the byte
+    alignment the view's start must keep (16: what the vector loads of most kernels need; odd widths keep less)."""
+    bshape, view_of = _geometry(shape, rows, left, right, contiguous)
+    buf = torch.full(bshape, SENTINEL, dtype=dtype, device=device)
+    assert float(buf.reshape(-1)[0]) == SENTINEL, f"{SENTINEL} is not exact in {dtype}"
+    outside = torch.ones(bshape, dtype=torch.bool, device=device)
+    view_of(outside).fill_(False)
+    view = view_of(buf)
+    assert int(outside.sum()) == buf.numel() - view.numel() and view.data_ptr() % align == 0
+    return buf, view, outside
+
+
+def poisoned(t, rows=ROW_TILE, left=0, right=0, contiguous=False, align=16):
+    """t's values in a view of guarded()'s geometry inside a NaN-filled buffer."""
+    assert t.is_floating_point()
+    bshape, view_of = _geometry(t.shape, rows, left, right, contiguous)
+    buf = torch.full(bshape, float("nan"), dtype=t.dtype, device=t.device)
+    view = view_of(buf)
+    view.copy_(t)
+    assert view.data_ptr() % align == 0
+    return view
+
+
+def assert_untouched(buffer, outside_mask, name):
+    """Every element outside the view still holds the sentinel."""
+    hit = (buffer != SENTINEL) & outside_mask
+    if bool(hit.any()):
+        idx = hit.nonzero()
+        first = tuple(int(i) for i in idx[0])
+        raise AssertionError(f"{name}: {idx.shape[0]} element(s) written outside the view; first at buffer index {first} "
+                             f"(buffer shape {tuple(buffer.shape)}): {float(buffer[first])!r}")
+
+
+def assert_finite(t, name):
+    bad = ~torch.isfinite(t)
+    assert not bool(bad.any()), f"{name}: {int(bad.sum())} of {t.numel()} element(s) not finite: memory outside an input view reached the result"
+
+
+def assert_same_bits(got, want, name):
+    """The guarded launch's output against the plain launch's: shape, dtype and every bit (NaN equals nothing)."""
+    assert got.shape == want.shape and got.dtype == want.dtype, f"{name}: {tuple(got.shape)} {got.dtype} vs {tuple(want.shape)} {want.dtype}"
+    if not torch.equal(got, want):
+        diff = ~(got == want)
+        first = tuple(int(i) for i in diff.nonzero()[0])
+        raise AssertionError(f"{name}: {int(diff.sum())} of {got.numel()} element(s) differ from the plain launch; first at {first}: "
+                             f"{float(got[first])!r} vs {float(want[first])!r}")
+
+
+def assert_far_from_sentinel(ref, name):
+    """The case's reference output is finite and below half the sentinel's magnitude: a result cannot pass for an untouched guard."""
+    r = ref.detach().double()
+    assert bool(torch.isfinite(r).all()), f"{name}: reference not finite"
+    assert float(r.abs().max()) < 0.5 * abs(SENTINEL), f"{name}: reference reaches {float(r.abs().max()):.3e}, too near the sentinel {SENTINEL}"
+
+
+class Guards:
+    """The guarded outputs of one launch: ``view = g.out(name, shape, dtype, ...)`` per output, then ``g.check({name: plain result})``:
+    the plain launch's outputs are far from the sentinel and finite; the guarded views hold their bits; nothing outside is written."""
+
+    def __init__(self, device):
+        self.device, self.items = device, {}
+
+    def out(self, name, shape, dtype, **kw):
+        assert name not in self.items, name
+        self.items[name] = guarded(shape, dtype, self.device, **kw)
+        return self.items[name][1]
+
+    def view(self, name):
+        return self.items[name][1]
+
+    def check(self, plain):
+        assert set(plain) == set(self.items), (sorted(plain), sorted(self.items))
+        for name, want in plain.items():
+            buf, view, outside = self.items[name]
+            assert_far_from_sentinel(want, name)
+            assert_untouched(buf, outside, name)
+            assert_finite(view, name)
+            assert_same_bits(view, want, name)

@@ -446,12 +446,14 @@ def test_dwconv1d_forward_backward(ops, shape, k, causal, dtype):
 
 
 @pytest.mark.parametrize("shape,k,causal", [((2, 250, 48), 31, False), ((3, 1000, 256), 31, False), ((2, 37, 17), 31, True),
-                                            ((1, 2500, 8), 15, False), ((2, 5, 144), 31, False), ((2, 130, 300), 31, False)])
+                                            ((1, 2500, 8), 15, False), ((2, 5, 144), 31, False), ((2, 130, 300), 31, False),
+                                            ((2, 70, 256), 32, False), ((2, 70, 256), 32, True)])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_dwconv_channels_last_forward_backward(ops, shape, k, causal, dtype):
     """cm_dwconv_cl_fwd / _bwd (channels-last rows; the autograd node of the module-API ConvolutionModule) vs torch's
     depthwise conv1d + autograd in float64: ragged tiles / runs, dim above and below one workgroup, causal padding; the
-    tap gradients are bit-identical between two runs (fixed-order reduction)."""
+    tap gradients are bit-identical between two runs (fixed-order reduction).  k = 32 with a full 256-channel block: the largest tap
+    table (256 x 32 floats) the tiled kernels stage in the tile's LDS region, more than one bf16 tile."""
     b, l, d = shape
     gen = torch.Generator().manual_seed(l + d + k)
     x = torch.randn(b, l, d, generator=gen).to(dtype)
@@ -462,7 +464,7 @@ def test_dwconv_channels_last_forward_backward(ops, shape, k, causal, dtype):
     wr, br = w.double().requires_grad_(True), bias.double().requires_grad_(True)
     pad = k - 1 if causal else k // 2
     ref = torch.nn.functional.conv1d(xr.transpose(1, 2), wr, br, padding=pad, groups=d)
-    ref = (ref[..., :l] if causal else ref).transpose(1, 2)
+    ref = ref[..., :l].transpose(1, 2)                 # causal: the k - 1 trailing steps; an even k padded k // 2 on both sides: one
     ref.backward(dy.double())
     xg = x.to(DEV).requires_grad_(True)
     wg, bg = w.to(DEV).requires_grad_(True), bias.to(DEV).requires_grad_(True)
