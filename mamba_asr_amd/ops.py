@@ -106,10 +106,11 @@ class ReflectPadTfFn(torch.autograd.Function):
         return reflect_pad_tf(dy if dy.is_contiguous() else dy.contiguous(), ctx.pad, backward=True, shape=ctx.shape), None
 
 
-def wgrad(a, b, nbatch=None, variant=0):
+def wgrad(a, b, nbatch=None, variant=0, bufs=None):
     """dW (M, N) fp32 = a^T b for a (rows, M), b (rows, N): the weight gradient of a Linear from its output gradient and its input.
     bf16 operands with M, N multiples of 128: cm_wgrad_bf16 (split over row chunks, fixed-order fold).  Otherwise ``nbatch``
-    batched GEMMs over equal row chunks folded by cm_sum_leading (fp32 accumulation in a fixed order either way)."""
+    batched GEMMs over equal row chunks folded by cm_sum_leading (fp32 accumulation in a fixed order either way).
+    ``bufs``: caller-supplied ``out`` (M, N) and ``workspace`` (cm_wgrad_workspace_floats) of the cm_wgrad_bf16 route."""
     _dev_check(a, b)
     rows, M = a.shape
     Nn = b.shape[1]
@@ -119,11 +120,14 @@ def wgrad(a, b, nbatch=None, variant=0):
         args.rows, args.m, args.n, args.variant = rows, M, Nn, int(variant)   # 0: the library picks; 1 registers, 2 LDS-DMA staging
         args.a, args.b, args.lda, args.ldb = _ptr(a), _ptr(b), a.stride(0), b.stride(0)
         nws = int(N.lib().cm_wgrad_workspace_floats(rows, M, Nn))
-        ws = torch.empty((nws,), dtype=torch.float32, device=a.device)
-        out = torch.empty((M, Nn), dtype=torch.float32, device=a.device)
+        take = _bufs(bufs, ("out", "workspace"), "wgrad")
+        ws = take("workspace", (nws,), torch.float32, a.device)
+        out = take("out", (M, Nn), torch.float32, a.device)
         args.out, args.workspace, args.workspace_floats, args.stream = _ptr(out), _ptr(ws), nws, _stream()
         _launch("cm_wgrad_bf16", N.lib().cm_wgrad_bf16, args, units=rows)
         return out
+    if bufs is not None:
+        raise RuntimeError("wgrad: bufs places the buffers of cm_wgrad_bf16, which does not take these operands")
     nb = nbatch if (nbatch and rows % nbatch == 0) else 1
     return sum_leading(torch.bmm(a.view(nb, rows // nb, M).transpose(1, 2), b.view(nb, rows // nb, Nn)))
 
@@ -138,11 +142,13 @@ def pack_cached_t(p: torch.Tensor) -> "PackedWeight":
     return _PACK_T.lookup(p, weight_cache.param_key(p))
 
 
-def ffn_bwd_fused(dout, w2t, w1t, pre, alpha, p1, p2, seed1, seed2):
+def ffn_bwd_fused(dout, w2t, w1t, pre, alpha, p1, p2, seed1, seed2, bufs=None):
     """The data-gradient chain of a feed-forward module's backward in one kernel (cm_ffn_bwd_fused), for the forward
     ffn_fused(..., train=(p1, p2, seed1, seed2)) ran.  dout (rows, 256) fp32; w2t / w1t PackedWeight of W2^T (hidden, 256) /
     W1^T (256, hidden); pre (rows, hidden) bf16.  -> (da2, da1, act, dh, db1, db2): bf16 (rows, 256) / (rows, hidden) x 2 /
-    (rows, 256), fp32 (hidden) / (256)."""
+    (rows, 256), fp32 (hidden) / (256).
+    ``bufs``: caller-supplied ``da2`` / ``da1`` / ``act`` / ``dh``, ``db1`` (hidden + 256 floats: [db1 | db2], which the C contract
+    wants adjacent) and ``workspace`` (cm_ffn_bwd_workspace_floats)."""
     _dev_check(dout, pre)
     rows, d = dout.shape
     hidden = pre.shape[1]
@@ -151,13 +157,18 @@ def ffn_bwd_fused(dout, w2t, w1t, pre, alpha, p1, p2, seed1, seed2):
     if w2t.shape != (hidden, d) or w1t.shape != (d, hidden):
         raise RuntimeError("ffn_bwd_fused: packed weight shapes do not match")
     dev = dout.device
-    da2 = torch.empty((rows, d), dtype=torch.bfloat16, device=dev)
-    dh = torch.empty((rows, d), dtype=torch.bfloat16, device=dev)
-    da1 = torch.empty((rows, hidden), dtype=torch.bfloat16, device=dev)
-    act = torch.empty((rows, hidden), dtype=torch.bfloat16, device=dev)
+    take = _bufs(bufs, ("da2", "da1", "act", "dh", "db1", "workspace"), "ffn_bwd_fused")
+    da2 = take("da2", (rows, d), torch.bfloat16, dev)
+    dh = take("dh", (rows, d), torch.bfloat16, dev)
+    da1 = take("da1", (rows, hidden), torch.bfloat16, dev)
+    act = take("act", (rows, hidden), torch.bfloat16, dev)
     nws = int(N.lib().cm_ffn_bwd_workspace_floats(rows, hidden))
-    ws = torch.empty((nws + hidden + d,), dtype=torch.float32, device=dev)
-    db1, db2 = ws[nws:nws + hidden], ws[nws + hidden:]
+    if bufs is None:
+        ws = torch.empty((nws + hidden + d,), dtype=torch.float32, device=dev)
+        db1, db2 = ws[nws:nws + hidden], ws[nws + hidden:]
+    else:
+        ws, db = take("workspace", (nws,), torch.float32, dev), take("db1", (hidden + d,), torch.float32, dev)
+        db1, db2 = db[:hidden], db[hidden:]
     a = N.FfnBwdArgs()
     a.rows, a.dim, a.hidden = rows, d, hidden
     a.dout, a.w2t, a.w1t, a.pre = _ptr(dout), _ptr(w2t.data), _ptr(w1t.data), _ptr(pre)
@@ -177,6 +188,29 @@ def _dev_check(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:
             raise RuntimeError("mamba_asr_amd ops run on the GPU only (got a CPU tensor); there is no CPU fallback")
+
+
+def _fresh(name, shape, dtype, device, rows3=False):
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+def _bufs(bufs, names, what):
+    """-> take(name, shape, dtype, device): the caller-supplied buffer ``bufs[name]`` (a dict from the C struct's field name to a
+    tensor; the guard-band tests place outputs and workspaces with it), validated as _out_rows does, or a fresh one.  None: every
+    buffer is fresh.  ``rows3``: a (batch, seqlen, dim) buffer may be any view with the channel axis contiguous."""
+    if bufs is None:
+        return _fresh
+    if not set(bufs) <= set(names):
+        raise RuntimeError(f"{what}: bufs has no {sorted(set(bufs) - set(names))}; its names are {sorted(names)}")
+
+    def take(name, shape, dtype, device, rows3=False):
+        t = bufs.get(name)
+        if t is not None and rows3:
+            if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.stride(2) != 1 or t.device != device:
+                raise RuntimeError(f"{what}: bufs[{name!r}] must be a {dtype} tensor of shape {tuple(shape)} on {device} with the channel axis contiguous")
+            return t
+        return _out_rows(t, shape, dtype, device, f"{what}: bufs[{name!r}]")
+    return take
 
 
 def _time_contig(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -586,21 +620,22 @@ def effective_seed(seed: int, epoch: int) -> int:
     return (int(seed) + int(epoch) * SEED_EPOCH_MUL) & (2 ** 64 - 1)
 
 
-def bias_act_dropout_fwd(a, bias, act=0, p=0.0, res=None, alpha=1.0, seed=None, store_mask=True):
+def bias_act_dropout_fwd(a, bias, act=0, p=0.0, res=None, alpha=1.0, seed=None, store_mask=True, bufs=None):
     """y = dropout(act(a + bias)) in a's dtype, or with ``res`` (fp32, a's shape) y = res + alpha * dropout(a + bias) in fp32
     (cm_bias_act_dropout_fwd).  a (rows, dim) contiguous bf16 / fp32; act 0 none, 1 GELU.  -> (y, mask or None).
     The keep decisions are a function of (seed, element index) (csrc/cm_dropout.h): with ``seed`` given (draw_seed()) and
-    ``store_mask=False`` no mask is written and bias_act_dropout_bwd re-derives it from the same seed."""
+    ``store_mask=False`` no mask is written and bias_act_dropout_bwd re-derives it from the same seed.  ``bufs``: caller-supplied ``y`` and ``mask``."""
     _dev_check(a, bias, res)
     if a.dim() != 2 or not a.is_contiguous() or a.dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError("bias_act_dropout_fwd: a must be a contiguous (rows, dim) bf16 / fp32 tensor")
     rows, dim = a.shape
     args = _elem_args(rows, dim, a.dtype, act, p, alpha)
     bs = _f32c(bias)
-    mask = torch.empty((rows, dim), dtype=torch.uint8, device=a.device) if (p > 0.0 and store_mask) else None
+    take = _bufs(bufs, ("y", "mask"), "bias_act_dropout_fwd")
+    mask = take("mask", (rows, dim), torch.uint8, a.device) if (p > 0.0 and store_mask) else None
     if res is not None and (res.dtype != torch.float32 or not res.is_contiguous() or res.shape != a.shape):
         raise RuntimeError("bias_act_dropout_fwd: res must be a contiguous fp32 tensor of a's shape")
-    y = torch.empty((rows, dim), dtype=torch.float32 if res is not None else a.dtype, device=a.device)
+    y = take("y", (rows, dim), torch.float32 if res is not None else a.dtype, a.device)
     args.a, args.bias, args.res, args.y, args.mask = _ptr(a), _ptr(bs), _ptr(res), _ptr(y), _ptr(mask)
     if p > 0.0:
         args.seed = draw_seed() if seed is None else int(seed)
@@ -608,11 +643,13 @@ def bias_act_dropout_fwd(a, bias, act=0, p=0.0, res=None, alpha=1.0, seed=None, 
     return y, mask
 
 
-def bias_act_dropout_bwd(dy, mask, p, a=None, bias=None, act=0, alpha=1.0, out_dtype=None, want_dbias=True, seed=None, want_act=False):
+def bias_act_dropout_bwd(dy, mask, p, a=None, bias=None, act=0, alpha=1.0, out_dtype=None, want_dbias=True, seed=None, want_act=False,
+                         bufs=None):
     """da = alpha * dy * mask / (1 - p) * act'(a + bias) in ``out_dtype`` (default a's / dy's dtype); dbias = column sums of da
     (fp32, deterministic) (cm_bias_act_dropout_bwd).  dy (rows, dim) fp32 or the I/O dtype.  -> (da, dbias or None).
     ``mask`` None with ``seed`` given: the decisions are re-derived from the seed.  ``want_act`` (act 1, bf16): also returns
-    dropout(GELU(a + bias)) recomputed, as cm_ffn_fused's training forward fed it to its second GEMM -> (da, dbias, act)."""
+    dropout(GELU(a + bias)) recomputed, as cm_ffn_fused's training forward fed it to its second GEMM -> (da, dbias, act).
+    ``bufs``: caller-supplied ``da``, ``act_out``, ``dbias`` and ``dbias_part`` (cm_bias_act_dropout_bwd_workspace_floats)."""
     _dev_check(dy, mask, a, bias)
     if dy.dim() != 2 or not dy.is_contiguous():
         raise RuntimeError("bias_act_dropout_bwd: dy must be a contiguous (rows, dim) tensor")
@@ -626,24 +663,28 @@ def bias_act_dropout_bwd(dy, mask, p, a=None, bias=None, act=0, alpha=1.0, out_d
     if seed is not None:
         args.seed = int(seed)
     bs = _f32c(bias)
-    da = torch.empty((rows, dim), dtype=io, device=dy.device)
+    take = _bufs(bufs, ("da", "act_out", "dbias", "dbias_part"), "bias_act_dropout_bwd")
+    da = take("da", (rows, dim), io, dy.device)
     act_out = None
     if want_act:
-        act_out = torch.empty((rows, dim), dtype=io, device=dy.device)
+        act_out = take("act_out", (rows, dim), io, dy.device)
         args.act_out = _ptr(act_out)
     args.a, args.bias, args.mask, args.dy, args.da = _ptr(a), _ptr(bs), _ptr(mask), _ptr(dy), _ptr(da)
     args.dy_f32 = int(dy.dtype == torch.float32 and io != torch.float32)
     dbias = None
     if want_dbias:
         nws = int(N.lib().cm_bias_act_dropout_bwd_workspace_floats(rows, dim))
-        ws = torch.empty((nws + dim,), dtype=torch.float32, device=dy.device)
-        dbias = ws[nws:]
+        if bufs is None:
+            ws = torch.empty((nws + dim,), dtype=torch.float32, device=dy.device)
+            dbias = ws[nws:]
+        else:
+            ws, dbias = take("dbias_part", (nws,), torch.float32, dy.device), take("dbias", (dim,), torch.float32, dy.device)
         args.dbias, args.dbias_part, args.overwrite = _ptr(dbias), _ptr(ws), 1
     _launch("cm_bias_act_dropout_bwd", N.lib().cm_bias_act_dropout_bwd, args, units=rows)
     return (da, dbias, act_out) if want_act else (da, dbias)
 
 
-def bias_glu_fwd(a, bias):
+def bias_glu_fwd(a, bias, bufs=None):
     """(rows, 2 dim) -> (rows, dim): (a[:, :dim] + b[:dim]) * sigmoid(a[:, dim:] + b[dim:])  (cm_bias_act_dropout_fwd, act 2)."""
     _dev_check(a, bias)
     rows, d2 = a.shape
@@ -651,13 +692,13 @@ def bias_glu_fwd(a, bias):
         raise RuntimeError("bias_glu_fwd: a must be a contiguous (rows, 2 dim) bf16 / fp32 tensor, dim a multiple of 8")
     args = _elem_args(rows, d2 // 2, a.dtype, 2, 0.0, 1.0)
     bs = _f32c(bias)
-    y = torch.empty((rows, d2 // 2), dtype=a.dtype, device=a.device)
+    y = _bufs(bufs, ("y",), "bias_glu_fwd")("y", (rows, d2 // 2), a.dtype, a.device)
     args.a, args.bias, args.y = _ptr(a), _ptr(bs), _ptr(y)
     _launch("cm_bias_act_dropout_fwd", N.lib().cm_bias_act_dropout_fwd, args, units=rows)
     return y
 
 
-def bias_glu_bwd(dy, a, bias):
+def bias_glu_bwd(dy, a, bias, bufs=None):
     """-> (da (rows, 2 dim) in a's dtype, dbias (2 dim) fp32) of bias_glu_fwd (cm_bias_act_dropout_bwd, act 2; deterministic)."""
     _dev_check(dy, a, bias)
     rows, d = dy.shape
@@ -665,10 +706,15 @@ def bias_glu_bwd(dy, a, bias):
         raise RuntimeError("bias_glu_bwd: dy (rows, dim) and a (rows, 2 dim) must be contiguous and share a dtype")
     args = _elem_args(rows, d, a.dtype, 2, 0.0, 1.0)
     bs = _f32c(bias)
-    da = torch.empty_like(a)
     nws = int(N.lib().cm_bias_act_dropout_bwd_workspace_floats(rows, d))
-    ws = torch.empty((nws + 2 * d,), dtype=torch.float32, device=dy.device)
-    dbias = ws[nws:]
+    if bufs is None:
+        da = torch.empty_like(a)
+        ws = torch.empty((nws + 2 * d,), dtype=torch.float32, device=dy.device)
+        dbias = ws[nws:]
+    else:
+        take = _bufs(bufs, ("da", "dbias", "dbias_part"), "bias_glu_bwd")
+        da = take("da", a.shape, a.dtype, a.device)
+        ws, dbias = take("dbias_part", (nws,), torch.float32, dy.device), take("dbias", (2 * d,), torch.float32, dy.device)
     args.overwrite = 1
     args.a, args.bias, args.dy, args.da, args.dbias, args.dbias_part = _ptr(a), _ptr(bs), _ptr(dy), _ptr(da), _ptr(dbias), _ptr(ws)
     _launch("cm_bias_act_dropout_bwd", N.lib().cm_bias_act_dropout_bwd, args, units=rows)
@@ -1416,19 +1462,22 @@ def _dwconv_cl_args(x, weight, bias, pad_left):
     return a, w, bs
 
 
-def dwconv_cl_fwd(x, weight, bias=None, pad_left=None):
+def dwconv_cl_fwd(x, weight, bias=None, pad_left=None, bufs=None):
     """Depthwise Conv1d over time on channels-last rows (cm_dwconv_cl_fwd): x (batch, seqlen, dim), channel axis
-    contiguous; weight (dim, 1, k) or (dim, k); returns y (batch, seqlen, dim)."""
+    contiguous; weight (dim, 1, k) or (dim, k); returns y (batch, seqlen, dim).  ``bufs``: a caller-supplied ``y`` (any view with
+    the channel axis contiguous)."""
     k = weight.shape[-1]
     a, w, bs = _dwconv_cl_args(x, weight, bias, k // 2 if pad_left is None else pad_left)
-    y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    y = _bufs(bufs, ("y",), "dwconv_cl_fwd")("y", x.shape, x.dtype, x.device, rows3=True)
     a.y, a.y_bs, a.y_ts = _ptr(y), y.stride(0), y.stride(1)
     _launch("cm_dwconv_cl_fwd", N.lib().cm_dwconv_cl_fwd, a, units=x.shape[0] * x.shape[1])
     return y
 
 
-def dwconv_cl_bwd(x, weight, dy, has_bias=True, pad_left=None):
-    """-> (dx, dweight (dim, k) fp32, dbias (dim) fp32 or None) of dwconv_cl_fwd (cm_dwconv_cl_bwd, deterministic)."""
+def dwconv_cl_bwd(x, weight, dy, has_bias=True, pad_left=None, bufs=None):
+    """-> (dx, dweight (dim, k) fp32, dbias (dim) fp32 or None) of dwconv_cl_fwd (cm_dwconv_cl_bwd, deterministic).
+    ``bufs``: caller-supplied ``dx`` (any view with the channel axis contiguous), ``dweight``, ``dbias`` and ``partial``
+    (cm_dwconv_cl_workspace_floats)."""
     k = weight.shape[-1]
     a, w, _ = _dwconv_cl_args(x, weight, None, k // 2 if pad_left is None else pad_left)
     _dev_check(dy)
@@ -1436,11 +1485,12 @@ def dwconv_cl_bwd(x, weight, dy, has_bias=True, pad_left=None):
         dy = dy.contiguous()
     if dy.dtype != x.dtype or dy.shape != x.shape:
         raise RuntimeError("dwconv_cl_bwd: dy must match x in shape and dtype")
-    dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-    dw = torch.empty_like(w)
-    db = torch.empty((x.shape[2],), dtype=torch.float32, device=x.device) if has_bias else None
+    take = _bufs(bufs, ("dx", "dweight", "dbias", "partial"), "dwconv_cl_bwd")
+    dx = take("dx", x.shape, x.dtype, x.device, rows3=True)
+    dw = take("dweight", w.shape, torch.float32, x.device)
+    db = take("dbias", (x.shape[2],), torch.float32, x.device) if has_bias else None
     a.overwrite = 1
-    part = torch.empty((N.lib().cm_dwconv_cl_workspace_floats(x.shape[0], x.shape[1], x.shape[2]),), dtype=torch.float32, device=x.device)
+    part = take("partial", (N.lib().cm_dwconv_cl_workspace_floats(x.shape[0], x.shape[1], x.shape[2]),), torch.float32, x.device)
     a.dy, a.dy_bs, a.dy_ts, a.dx, a.dx_bs, a.dx_ts = _ptr(dy), dy.stride(0), dy.stride(1), _ptr(dx), dx.stride(0), dx.stride(1)
     a.dweight, a.dbias, a.partial = _ptr(dw), _ptr(db), _ptr(part)
     _launch("cm_dwconv_cl_bwd", N.lib().cm_dwconv_cl_bwd, a, units=x.shape[0] * x.shape[1])
@@ -1484,9 +1534,10 @@ def _ln_epilogue(a, x2, leaky_slope, chan_mask, mask_rows):
         a.chan_mask, a.mask_rows, a.mask_c = _ptr(chan_mask), int(mask_rows), c
 
 
-def layernorm_fwd(x, weight, bias, eps, out_dtype=None, leaky_slope=None, chan_mask=None, mask_rows=1):
+def layernorm_fwd(x, weight, bias, eps, out_dtype=None, leaky_slope=None, chan_mask=None, mask_rows=1, bufs=None):
     """LayerNorm over the last axis (cm_layernorm_fwd) -> (y, mean, rstd); x fp32 or bf16, contiguous rows; y in
-    `out_dtype` (default fp32: what torch's autocast gives, reference modules/Conmamba.py:597-620)."""
+    `out_dtype` (default fp32: what torch's autocast gives, reference modules/Conmamba.py:597-620).  ``bufs``: caller-supplied ``y`` (rows, dim)
+    and ``mean`` ((2, rows): [mean | rstd], the one statistics tensor returned)."""
     _dev_check(x, weight, bias)
     if x.dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError(f"layernorm_fwd: unsupported dtype {x.dtype}")
@@ -1495,8 +1546,9 @@ def layernorm_fwd(x, weight, bias, eps, out_dtype=None, leaky_slope=None, chan_m
         x2 = x2.contiguous()
     out_dtype = out_dtype or torch.float32
     w, b = weight.detach().float().contiguous(), bias.detach().float().contiguous()
-    y = torch.empty(x2.shape, dtype=out_dtype, device=x.device)
-    stats = torch.empty((2, x2.shape[0]), dtype=torch.float32, device=x.device)
+    take = _bufs(bufs, ("y", "mean"), "layernorm_fwd")
+    y = take("y", x2.shape, out_dtype, x.device)
+    stats = take("mean", (2, x2.shape[0]), torch.float32, x.device)
     a = _layernorm_args(x2, w, eps, out_dtype)
     a.beta, a.y, a.mean, a.rstd = _ptr(b), _ptr(y), _ptr(stats[0]), _ptr(stats[1])
     _ln_epilogue(a, x2, leaky_slope, chan_mask, mask_rows)
@@ -1504,17 +1556,21 @@ def layernorm_fwd(x, weight, bias, eps, out_dtype=None, leaky_slope=None, chan_m
     return y.view(x.shape), x2, stats
 
 
-def layernorm_bwd(dy, x2, stats, weight, eps, need_dx=True, dres=None, bias=None, leaky_slope=None, chan_mask=None, mask_rows=1):
+def layernorm_bwd(dy, x2, stats, weight, eps, need_dx=True, dres=None, bias=None, leaky_slope=None, chan_mask=None, mask_rows=1,
+                  bufs=None):
     """-> (dx (x2's dtype and shape) or None, dgamma, dbeta (dim) fp32) of layernorm_fwd (cm_layernorm_bwd, deterministic).
-    ``dres`` (fp32, x2's shape; fp32 x2, dim <= 1024): added to dx in the same pass (the residual branch's gradient)."""
+    ``dres`` (fp32, x2's shape; fp32 x2, dim <= 1024): added to dx in the same pass (the residual branch's gradient).
+    ``bufs``: caller-supplied ``dx``, ``dgamma`` ((2, dim): [dgamma | dbeta], the one tensor both are returned from) and
+    ``workspace`` (cm_layernorm_bwd_workspace_floats)."""
     _dev_check(dy, x2, stats, weight)
     dy2 = dy.reshape(x2.shape)
     if not dy2.is_contiguous():
         dy2 = dy2.contiguous()
     w = weight.detach().float().contiguous()
-    dx = torch.empty_like(x2) if need_dx else None
-    dgb = torch.empty((2, x2.shape[1]), dtype=torch.float32, device=x2.device)
-    ws = torch.empty((N.lib().cm_layernorm_bwd_workspace_floats(x2.shape[0], x2.shape[1]),), dtype=torch.float32, device=x2.device)
+    take = _bufs(bufs, ("dx", "dgamma", "workspace"), "layernorm_bwd")
+    dx = (torch.empty_like(x2) if bufs is None else take("dx", x2.shape, x2.dtype, x2.device)) if need_dx else None
+    dgb = take("dgamma", (2, x2.shape[1]), torch.float32, x2.device)
+    ws = take("workspace", (N.lib().cm_layernorm_bwd_workspace_floats(x2.shape[0], x2.shape[1]),), torch.float32, x2.device)
     a = _layernorm_args(x2, w, eps, dy2.dtype)
     a.mean, a.rstd, a.dy, a.dx = _ptr(stats[0]), _ptr(stats[1]), _ptr(dy2), _ptr(dx)
     a.dgamma, a.dbeta, a.workspace = _ptr(dgb[0]), _ptr(dgb[1]), _ptr(ws)

@@ -6,8 +6,17 @@ one workgroup tile of the kernel under test, so a whole-tile overrun still lands
 
 Geometry.  A 3-D (batch, seqlen, width) view of a (batch + 2, seqlen + rows, left + width + right) buffer: ``left`` / ``right`` guard
 columns beside every row, ``rows`` guard rows behind every utterance, one whole guard utterance in front of the batch and one behind.
+A 2-D (rows, width) tensor given guard columns (left or right > 0) is a column slice of a wider matrix: the same geometry with batch 1,
+indexed [0] -- ``rows`` guard rows behind, a whole guard block in front and behind, guard columns beside every row.
 Everything else (2-D (rows, D) tensors the kernels want contiguous; 3-D with contiguous=True; any other rank) stays contiguous: a flat
 buffer with ``rows`` x shape[-1] guard elements in front and behind.
+
+Integer outputs (the uint8 dropout mask) take INT_SENTINEL: -65536 does not exist in uint8, and the byte is neither 0 nor 1.
+A workspace (Guards.scratch) is NaN inside and sentinel outside: nothing outside may be written, and a partial row that a fold reads
+although no workgroup wrote it brings NaN into a result, where assert_finite / assert_same_bits report it -- a recycled
+allocation would still hold the previous launch's correct partials there.
+
+Launch / two_step: the two-launch protocol the GPU files share (plain tensors, then poisoned inputs / guarded outputs).
 
 Plain module (as tests/ctc_beam_ref.py), any torch.device.
 """
@@ -16,6 +25,7 @@ import math
 import torch
 
 SENTINEL = -65536.0            # exact in bf16 (-2^16); the cases' results stay far from it (assert_far_from_sentinel on the reference)
+INT_SENTINEL = 0xA5            # integer outputs (a stored keep mask holds 0 / 1 only)
 ROW_TILE = 64                  # rows per workgroup of the row kernels (cm_ffn_fused, cm_ln_pw_glu, cm_gemm_bf16, cm_add_layernorm)
 TIME_TILE = 32                 # time steps per workgroup of the time-tiled kernels (conv_xproj, scan, dwconv rows)
 LEFT, RIGHT = 8, 16            # guard columns: 16 / 32 bytes in bf16, 32 / 64 in fp32 -- views stay 16-byte aligned
@@ -28,17 +38,24 @@ def _geometry(shape, rows, left, right, contiguous):
     if len(shape) == 3 and not contiguous:
         b, l, w = shape
         return (b + 2, l + rows, left + w + right), lambda buf: buf[1:b + 1, :l, left:left + w]
+    if len(shape) == 2 and not contiguous and (left or right):
+        l, w = shape
+        return (3, l + rows, left + w + right), lambda buf: buf[1:2, :l, left:left + w][0]
     assert left == 0 and right == 0, "a contiguous view has no room for guard columns"
     n, pad = math.prod(shape), rows * shape[-1]
     return (pad + n + pad,), lambda buf: buf[pad:pad + n].view(shape)
+
+
+def sentinel_of(dtype):
+    return SENTINEL if dtype.is_floating_point else INT_SENTINEL
 
 
 def guarded(shape, dtype, device, rows=ROW_TILE, left=0, right=0, contiguous=False, align=16):
     """-> (sentinel-filled buffer, its view of ``shape``, bool mask of the buffer's elements outside the view).  ``align``: the byte
     alignment the view's start must keep (16: what the vector loads of most kernels need; odd widths keep less)."""
     bshape, view_of = _geometry(shape, rows, left, right, contiguous)
-    buf = torch.full(bshape, SENTINEL, dtype=dtype, device=device)
-    assert float(buf.reshape(-1)[0]) == SENTINEL, f"{SENTINEL} is not exact in {dtype}"
+    buf = torch.full(bshape, sentinel_of(dtype), dtype=dtype, device=device)
+    assert float(buf.reshape(-1)[0]) == sentinel_of(dtype), f"{sentinel_of(dtype)} is not exact in {dtype}"
     outside = torch.ones(bshape, dtype=torch.bool, device=device)
     view_of(outside).fill_(False)
     view = view_of(buf)
@@ -57,9 +74,22 @@ def poisoned(t, rows=ROW_TILE, left=0, right=0, contiguous=False, align=16):
     return view
 
 
+def scratch(numel, dtype, device, pad=4096):
+    """A workspace of ``numel`` elements: NaN inside, ``pad`` sentinel elements in front and behind (at least one partial row of the
+    kernel under test).  -> (buffer, view, outside mask) as guarded()."""
+    assert dtype.is_floating_point and numel > 0 and pad > 0 and (pad * dtype.itemsize) % 16 == 0, (numel, dtype, pad)
+    buf = torch.full((pad + numel + pad,), SENTINEL, dtype=dtype, device=device)
+    outside = torch.ones(buf.shape, dtype=torch.bool, device=device)
+    outside[pad:pad + numel] = False
+    view = buf[pad:pad + numel]
+    view.fill_(float("nan"))
+    assert view.data_ptr() % 16 == 0
+    return buf, view, outside
+
+
 def assert_untouched(buffer, outside_mask, name):
-    """Every element outside the view still holds the sentinel."""
-    hit = (buffer != SENTINEL) & outside_mask
+    """Every element outside the view still holds the sentinel (of the buffer's dtype)."""
+    hit = (buffer != sentinel_of(buffer.dtype)) & outside_mask
     if bool(hit.any()):
         idx = hit.nonzero()
         first = tuple(int(i) for i in idx[0])
@@ -83,18 +113,29 @@ def assert_same_bits(got, want, name):
 
 
 def assert_far_from_sentinel(ref, name):
-    """The case's reference output is finite and below half the sentinel's magnitude: a result cannot pass for an untouched guard."""
+    """The case's reference output is finite and below half the sentinel's magnitude: a result cannot pass for an untouched guard.
+    An integer output never holds the sentinel byte."""
+    if not ref.dtype.is_floating_point:
+        assert not bool((ref == INT_SENTINEL).any()), f"{name}: reference holds the integer sentinel {INT_SENTINEL:#x}"
+        return
     r = ref.detach().double()
     assert bool(torch.isfinite(r).all()), f"{name}: reference not finite"
     assert float(r.abs().max()) < 0.5 * abs(SENTINEL), f"{name}: reference reaches {float(r.abs().max()):.3e}, too near the sentinel {SENTINEL}"
 
 
 class Guards:
-    """The guarded outputs of one launch: ``view = g.out(name, shape, dtype, ...)`` per output, then ``g.check({name: plain result})``:
-    the plain launch's outputs are far from the sentinel and finite; the guarded views hold their bits; nothing outside is written."""
+    """The guarded outputs of one launch: ``view = g.out(name, shape, dtype, ...)`` per output, ``g.scratch(name, numel, dtype)`` per
+    workspace, then ``g.check({name: plain result})``: the plain launch's outputs are far from the sentinel and finite; the guarded
+    views hold their bits; nothing outside an output or a workspace is written (a workspace's content is the kernel's own)."""
 
     def __init__(self, device):
-        self.device, self.items = device, {}
+        self.device, self.items, self.scratches = device, {}, set()
+
+    def scratch(self, name, numel, dtype, pad=4096):
+        assert name not in self.items, name
+        self.items[name] = scratch(numel, dtype, self.device, pad)
+        self.scratches.add(name)
+        return self.items[name][1]
 
     def out(self, name, shape, dtype, **kw):
         assert name not in self.items, name
@@ -105,10 +146,65 @@ class Guards:
         return self.items[name][1]
 
     def check(self, plain):
-        assert set(plain) == set(self.items), (sorted(plain), sorted(self.items))
+        assert set(plain) == set(self.items) - self.scratches, (sorted(plain), sorted(self.items), sorted(self.scratches))
+        for name in sorted(self.scratches):
+            assert_untouched(self.items[name][0], self.items[name][2], name)
         for name, want in plain.items():
             buf, view, outside = self.items[name]
             assert_far_from_sentinel(want, name)
             assert_untouched(buf, outside, name)
-            assert_finite(view, name)
+            if view.dtype.is_floating_point:
+                assert_finite(view, name)
             assert_same_bits(view, want, name)
+
+
+class Launch:
+    """The tensors of one launch on ``device``: plain (guard=False) or poisoned inputs / guarded outputs / scratch workspaces
+    (guard=True)."""
+
+    def __init__(self, guard, device):
+        self.guard, self.device, self.g, self.outs = guard, device, (Guards(device) if guard else None), {}
+
+    def vec(self, t):
+        """A small contiguous parameter tensor (bias, LayerNorm weight, A, taps) with 4 x its last axis of NaN in front and behind."""
+        return None if t is None else (poisoned(t, rows=4) if self.guard else t)
+
+    def rows(self, t, rows=ROW_TILE):
+        """A contiguous (rows, D) tensor with ``rows`` NaN rows in front and behind."""
+        return None if t is None else (poisoned(t, rows=rows) if self.guard else t.clone())
+
+    def flat(self, t, rows):
+        """A contiguous input of any rank with ``rows`` x its last axis of NaN in front and behind."""
+        return None if t is None else (poisoned(t, rows=rows, contiguous=True) if self.guard else t.clone())
+
+    def cols(self, t, dead=None, align=16, rows=TIME_TILE, left=LEFT, right=RIGHT):
+        """A (batch, seqlen, width) or (rows, width) input inside NaN columns / rows / utterances; ``dead``: a column range the kernel
+        must not read."""
+        v = poisoned(t, align=align, rows=rows, left=left, right=right) if self.guard else t.clone()
+        if dead is not None and self.guard:
+            v[..., dead[0]:dead[1]] = float("nan")
+        return v
+
+    def out(self, name, shape, dtype, fill=None, **kw):
+        """An output: zeros (plain) or a sentinel-guarded view; ``fill``: initial content of both (an aliased input, or 0 where the
+        kernel need not write every element)."""
+        t = self.g.out(name, shape, dtype, **kw) if self.guard else torch.zeros(shape, dtype=dtype, device=self.device)
+        if fill is not None:
+            t.copy_(fill) if torch.is_tensor(fill) else t.fill_(fill)
+        self.outs[name] = t
+        return t
+
+    def scratch(self, name, numel, dtype=torch.float32, pad=4096):
+        """A workspace: uninitialised (plain) or NaN inside sentinels."""
+        return self.g.scratch(name, numel, dtype, pad) if self.guard else torch.empty((numel,), dtype=dtype, device=self.device)
+
+
+def two_step(run, device):
+    """run(Launch) launches the kernel on the Launch's tensors.  -> the plain launch's outputs by name."""
+    plain, guard = Launch(False, device), Launch(True, device)
+    run(plain)
+    run(guard)
+    if torch.device(device).type == "cuda":
+        torch.cuda.synchronize()
+    guard.g.check(plain.outs)
+    return plain.outs

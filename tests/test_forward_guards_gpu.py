@@ -39,57 +39,14 @@ def dev(t):
     return None if t is None else t.to(DEV)
 
 
-def pvec(t):
-    """A small contiguous parameter tensor (bias, LayerNorm weight, A, taps) with 4 x its last axis of NaN in front and behind."""
-    return G.poisoned(t, rows=4)
-
-
-def prow(t):
-    """A contiguous (rows, D) tensor with 64 NaN rows in front and behind."""
-    return G.poisoned(t, rows=RT)
-
-
-class Launch:
-    """The tensors of one launch: plain (guard=False) or poisoned inputs / guarded outputs (guard=True)."""
-
-    def __init__(self, guard):
-        self.guard, self.g, self.outs = guard, (G.Guards(DEV) if guard else None), {}
-
-    def vec(self, t):
-        return None if t is None else (pvec(t) if self.guard else t)
-
-    def rows(self, t):
-        return None if t is None else (prow(t) if self.guard else t.clone())
-
-    def flat(self, t, rows):
-        """A contiguous input of any rank with ``rows`` x its last axis of NaN in front and behind."""
-        return None if t is None else (G.poisoned(t, rows=rows, contiguous=True) if self.guard else t.clone())
-
-    def cols(self, t, dead=None, align=16):
-        """A (batch, seqlen, width) input inside NaN columns / rows / utterances; ``dead``: a column range the kernel must not read."""
-        v = G.poisoned(t, align=align, **COLS) if self.guard else t.clone()
-        if dead is not None and self.guard:
-            v[:, :, dead[0]:dead[1]] = NAN
-        return v
-
-    def out(self, name, shape, dtype, fill=None, **kw):
-        """An output: zeros (plain) or a sentinel-guarded view; ``fill``: initial content of both (an aliased input, or 0 where the
-        kernel need not write every element)."""
-        t = self.g.out(name, shape, dtype, **kw) if self.guard else torch.zeros(shape, dtype=dtype, device=DEV)
-        if fill is not None:
-            t.copy_(fill) if torch.is_tensor(fill) else t.fill_(fill)
-        self.outs[name] = t
-        return t
+def Launch(guard):
+    """guard_bands.Launch on the GPU: plain (guard=False) or poisoned inputs / guarded outputs (guard=True)."""
+    return G.Launch(guard, DEV)
 
 
 def two_step(run):
     """run(Launch) launches the kernel on the Launch's tensors.  -> the plain launch's outputs by name."""
-    plain, guarded = Launch(False), Launch(True)
-    run(plain)
-    run(guarded)
-    torch.cuda.synchronize()
-    guarded.g.check(plain.outs)
-    return plain.outs
+    return G.two_step(run, DEV)
 
 
 # ------------------------------------------------------------------------------------------------------------------------

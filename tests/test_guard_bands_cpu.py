@@ -158,3 +158,147 @@ def test_reference_near_the_sentinel_is_refused():
     with pytest.raises(AssertionError, match="ref_out: reference not finite"):
         G.assert_far_from_sentinel(torch.tensor([1.0, float("inf")]), "ref_out")
     G.assert_far_from_sentinel(torch.tensor([1.0, -300.0]), "ref_out")
+
+
+# what the training kernels add: workspaces, the uint8 mask, 2-D column slices --------------------------------------------------
+TILE = 4                                                                      # rows per "workgroup" of the fake column-sum kernels
+
+
+def k_colsum(inp, ws, out, fold_extra=0, skip_last_store=False, ws_overrun=False):
+    """out[c] = sum over rows of inp[:, c] as per-workgroup partial rows in ``ws`` + a fixed-order fold.  ``fold_extra``: the fold
+    reads that many rows more than there are workgroups; ``skip_last_store``: the last workgroup exits without storing its row;
+    ``ws_overrun``: one float is stored past the workspace."""
+    r, d = inp.shape
+    nwg = (r + TILE - 1) // TILE
+    part = ws[:nwg * d].view(nwg, d)
+    for w in range(nwg):
+        if not (skip_last_store and w == nwg - 1):
+            part[w] = inp[w * TILE:(w + 1) * TILE].float().sum(0)
+    if ws_overrun:
+        _reach(ws, (ws.numel() + 1,))[ws.numel()] = 1.0
+    out.copy_(_reach(ws, ((nwg + fold_extra) * d,)).view(nwg + fold_extra, d).sum(0))
+
+
+def _colsum_case(rows=9, d=8, ws_rows=None, **fault):
+    """The two-step protocol on k_colsum: the plain launch on a workspace that a previous launch left full of correct partials (what
+    the caching allocator hands back), the guarded one on a scratch."""
+    inp = torch.randn(rows, d)
+    nwg = (rows + TILE - 1) // TILE
+    nws = (ws_rows or nwg) * d
+    stale = torch.empty(nws + d)
+    k_colsum(inp, stale[:nws], torch.empty(d))                               # the "first run" of a run-twice determinism check
+    stale[nws:] = 0.0
+
+    def run(L):
+        ws = L.scratch("workspace", nws, pad=2 * d) if L.guard else stale[:nws]
+        k_colsum(L.rows(inp, rows=TILE), ws, L.out("dbias", (d,), torch.float32, rows=TILE), **fault)
+    return run, inp
+
+
+def test_scratch_geometry():
+    buf, view, outside = G.scratch(24, torch.float32, CPU, pad=8)
+    assert buf.numel() == 40 and view.numel() == 24 and view.data_ptr() % 16 == 0 and int(outside.sum()) == 16
+    assert bool(torch.isnan(view).all()) and bool((buf[:8] == G.SENTINEL).all()) and bool((buf[32:] == G.SENTINEL).all())
+    G.assert_untouched(buf, outside, "fresh")
+    view.fill_(3.0)                                                          # the inside is the kernel's own
+    G.assert_untouched(buf, outside, "written inside")
+
+
+def test_fold_and_workspace_kernels():
+    run, inp = _colsum_case()
+    outs = G.two_step(run, CPU)
+    folded = lambda t: torch.stack([t[:4].sum(0), t[4:8].sum(0), t[8:].sum(0)]).sum(0)
+    assert torch.equal(outs["dbias"], folded(inp))
+    # a fold that reads one partial row too many, in a workspace with room for it (cm_layernorm_bwd's holds 512 rows whatever the grid):
+    # the stale row is zero in the plain launch, NaN in the scratch
+    run, _ = _colsum_case(ws_rows=4, fold_extra=1)
+    with pytest.raises(AssertionError, match=r"dbias: 8 of 8 element\(s\) not finite"):
+        G.two_step(run, CPU)
+    # ... and in a workspace of exactly the sizing function's rows: the row behind it is the sentinel band
+    run, _ = _colsum_case(fold_extra=1)
+    with pytest.raises(AssertionError, match=r"dbias: 8 of 8 element\(s\) differ from the plain launch"):
+        G.two_step(run, CPU)
+    # a workgroup that exits without storing: the recycled workspace of the plain launch still holds the previous launch's row
+    run, inp = _colsum_case(skip_last_store=True)
+    plain = G.Launch(False, CPU)
+    run(plain)
+    assert torch.equal(plain.outs["dbias"], folded(inp)), "the recycled workspace hides it"
+    with pytest.raises(AssertionError, match=r"dbias: 8 of 8 element\(s\) not finite"):
+        G.two_step(run, CPU)
+    # a store one float past the workspace
+    run, _ = _colsum_case(ws_overrun=True)
+    with pytest.raises(AssertionError, match=r"workspace: 1 element\(s\) written outside the view"):
+        G.two_step(run, CPU)
+
+
+def k_mask(inp, mask, y, one_past=False):
+    """y = inp where kept; the keep decisions go to ``mask`` as bytes.  ``one_past``: one byte more is stored."""
+    keep = inp > 0
+    mask.copy_(keep.to(torch.uint8))
+    y.copy_(inp * keep)
+    if one_past:
+        _reach(mask, (mask.shape[0] + 1, mask.shape[1]))[mask.shape[0], 0] = 1
+
+
+def test_integer_sentinel_and_mask_kernels():
+    buf, view, outside = G.guarded((5, 8), torch.uint8, CPU, rows=16)
+    assert bool((buf == G.INT_SENTINEL).all()) and G.INT_SENTINEL not in (0, 1) and int(outside.sum()) == 2 * 16 * 8
+    G.assert_untouched(buf, outside, "fresh")
+    inp = torch.randn(5, 8)
+
+    def make(one_past):
+        def run(L):
+            k_mask(L.rows(inp, rows=16), L.out("mask", (5, 8), torch.uint8, rows=16), L.out("y", (5, 8), torch.float32, rows=16), one_past)
+        return run
+    outs = G.two_step(make(False), CPU)
+    assert torch.equal(outs["mask"].bool(), inp > 0)
+    faulty = G.Launch(True, CPU)
+    make(True)(faulty)
+    with pytest.raises(AssertionError, match=r"mask: 1 element\(s\) written outside the view"):
+        faulty.g.check(outs)
+    with pytest.raises(AssertionError, match="mask: reference holds the integer sentinel"):
+        G.assert_far_from_sentinel(torch.tensor([0, 1, G.INT_SENTINEL], dtype=torch.uint8), "mask")
+    g = G.Guards(CPU)
+    g.out("mask", (5, 8), torch.uint8, rows=16).fill_(1)
+    with pytest.raises(AssertionError, match=r"mask: \d+ of 40 element\(s\) differ from the plain launch"):
+        g.check({"mask": (inp > 0).to(torch.uint8)})
+
+
+def k_atb(a, b, out, extra_col=False, extra_row=False):
+    """out = a^T b of (rows, m) / (rows, n) operands addressed through their row strides.  ``extra_col``: a's column m is read into
+    out's last row; ``extra_row``: row ``rows`` of both operands is contracted as well."""
+    r, m = a.shape
+    k = r + 1 if extra_row else r
+    aa, bb = _reach(a, (k, m + 1 if extra_col else m)).float(), _reach(b, (k, b.shape[1])).float()
+    res = aa[:, :m].t() @ bb
+    if extra_col:
+        res[m - 1] += aa[:, m] @ bb
+    out.copy_(res)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_two_dim_column_slices(dtype):
+    kw = dict(rows=G.ROW_TILE, left=G.LEFT, right=G.RIGHT)
+    buf, view, outside = G.guarded((5, 24), dtype, CPU, **kw)
+    assert buf.shape == (3, 5 + G.ROW_TILE, G.LEFT + 24 + G.RIGHT) and view.shape == (5, 24) and view.stride() == (48, 1)
+    assert view.data_ptr() % 16 == 0 and int(outside.sum()) == buf.numel() - 5 * 24
+    assert not bool(outside[1, :5, G.LEFT:G.LEFT + 24].any()) and bool(outside[0].all()) and bool(outside[2].all()) and bool(outside[1, 5:].all())
+    a, b = torch.randn(5, 24).to(dtype), torch.randn(5, 16).to(dtype)
+    pa = G.poisoned(a, **kw)
+    assert torch.equal(pa, a) and pa.stride() == (48, 1)
+    around = _reach(pa, (7, 26), -pa.stride(0) - 1).clone()                   # one row and one column on every side
+    around[1:6, 1:25] = float("nan")
+    assert bool(torch.isnan(around).all())
+
+    def make(**fault):
+        def run(L):
+            k_atb(L.cols(a, rows=G.ROW_TILE), L.cols(b, rows=G.ROW_TILE), L.out("dw", (24, 16), torch.float32), **fault)
+        return run
+    outs = G.two_step(make(), CPU)
+    assert torch.equal(outs["dw"], a.float().t() @ b.float())
+    # in a dense slice of a wider activation the column beside it and the row behind a chunk are finite data: only the poisoned views show
+    for fault, count in ((dict(extra_col=True), 16), (dict(extra_row=True), 384)):
+        faulty = G.Launch(True, CPU)
+        make(**fault)(faulty)
+        with pytest.raises(AssertionError, match=rf"dw: {count} of 384 element\(s\) not finite"):
+            faulty.g.check(outs)
