@@ -22,6 +22,17 @@
  *     that x / z (and dx / dz) may be the two halves of one xz tensor (:180, :249-256);
  *   - fp32 reduction outputs (dA, dD, ddelta_bias, dB, dC, dweight, dbias) are ACCUMULATED
  *     into: the caller zero-initialises them (or passes running sums on purpose).
+ *
+ * This file is also the source of the Python binding: mamba_asr_amd/_native.py parses it at import and derives every
+ * ctypes structure, every prototype and every CM_* constant from it (there is no second copy to keep in step), and it
+ * refuses a declaration it does not understand.  So the header stays inside this subset of C:
+ *   - conditionals: the include guard, the __cplusplus block and #ifdef CM_ABLATE ... #endif only;
+ *   - `typedef struct cm_x { ... } cm_x;` with fields of type int, int32_t, uint32_t, int64_t, uint64_t, float, double, an
+ *     earlier struct by value, or a pointer; several declarators per declaration and [N] arrays are fine; no bit-fields,
+ *     unions or function pointers;
+ *   - `typedef enum { A = 0, ... } name;` and `#define CM_X <integer>` (parentheses, sign, hex, u / l suffixes);
+ *   - prototypes returning int, int32_t, int64_t or const char *, taking those integer types and pointers.
+ * tests/test_abi.py checks the derived layouts against the C compiler's sizeof / offsetof.
  */
 #ifndef CONMAMBA_HIP_H
 #define CONMAMBA_HIP_H

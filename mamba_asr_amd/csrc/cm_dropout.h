@@ -9,6 +9,7 @@
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
+#include "../../include/conmamba_hip.h"      // CM_SEED_EPOCH_MUL
 
 __device__ __forceinline__ uint32_t cm_hash32(uint32_t x) {           // murmur3 finaliser
     x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
@@ -24,7 +25,7 @@ __host__ __device__ __forceinline__ float cm_drop_scale(float p) {
 // effective seed of a launch: the caller's seed, plus (optionally) a device word read when the kernel runs, so that a captured
 // hipGraph draws fresh decisions at every replay (cm_ffn_elem_args.seed_epoch); forward and backward of one replay see the same word
 __device__ __forceinline__ uint64_t cm_drop_seed(uint64_t seed, const uint64_t *epoch) {
-    return epoch ? seed + *epoch * 0x9E3779B97F4A7C15ull : seed;
+    return epoch ? seed + *epoch * CM_SEED_EPOCH_MUL : seed;
 }
 __device__ __forceinline__ uint32_t cm_drop_base(uint64_t seed, uint64_t group) {
     return cm_hash32((uint32_t)group ^ (uint32_t)seed) + (uint32_t)(group >> 32) * 0x85EBCA6Bu + (uint32_t)(seed >> 32);

@@ -603,7 +603,7 @@ def draw_seed() -> int:
 # (cm_ffn_elem_args.seed_epoch), so a graph whose first node increments the word draws new decisions per replay while the
 # forward and backward kernels of one replay still agree.  None (default): the host seed alone.  graphs.GraphedTrainStep sets it.
 SEED_EPOCH = None
-SEED_EPOCH_MUL = 0x9E3779B97F4A7C15
+SEED_EPOCH_MUL = N.CM_SEED_EPOCH_MUL
 
 
 def _seed_epoch_ptr():

@@ -1,8 +1,10 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads and exports every symbol
 include/conmamba_hip.h declares; argument validation works without a GPU."""
 import ctypes as C
+import keyword
 import os
 import re
+import shutil
 import subprocess
 
 import pytest
@@ -33,6 +35,150 @@ def test_header_symbols_exported(native):
     # the product library carries no process-global switch (ablation variants live in the CM_ABLATE build only)
     for name in ("cm_debug_set", "cm_debug_get", "cm_scan_set_split"):
         assert not hasattr(handle, name), f"{name} must not be exported by the product library"
+
+
+def _host_cc():
+    """$CC, else cc, else the clang that ships beside hipcc: the first that runs."""
+    hipcc = shutil.which("hipcc") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+    beside = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "llvm", "bin", "clang")
+    tried = [c for c in (os.environ.get("CC"), "cc", beside) if c]
+    for cc in tried:
+        try:
+            if subprocess.run(cc.split() + ["--version"], capture_output=True).returncode == 0:
+                return cc.split()
+        except OSError:
+            pass
+    pytest.fail(f"no host C compiler runs (tried {tried}): the library cannot be built here either")
+
+
+def test_struct_layouts_match_the_compiler(native, tmp_path):
+    """Every derived ctypes class against the C compiler's own sizeof / offsetof of the real header: the size of every
+    struct, the offset and size of every field (pad words included)."""
+    hdr = open(os.path.join(ROOT, "include", "conmamba_hip.h")).read()
+    structs = native.HEADER.structs
+    assert set(structs) == set(re.findall(r"^typedef\s+struct\s+(\w+)\s*\{", hdr, re.M)) and len(structs) >= 38
+    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "conmamba_hip.h"', 'int main(void) {']
+    want = []
+    for cname, cls in structs.items():
+        src.append(f'    printf("{cname} %zu\\n", sizeof({cname}));')
+        want.append(f"{cname} {C.sizeof(cls)}")
+        for field, _ in cls._fields_:
+            cfield = field[:-1] if field.endswith("_") and keyword.iskeyword(field[:-1]) else field      # in_ is C's `in`
+            src.append(f'    printf("{cname}.{cfield} %zu %zu\\n", offsetof({cname}, {cfield}), sizeof((({cname} *)0)->{cfield}));')
+            want.append(f"{cname}.{cfield} {getattr(cls, field).offset} {getattr(cls, field).size}")
+    src += ['    return 0;', '}', '']
+    (tmp_path / "probe.c").write_text("\n".join(src))
+    subprocess.check_call(_host_cc() + ["-I", os.path.join(ROOT, "include"), "-o", str(tmp_path / "probe"), str(tmp_path / "probe.c")])
+    got = subprocess.check_output([str(tmp_path / "probe")], text=True).splitlines()
+    assert len(got) == len(want) > 600
+    assert [g for g, w in zip(got, want) if g != w] == [], "compiler (left in the list) and ctypes disagree"
+    assert native.LayerNormArgs is structs["cm_layernorm_args"] and native.ScanClDir is structs["cm_scan_cl_dir"]
+    assert hasattr(native.GluDwconvArgs, "in_") and not hasattr(native.GluDwconvArgs, "in")
+    assert native.ABI_VERSION == native.CM_ABI_VERSION == int(re.search(r"#define CM_ABI_VERSION (\d+)", hdr).group(1))
+    assert native.CM_SEED_EPOCH_MUL == 0x9E3779B97F4A7C15 and native.CM_EALIGN == -3 and native.CM_BF16 == 1
+
+
+@pytest.mark.parametrize("snippet, quoted", [
+    ("typedef struct cm_t { int32_t a; unsigned short x; } cm_t;", "unsigned short x"),              # unknown base type
+    ("typedef struct cm_t { int32_t a; size_t n; } cm_t;", "size_t n"),
+    ("typedef struct cm_t { const foo_t *p; } cm_t;", "foo_t *p"),                                   # unknown pointee
+    ("typedef struct cm_t { int32_t flag : 1; int32_t rest : 31; } cm_t;", "int32_t flag : 1"),      # bit-field
+    ("typedef struct cm_t { int32_t kind; union { int32_t i; float f; } u; } cm_t;", "union {"),     # union member
+    ("typedef union cm_u { int32_t i; float f; } cm_u;", "typedef union cm_u"),
+    ("typedef struct cm_t { void *ctx; int (*callback)(void *); } cm_t;", "int (*callback)(void *)"),   # function pointer
+    ("typedef struct cm_t { int32_t a; } cm_other;", "cm_other"),
+    ("typedef struct cm_t { void * const p; } cm_t;", "void * const p"),
+    ("#if defined(CM_WIDE)\ntypedef struct cm_t { int64_t a; } cm_t;\n#endif", "#if defined(CM_WIDE)"),     # stray conditional
+    ("#ifdef CM_OTHER\nint cm_f(void);\n#endif", "#ifdef CM_OTHER"),
+    ("#ifdef CM_ABLATE\n#else\nint cm_f(void);\n#endif", "#else"),
+    ("#define CM_X (1 << 4)", "#define CM_X (1 << 4)"),
+    ("#define CM_MAX(a, b) ((a) > (b) ? (a) : (b))", "#define CM_MAX(a, b)"),
+    ("typedef enum { CM_A = 0, CM_B } cm_e;", "CM_B"),
+    ("float cm_f(int32_t n);", "float cm_f(int32_t n)"),                                             # return type outside the list
+    ("int cm_f(size_t n);", "int cm_f(size_t n)"),
+    ("int cm_f(int32_t n)", "int cm_f(int32_t n)"),                                                  # no terminator
+    ("int cm_f(void);\nint cm_f(void);", "int cm_f(void)"),
+    ("static const int cm_k = 3;", "static const int cm_k = 3"),
+])
+def test_parser_refuses_what_it_does_not_understand(native, snippet, quoted):
+    with pytest.raises(ValueError, match=re.escape(quoted)):
+        native.parse_header(snippet)
+
+
+def test_parser_reads_the_supported_forms(native):
+    h = native.parse_header("""
+        /* a block comment; with, separators */
+        #ifndef CM_T_H
+        #define CM_T_H
+        #include <stdint.h>
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        #define CM_T_VERSION 3
+        #define CM_T_NEG   (-2)   // trailing; comment, too
+        #define CM_T_BIG 0x9E3779B97F4A7C15ull
+        typedef enum { CM_T_A = 0, CM_T_B = 0x10 } cm_t_kind;
+        typedef struct cm_t_dir {
+            const float *w;       /* a comment; holding , and ; */
+            int64_t bs, ts;
+            int32_t rank;         // one; more, of them
+        } cm_t_dir;
+        typedef struct cm_t_args {
+            int32_t n;
+            cm_t_dir dir[2];
+            uint64_t hash_base[2], hash_sep;
+            double scale;
+            const void *in;
+            float *a, *b;
+            uint8_t *mask;
+            cm_t_dir *one;
+            int last;
+        } cm_t_args;
+        int cm_t_run(const cm_t_args *args);
+        int64_t cm_t_pack(const void *w /* (rows, cols); packed */, int32_t rows,
+                          int32_t cols,   // cols, then the stream
+                          void *stream);
+        const char *cm_t_error(void);
+        #ifdef CM_ABLATE
+        int cm_t_debug(int which);
+        #endif
+        #ifdef __cplusplus
+        }
+        #endif
+        #endif
+        """)
+    assert h.consts == {"CM_T_VERSION": 3, "CM_T_NEG": -2, "CM_T_BIG": 0x9E3779B97F4A7C15, "CM_T_A": 0, "CM_T_B": 16}
+    assert list(h.structs) == ["cm_t_dir", "cm_t_args"]
+    D, A = h.structs["cm_t_dir"], h.structs["cm_t_args"]
+    assert (D.__name__, A.__name__) == ("TDir", "TArgs")
+
+    def layout(cls):
+        return [(n, getattr(cls, n).offset, getattr(cls, n).size) for n, _ in cls._fields_]
+    assert layout(D) == [("w", 0, 8), ("bs", 8, 8), ("ts", 16, 8), ("rank", 24, 4)] and C.sizeof(D) == 32
+    assert layout(A) == [("n", 0, 4), ("dir", 8, 64), ("hash_base", 72, 16), ("hash_sep", 88, 8), ("scale", 96, 8), ("in_", 104, 8),
+                         ("a", 112, 8), ("b", 120, 8), ("mask", 128, 8), ("one", 136, 8), ("last", 144, 4)] and C.sizeof(A) == 152
+    t = dict(A._fields_)
+    assert t["dir"] is D * 2 and t["hash_base"] is C.c_uint64 * 2 and t["scale"] is C.c_double and t["last"] is C.c_int
+    assert all(t[k] is C.c_void_p for k in ("in_", "a", "b", "mask", "one"))
+    assert h.protos == {"cm_t_run": (C.c_int, [C.POINTER(A)]),
+                        "cm_t_pack": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+                        "cm_t_error": (C.c_char_p, [])}
+    assert h.ablate_protos == {"cm_t_debug": (C.c_int, [C.c_int])}
+
+
+def test_store_to_a_name_that_is_no_field_raises(native):
+    a = native.ScanFwdArgs()
+    a.seqlen = 5                                    # a field: stored
+    assert a.seqlen == 5
+    with pytest.raises(AttributeError):
+        a.no_such_field = 1
+    s = native.ScanClArgs()
+    s.dir[0].xdbl_ts = 7
+    assert s.dir[0].xdbl_ts == 7
+    with pytest.raises(AttributeError):
+        s.dir[0].xdlb_ts = 7                        # the typo that used to leave the C field zero
+    for cls in native.HEADER.structs.values():
+        assert cls.__slots__ == () and not hasattr(cls(), "__dict__")
 
 
 def test_abi_version_and_chunks(native):
