@@ -435,6 +435,53 @@ typedef struct cm_ctc_beam_args {
 int64_t cm_ctc_beam_workspace_bytes(const cm_ctc_beam_args *args);
 int cm_ctc_beam_search(const cm_ctc_beam_args *args);
 
+/* The same search carried across streaming chunks (csrc/ctc_beam_stream.hip): one call consumes the next chunk of
+ * every stream of a batch from a caller-owned state and runs the frame body of cm_ctc_beam_search on it (csrc/ctc_beam_impl.h,
+ * shared), so after n frames in any chunking the hypotheses carry the bits cm_ctc_beam_search returns for lengths = n.
+ * State: one slab of cm_ctc_beam_stream_state_bytes(beam_size, max_frames) bytes per slot, state_stride_bytes apart (a multiple of
+ * 16, as the state pointer): a 16-byte header (live beams, processed frames, frames consumed, NaN frame + 1), the beam_size beams
+ * as a struct of arrays (80 bytes each) and the history (max_frames x beam_size int32, (parent << 16) | (token + 1)); plain memory
+ * without pointers -- copying a slab copies a stream.  An all-zero slab is a slot that was never reset.  The function returns 0
+ * outside beam_size in [1, 256], max_frames in [1, 0x7fff0000 / 256].
+ * Per call and slot b: reset[b] != 0 (reset may be NULL) starts the slot from the single initial beam; then chunk_len[b] (clamped
+ * to [0, T]) rows of log_probs[b] are consumed -- no row past chunk_len[b] - 1 is read; then emit[b] != 0 (emit may be NULL)
+ * writes the hypotheses as cm_ctc_beam_search does, tokens being (batch, topk, max_frames), without changing beams or history.  A
+ * slot that neither consumes, resets nor emits returns at once: its output rows and status[b] are left unwritten.  T == 0 is a
+ * reset / emit-only call (log_probs may then be NULL).
+ * status[b]: -1 ok;  f >= 0: the first frame holding a NaN, counted from the reset -- stored in the state until the next reset, the
+ * slot consumes nothing more and an emit gives num_hyps[b] = 0;  -2: the chunk was refused and the state left unchanged, because
+ * it would take the slot past max_frames or because the slot was never reset (an emit then still returns what the state holds,
+ * nothing for a slot never reset).
+ * workspace: cm_ctc_beam_stream_workspace_bytes() bytes per call, the candidate sorts that outgrow LDS (0, and workspace may be
+ * NULL, when beam_size x V <= 1024).  Arguments are validated on the host before any launch. */
+typedef struct cm_ctc_beam_stream_args {
+    int32_t batch, T, V, dtype;               /* batch: slots; T: rows per slot in this chunk; dtype CM_F32 or CM_BF16; V <= 4096 */
+    int64_t lp_bs, lp_ts;                     /* log_probs element strides of slot and time                     */
+    const void *log_probs;                    /* (batch, T, V)                                                  */
+    const int32_t *chunk_len;                 /* (batch) rows of this chunk to consume; 0: idle                 */
+    const int32_t *reset, *emit;              /* (batch) or NULL                                                */
+    const int32_t *tok_class;                 /* (V)                                                            */
+    const uint64_t *tok_hash, *tok_pow;       /* (V, 2)                                                         */
+    uint64_t hash_base[2], hash_sep;
+    int32_t blank, beam_size, topk, prune_history;   /* beam_size <= 256                                        */
+    double beam_prune_logp, token_prune_min_logp, blank_skip_threshold;
+    double blank_skip_log;                    /* set by the library                                             */
+    void *state;                              /* batch slabs                                                    */
+    int64_t state_stride_bytes;
+    int32_t max_frames, reserved0;            /* frames per utterance (between two resets)                      */
+    int32_t *tokens;                          /* (batch, topk, max_frames)                                      */
+    int32_t *token_len;                       /* (batch, topk)                                                  */
+    double *scores;                           /* (batch, topk)                                                  */
+    int32_t *num_hyps, *status;               /* (batch)                                                        */
+    void *workspace;
+    int64_t workspace_bytes;
+    void *stream;
+} cm_ctc_beam_stream_args;
+
+int64_t cm_ctc_beam_stream_state_bytes(int32_t beam_size, int32_t max_frames);
+int64_t cm_ctc_beam_stream_workspace_bytes(const cm_ctc_beam_stream_args *args);
+int cm_ctc_beam_stream(const cm_ctc_beam_stream_args *args);
+
 /* CTC prefix scores for joint CTC/attention S2S decoding (csrc/ctc_prefix.hip; what speechbrain's CTCScorer adds to the decoder's
  * log-probabilities, the reference S2S recipes' `ctc_weight_decode`; DESIGN.md §4d holds the contract).  logp (U, T, V) fp32
  * contiguous CTC log-posteriors; n_u[u] frames of utterance u to use (clamped to [0, T] in the kernels).  Hypothesis row r belongs

@@ -123,6 +123,11 @@ class ConMambaASR(nn.Module):
         in time look at the future of the utterance."""
         return self.Transformer.encode_streaming(src, context)
 
+    def log_probs_streaming(self, src, context):
+        """encode_streaming's chunk through the CTC head: log_softmax(ctc_lin(encode_streaming(src, context))), (B, t, vocab) --
+        what ctc_decode.StreamingCTCBeamSearcher.step consumes."""
+        return torch.log_softmax(self.ctc_lin(self.encode_streaming(src, context)), dim=-1)
+
     def forward_ctc(self, wavs, wav_lens, epoch=0, augment=None, feats=None):
         """-> log-probabilities (B, T', vocab), train_CTC.py:296-302."""
         enc = self.encode(wavs, wav_lens, epoch, augment, feats=feats)

@@ -29,6 +29,11 @@ Choices recorded where speechbrain could not be checked: n_b = round(wav_lens[b]
 speechbrain may truncate); the exact blank-skip comparison; the loop order over selected tokens (speechbrain iterates a Python
 set: only ties and rounding can differ).  n_b = 0 gives the single hypothesis "" with score 0.  NaN in a decoded frame raises
 ValueError naming the utterance.
+
+Streaming.  StreamingCTCBeamSearcher carries the same search across chunks (ops.ctc_beam_stream, csrc/ctc_beam_stream.hip): the
+beams and the backtracking history live in a device slab per stream, a step is one launch that reads nothing back, and
+hypotheses() after n frames is by definition what the search above returns for n_b = n -- the kernels share the frame body, so the
+score bits agree as well.
 """
 from __future__ import annotations
 
@@ -157,15 +162,19 @@ class CTCBeamSearcher:
             log_probs, lengths, tc, th, tp, HASH_BASE, HASH_SEP, blank=self.blank_index, beam_size=self.beam_size,
             topk=self.topk, prune_history=self.prune_history, beam_prune_logp=self.beam_prune_logp,
             token_prune_min_logp=self.token_prune_min_logp, blank_skip_threshold=self.blank_skip_threshold)
+        return self._hypotheses(tokens, token_len, scores, num_hyps, bad, range(b), "utterance")
+
+    def _hypotheses(self, tokens, token_len, scores, num_hyps, bad, rows, what) -> List[List[CTCHypothesis]]:
+        """The kernel's outputs of the named rows, read to the host: NaN check, then one list of hypotheses per row."""
         bad, num_hyps = bad.cpu().tolist(), num_hyps.cpu().tolist()
-        for u, f in enumerate(bad):
-            if f >= 0:
-                raise ValueError(f"CTCBeamSearcher: log_probs of utterance {u} hold NaN at frame {f}")
+        for u in rows:
+            if bad[u] >= 0:
+                raise ValueError(f"{type(self).__name__}: log_probs of {what} {u} hold NaN at frame {bad[u]}")
         token_len, scores = token_len.cpu().tolist(), scores.cpu().tolist()
-        lmax = max((token_len[u][h] for u in range(b) for h in range(num_hyps[u])), default=0)
+        lmax = max((token_len[u][h] for u in rows for h in range(num_hyps[u])), default=0)
         tok = tokens[:, :, :lmax].cpu().tolist()
         out = []
-        for u in range(b):
+        for u in rows:
             hyps = []
             for h in range(num_hyps[u]):
                 s = scores[u][h]
@@ -176,3 +185,124 @@ class CTCBeamSearcher:
     def decode_beams(self, log_probs, wav_lens=None, lm_start_state=None):
         """speechbrain's name for the same call."""
         return self(log_probs, wav_lens)
+
+
+class CTCStreamState:
+    """The streams of one StreamingCTCBeamSearcher.make_state call: the device slab (slots, state bytes) uint8 -- plain memory, a
+    row copied is a stream copied -- and per slot the host's upper bound of frames fed since the last reset (None: never reset)."""
+
+    def __init__(self, searcher: "StreamingCTCBeamSearcher", slab: torch.Tensor):
+        self._searcher, self.slab = searcher, slab
+        self.fed: List[Optional[int]] = [None] * slab.shape[0]
+
+    @property
+    def batch_size(self) -> int:
+        return self.slab.shape[0]
+
+    def reset(self, rows: Optional[Sequence[int]] = None) -> None:
+        """Start a new utterance in the named slots (default all), now: one launch that consumes nothing."""
+        rows = self._searcher._rows(self, rows)
+        self._searcher._launch(self, None, [0] * self.batch_size, reset=rows)
+        for u in rows:
+            self.fed[u] = 0
+
+
+class StreamingCTCBeamSearcher(CTCBeamSearcher):
+    """CTCBeamSearcher carried across chunks (cm_ctc_beam_stream): the constructor keywords of CTCBeamSearcher plus
+    max_frames, the frames one utterance (reset to reset) may hold -- 1500 is a minute of 40-ms encoder frames.  After n frames in
+    any chunking, hypotheses() returns what CTCBeamSearcher returns for those n frames, score bits included.
+
+        state = searcher.make_state(batch_size, device); state.reset()
+        searcher.step(log_probs_chunk, state)           # per chunk: one launch, nothing read back
+        searcher.hypotheses(state)                      # whenever wanted, in mid-stream too: the beams are left as they are
+    """
+
+    def __init__(self, *args, max_frames: int = 1500, **kw):
+        super().__init__(*args, **kw)
+        if not 1 <= max_frames <= 0x7fff0000 // 256:
+            raise ValueError(f"StreamingCTCBeamSearcher: max_frames {max_frames} not in [1, {0x7fff0000 // 256}]")
+        self.max_frames = int(max_frames)
+        self._dev_lengths = {}
+
+    def make_state(self, batch_size: int, device) -> CTCStreamState:
+        """``batch_size`` slots that were never reset: reset them (state.reset, or step's ``reset``) before their first chunk."""
+        return CTCStreamState(self, ops.ctc_beam_stream_state(batch_size, self.beam_size, self.max_frames, device))
+
+    def _rows(self, state, rows) -> List[int]:
+        rows = list(range(state.batch_size)) if rows is None else [int(u) for u in rows]
+        for u in rows:
+            if not 0 <= u < state.batch_size:
+                raise ValueError(f"StreamingCTCBeamSearcher: slot {u} outside a state of {state.batch_size} slots")
+        return rows
+
+    def _flags(self, values: Sequence[int], device) -> torch.Tensor:
+        return torch.tensor(list(values), dtype=torch.int32).to(device)
+
+    def _constant(self, value: int, n: int, device) -> torch.Tensor:
+        """(n) int32 of ``value`` on the device, made once: a step without host lists uploads nothing."""
+        key = (str(device), n, value)
+        if key not in self._dev_lengths:
+            self._dev_lengths[key] = torch.full((n,), value, dtype=torch.int32, device=device)
+        return self._dev_lengths[key]
+
+    def _launch(self, state, log_probs, lengths, reset=None, emit=None):
+        dev, n = state.slab.device, state.batch_size
+        tc, th, tp = self._tables(dev)
+        same = len(set(lengths)) == 1
+        chunk_len = self._constant(lengths[0], n, dev) if same else self._flags(lengths, dev)
+
+        def mark(rows):
+            return self._flags([1 if u in rows else 0 for u in range(n)], dev) if rows else None
+        return ops.ctc_beam_stream(
+            log_probs, chunk_len, state.slab, self.max_frames, tc, th, tp, HASH_BASE, HASH_SEP, reset=mark(reset), emit=mark(emit),
+            blank=self.blank_index, beam_size=self.beam_size, topk=self.topk, prune_history=self.prune_history,
+            beam_prune_logp=self.beam_prune_logp, token_prune_min_logp=self.token_prune_min_logp,
+            blank_skip_threshold=self.blank_skip_threshold)
+
+    def step(self, log_probs: torch.Tensor, state: CTCStreamState, lengths: Optional[Sequence[int]] = None,
+             reset: Optional[Sequence[int]] = None) -> None:
+        """Feed the next chunk log_probs (B, t, V): slot b consumes its first lengths[b] rows (host list; default t; 0: idle).
+        ``reset``: host list of the slots that start a new utterance with this chunk.  One launch and nothing read from the
+        device; with neither list given nothing is uploaded either, so the call can be captured in a hipGraph with the encoder
+        step -- after one eager call of the same (B, t) on this searcher, which makes the cached device constants outside the
+        graph's memory pool (the host's frame count sees the capture once, not the replays: the device then refuses a chunk past max_frames on
+        its own, status -2).  Raises ValueError before launching when a slot was never reset or would pass max_frames."""
+        n = state.batch_size
+        if log_probs.dim() != 3 or log_probs.shape[0] != n or log_probs.shape[2] != len(self.vocab_list):
+            raise ValueError(f"StreamingCTCBeamSearcher: log_probs must be ({n}, t, {len(self.vocab_list)}), got {tuple(log_probs.shape)}")
+        t = log_probs.shape[1]
+        lengths = [t] * n if lengths is None else [int(x) for x in lengths]
+        if len(lengths) != n or any(not 0 <= x <= t for x in lengths):
+            raise ValueError(f"StreamingCTCBeamSearcher: lengths must be {n} frame counts in [0, {t}], got {lengths}")
+        reset = self._rows(state, reset) if reset is not None else []
+        fed = list(state.fed)
+        for u in reset:
+            fed[u] = 0
+        for u, x in enumerate(lengths):
+            if x and fed[u] is None:
+                raise ValueError(f"StreamingCTCBeamSearcher: slot {u} was never reset: pass reset=[{u}] with its first chunk, or call state.reset([{u}])")
+            if x and fed[u] + x > self.max_frames:
+                raise ValueError(f"StreamingCTCBeamSearcher: slot {u} would hold {fed[u] + x} frames, more than max_frames={self.max_frames}: "
+                                 "end-point the utterance and reset the slot")
+            if x:
+                fed[u] += x
+        if not log_probs.is_cuda or not state.slab.is_cuda:
+            raise RuntimeError("StreamingCTCBeamSearcher runs on the GPU only (got a CPU tensor): move log_probs and the state to the GPU")
+        if t and (reset or any(lengths)):
+            self._launch(state, log_probs, lengths, reset=reset)
+        elif reset:
+            self._launch(state, None, [0] * n, reset=reset)
+        state.fed = fed
+
+    def hypotheses(self, state: CTCStreamState, rows: Optional[Sequence[int]] = None) -> List[List[CTCHypothesis]]:
+        """The hypotheses of the named slots (default all) after the frames fed so far, one list per named slot in the order given:
+        an emit-only launch, then the one host read.  The beams stay as they are: callable any number of times, in mid-stream
+        and at the end.  A slot never reset has no hypotheses.  Raises ValueError naming the slot and the frame, counted from its
+        reset, when the slot met a NaN."""
+        rows = self._rows(state, rows)
+        if not state.slab.is_cuda:
+            raise RuntimeError("StreamingCTCBeamSearcher runs on the GPU only (got a CPU state)")
+        if not rows:
+            return []
+        tokens, token_len, scores, num_hyps, status = self._launch(state, None, [0] * state.batch_size, emit=rows)
+        return self._hypotheses(tokens, token_len, scores, num_hyps, status, rows, "slot")

@@ -785,6 +785,73 @@ def ctc_beam_search(log_probs, lengths, tok_class, tok_hash, tok_pow, hash_base,
     return tokens, token_len, scores, num_hyps, bad_frame
 
 
+def ctc_beam_stream_state(slots, beam_size, max_frames, device):
+    """The zeroed state of ``slots`` streamed CTC beam searches: (slots, cm_ctc_beam_stream_state_bytes(beam_size, max_frames)) uint8.
+    An all-zero slab is a slot that was never reset; a row is plain memory, so copying it copies the stream."""
+    nbytes = int(N.lib().cm_ctc_beam_stream_state_bytes(int(beam_size), int(max_frames)))
+    if nbytes <= 0 or slots < 1:
+        raise RuntimeError(f"ctc_beam_stream_state: slots {slots} < 1, beam_size {beam_size} not in [1, 256] or max_frames "
+                           f"{max_frames} not in [1, {0x7fff0000 // 256}]")
+    return torch.zeros((int(slots), nbytes), dtype=torch.uint8, device=device)
+
+
+def ctc_beam_stream(log_probs, chunk_len, state, max_frames, tok_class, tok_hash, tok_pow, hash_base, hash_sep, reset=None, emit=None,
+                    blank=0, beam_size=100, topk=1, prune_history=False, beam_prune_logp=-10.0, token_prune_min_logp=-5.0,
+                    blank_skip_threshold=1.0, bufs=None):
+    """The next chunk of every stream through the CTC beam search (cm_ctc_beam_stream): one launch, no host synchronisation.
+    log_probs (slots, t, V) fp32 / bf16 with unit vocabulary stride, or None for a reset / emit-only call; chunk_len (slots) int32
+    on the device, the rows each slot consumes; state (slots, >= state bytes) uint8 from ctc_beam_stream_state, updated in place;
+    reset / emit (slots) int32 device tensors or None; the token tables as for ctc_beam_search.
+    -> (tokens (slots, topk, max_frames) int32, token_len (slots, topk) int32, scores (slots, topk) fp64, num_hyps (slots) int32,
+    status (slots) int32).  Only the rows of slots that were active in this call are written (status), those of emitting slots
+    (the rest); everything else is uninitialised memory.  bufs: caller-placed "tokens", "token_len", "scores", "num_hyps",
+    "status" and "workspace" (uint8, cm_ctc_beam_stream_workspace_bytes)."""
+    _dev_check(log_probs, chunk_len, state, reset, emit, tok_class, tok_hash, tok_pow)
+    dev = state.device
+    slots = state.shape[0]
+    if state.dim() != 2 or state.dtype != torch.uint8 or state.stride(1) != 1:
+        raise RuntimeError("ctc_beam_stream: state must be the (slots, bytes) uint8 tensor of ctc_beam_stream_state (or row slices of it)")
+    for name, flag in (("chunk_len", chunk_len), ("reset", reset), ("emit", emit)):
+        if flag is not None and (flag.dtype != torch.int32 or tuple(flag.shape) != (slots,) or not flag.is_contiguous() or flag.device != dev):
+            raise RuntimeError(f"ctc_beam_stream: {name} must be a contiguous int32 tensor of shape ({slots},) on {dev}")
+    a = N.CtcBeamStreamArgs()
+    if log_probs is None:
+        t, v, lp = 0, int(tok_class.shape[0]), None
+        a.dtype = N.CM_F32
+    else:
+        if log_probs.dtype not in (torch.float32, torch.bfloat16):
+            log_probs = log_probs.float()
+        lp = log_probs.detach()
+        if lp.dim() != 3 or lp.shape[0] != slots or lp.device != dev:
+            raise RuntimeError(f"ctc_beam_stream: log_probs must be ({slots}, t, V) on {dev}, got {tuple(lp.shape)} on {lp.device}")
+        if lp.stride(2) != 1:
+            lp = lp.contiguous()
+        _, t, v = lp.shape
+        a.dtype, a.lp_bs, a.lp_ts = _DT[lp.dtype], lp.stride(0), lp.stride(1)
+    tc = tok_class.detach().to(device=dev, dtype=torch.int32).contiguous()
+    th = tok_hash.detach().to(device=dev, dtype=torch.int64).contiguous()
+    tp = tok_pow.detach().to(device=dev, dtype=torch.int64).contiguous()
+    a.batch, a.T, a.V = slots, t, v
+    a.log_probs, a.chunk_len, a.reset, a.emit = _ptr(lp), _ptr(chunk_len), _ptr(reset), _ptr(emit)
+    a.tok_class, a.tok_hash, a.tok_pow = _ptr(tc), _ptr(th), _ptr(tp)
+    a.hash_base[0], a.hash_base[1], a.hash_sep = int(hash_base[0]), int(hash_base[1]), int(hash_sep)
+    a.blank, a.beam_size, a.topk, a.prune_history = int(blank), int(beam_size), int(topk), int(bool(prune_history))
+    a.beam_prune_logp, a.token_prune_min_logp = float(beam_prune_logp), float(token_prune_min_logp)
+    a.blank_skip_threshold = float(blank_skip_threshold)
+    a.state, a.state_stride_bytes, a.max_frames = _ptr(state), state.stride(0), int(max_frames)
+    nws = int(N.lib().cm_ctc_beam_stream_workspace_bytes(ct.byref(a)))
+    take = _bufs(bufs, ("tokens", "token_len", "scores", "num_hyps", "status", "workspace"), "ctc_beam_stream")
+    tokens = take("tokens", (slots, topk, int(max_frames)), torch.int32, dev)
+    token_len = take("token_len", (slots, topk), torch.int32, dev)
+    scores = take("scores", (slots, topk), torch.float64, dev)
+    num_hyps, status = take("num_hyps", (slots,), torch.int32, dev), take("status", (slots,), torch.int32, dev)
+    ws = take("workspace", (nws,), torch.uint8, dev) if nws else None
+    a.tokens, a.token_len, a.scores, a.num_hyps, a.status = _ptr(tokens), _ptr(token_len), _ptr(scores), _ptr(num_hyps), _ptr(status)
+    a.workspace, a.workspace_bytes, a.stream = _ptr(ws), nws, _stream()
+    _launch("cm_ctc_beam_stream", N.lib().cm_ctc_beam_stream, a, units=slots * t)
+    return tokens, token_len, scores, num_hyps, status
+
+
 def _ctc_prefix_args(what, logp, n_u, row_utt, last, r_n, r_b, psi_g, blank, eos, validated):
     """The arguments cm_ctc_prefix_score and cm_ctc_prefix_advance share, checked: sizes, dtypes and (one host read, skipped
     with validated=True for a row_utt the caller has checked already) row_utt's range."""
