@@ -1284,6 +1284,82 @@ int cm_fbank_finish(const cm_fbank_args *args);
 int cm_fbank_wav(const cm_fbank_args *args);
 
 /* ---------------------------------------------------------------------------------------
+ * The Fbank and the CNN front end as a stream: waveform chunks in, encoder rows out.  All `batch` streams
+ * advance in lock step; every count below is host arithmetic on the number of samples handed over so far.
+ *
+ * cm_fbank_wav_stream: frames [f0, f0 + nf) of every stream, cm_fbank_wav's arithmetic per frame (same bits).  Frame f reads the
+ * samples [hop f - 256, hop f + 256) by their index in the utterance: index s < 0 and, at the end of the utterance
+ * (total >= 0), s >= total read as zero; consumed <= s < consumed + n comes from chunk[b, s - consumed]; consumed - 512 <= s <
+ * consumed from hist[b, s - consumed + 512].  Nothing else is read, and no sample outside those two arrays ever is.
+ *   chunk    : (batch, n) fp32, batch stride chunk_bs elements; NULL when n = 0
+ *   hist     : (batch, 512) fp32, the last 512 samples in front of the chunk (zeros in front of the utterance)
+ *   hist_out : (batch, 512) fp32, receives the last 512 samples of [hist | chunk]; must not overlap hist (other workgroups
+ *              of the launch still read it: CM_EINVAL) -- the caller swaps the two, the protocol of cm_conv_xproj_uni
+ *   db       : (batch, nf, n_mels) fp32, the dB values before the top_db clamp (out)
+ *   fmax     : (batch, nf) fp32, the maximum of each frame (out)
+ * nf = 0 only rolls the history.  n_fft 512, n_mels <= 128, hop even; consumed + n < 2^30.
+ *
+ * cm_fbank_finish_stream (same args, after cm_fbank_wav_stream): the causal top_db clamp, the floor of frame f being
+ * max(umax[b], fmax[b, f0 .. f]) - top_db, and the optional normalisation (v - mean[m]) / std[m], in place on db; umax[b]
+ * (-inf at the start of an utterance) is updated in place to the maximum over all frames so far.  With feat_hist / feat_hist_out
+ * it also rolls the feature history cm_cnn_front_stream reads: feat_hist_out (batch, 8, n_mels) receives the last 8 rows
+ * of [feat_hist | db] (zeros in front of frame 0); the two must not overlap.
+ * ------------------------------------------------------------------------------------- */
+typedef struct cm_fbank_stream_args {
+    int32_t batch, n_mels, n_fft, hop;
+    int32_t n;                          /* samples per stream in this call, >= 0                                    */
+    int32_t consumed;                   /* samples per stream handed over by earlier calls                          */
+    int32_t total;                      /* samples of the whole utterance when this call ends it, else -1            */
+    int32_t f0, nf;                     /* first frame and number of frames this call produces                      */
+    int32_t pad_;
+    const float *chunk;  int64_t chunk_bs;
+    const float *hist;
+    float *hist_out;
+    const float *window;                /* (512) fp32: the analysis window zero-padded (centred) to n_fft           */
+    const float *twiddle;               /* (512, 2) fp32: exp(-2 pi i k / 512)                                      */
+    const int32_t *band_lo, *band_hi;   /* (n_mels): filter m is non-zero only on bins [lo, hi)                     */
+    const int32_t *band_off;            /* (n_mels + 1): offsets into band_w                                        */
+    const float *band_w;                /* the filters' weights on their bands, packed                              */
+    float *db;
+    float *fmax;
+    float amin, top_db;
+    float *umax;                        /* (batch) fp32, in / out: cm_fbank_finish_stream only                      */
+    const float *mean, *std;            /* (n_mels) or NULL: cm_fbank_finish_stream only                            */
+    const float *feat_hist;             /* (batch, 8, n_mels) or NULL: cm_fbank_finish_stream only                  */
+    float *feat_hist_out;               /* (batch, 8, n_mels) or NULL                                               */
+    void *stream;
+} cm_fbank_stream_args;
+
+int cm_fbank_wav_stream(const cm_fbank_stream_args *args);
+int cm_fbank_finish_stream(const cm_fbank_stream_args *args);
+
+/* cm_cnn_front's rows [r0, r0 + nr) of every stream, with its block-1 row routine, MFMA chain and LayerNorms (same bits).  Row r
+ * reads the feature frames 4r - 3 .. 4r + 3 by their index in the utterance: frame f >= f0 comes from feats[b, f - f0], f0 - 8 <=
+ * f < f0 from feat_hist[b, f - f0 + 8].  Index -1 reflects to 1 (features and block-1 rows); the reflection at the end,
+ * T -> T - 2 and T1 -> T1 - 2, is taken only when the number of frames of the utterance is known (T_total >= 5, else -1).
+ * The caller guarantees 4 (r0 + nr - 1) + 3 < f0 + nf, or T_total = f0 + nf, and 4 r0 - 3 >= f0 - 8.
+ *   feats (batch, nf, 80) fp32, feat_hist (batch, 8, 80) fp32 (NULL: nothing in front of feats), out (batch, nr, 640) bf16;
+ *   weights as cm_cnn_front_args. */
+typedef struct cm_cnn_front_stream_args {
+    int32_t batch, F, C1, C2;
+    int32_t f0, nf;                     /* first frame of feats, frames in feats                                    */
+    int32_t r0, nr;                     /* first row and number of rows this call produces                          */
+    int32_t T_total;                    /* frames of the whole utterance when this call ends it, else -1            */
+    int32_t pad_;
+    const float *feats;
+    const float *feat_hist;
+    const float *w1, *b1, *ln1_g, *ln1_b;
+    const void  *w2;
+    const float *b2, *ln2_g, *ln2_b;
+    float eps1, eps2, slope;
+    int32_t pad2_;
+    void *out;
+    void *stream;
+} cm_cnn_front_stream_args;
+
+int cm_cnn_front_stream(const cm_cnn_front_stream_args *args);
+
+/* ---------------------------------------------------------------------------------------
  * SpecAugment masking (speechbrain SpectrogramDrop, reference hparams/CTC/conmamba_large.yaml:273-320 and
  * train_CTC.py:291): feats[b, t, f] = fill for every (b, t, f) covered by one of the utterance's masks along
  * `dim` (1 = time, 2 = frequency).  Mask starts/lengths are drawn by the host RNG: int32 (batch, n_masks).

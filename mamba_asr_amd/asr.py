@@ -119,9 +119,41 @@ class ConMambaASR(nn.Module):
 
     def encode_streaming(self, src, context):
         """The next chunk of the CNN front end's output rows (B, t, F, C) or (B, t, F * C) of the streams in ``context``
-        (self.Transformer.make_streaming_context(None, dict(batch_size=B))) -> encoder output (B, t, d_model).  Streaming starts behind the front end: the Fbank's top_db clamp and the CNN blocks' reflect padding
-        in time look at the future of the utterance."""
+        (self.Transformer.make_streaming_context(None, dict(batch_size=B))) -> encoder output (B, t, d_model).  The rows come
+        from the whole-utterance front end or, chunk by chunk from the waveform, from frontend_streaming; encode_wav_streaming
+        does both steps."""
         return self.Transformer.encode_streaming(src, context)
+
+    def make_streaming_context(self, batch_size, dtype=None):
+        """A blank context for streaming ``batch_size`` utterances in lock step from the waveform: ``.frontend``
+        (fused.FrontEndStreamingContext) and ``.encoder`` (self.Transformer.make_streaming_context(None, dict(batch_size=B))), with
+        ``reset()`` for the start of the next utterance on all streams.  ``dtype``: the compute dtype of both (default: the
+        autocast dtype when enabled, else the parameters')."""
+        from . import fused
+        p = self.ctc_lin.w.weight
+        if dtype is None:
+            dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else p.dtype
+        return fused.ASRStreamingContext(fused.FrontEndStreamingContext(batch_size, p.device, dtype),
+                                         self.Transformer.make_streaming_context(None, dict(batch_size=batch_size, dtype=dtype)))
+
+    def frontend_streaming(self, wav_chunk, ctx, last=False):
+        """The next samples (B, n), any n >= 0, of the streams in ``ctx`` (make_streaming_context) -> the CNN front end's rows that
+        became final, (B, t, 640) with t = 0 allowed; ``last`` ends the utterance and flushes its remaining rows
+        (fused.frontend_streaming: the look-ahead is 46 ms at the CTC-large settings, and the top_db clamp is the causal one of
+        sb_compat.Fbank(causal_top_db=True))."""
+        from . import fused
+        return fused.frontend_streaming(self, wav_chunk, ctx.frontend, last)
+
+    def encode_wav_streaming(self, wav_chunk, ctx, last=False):
+        """frontend_streaming's rows through encode_streaming -> (B, t, d_model); no encoder launch when no row is ready."""
+        rows = self.frontend_streaming(wav_chunk, ctx, last)
+        if rows.shape[1] == 0:
+            return torch.zeros((rows.shape[0], 0, self.cfg.d_model), dtype=torch.float32, device=rows.device)
+        return self.encode_streaming(rows, ctx.encoder)
+
+    def log_probs_wav_streaming(self, wav_chunk, ctx, last=False):
+        """encode_wav_streaming's chunk through the CTC head, (B, t, vocab): what ctc_decode.StreamingCTCBeamSearcher.step consumes."""
+        return torch.log_softmax(self.ctc_lin(self.encode_wav_streaming(wav_chunk, ctx, last)), dim=-1)
 
     def log_probs_streaming(self, src, context):
         """encode_streaming's chunk through the CTC head: log_softmax(ctc_lin(encode_streaming(src, context))), (B, t, vocab) --

@@ -55,14 +55,25 @@ struct front_lds {
     bf16x8 wfrag[2][18][64];              // block-2 weights as MFMA A-operand fragment images (36 KB; in registers they
 };                                        // cost 144 VGPRs and pushed the block-1 row computation into scratch)
 
-__global__ __launch_bounds__(512) void cnn_front_kernel(const cm_cnn_front_args p, int T1, int T2, int tiles_per_utt, int chunk, int chunks_per_utt,
+constexpr int FH = 8;                     // cm_cnn_front_stream: feature rows of history per stream
+constexpr int T_OPEN = 1 << 29;           // ... and its T / T1 while the utterance's end is unknown: no index reflects against it
+
+// STREAM (cm_cnn_front_stream; ARGS = cm_cnn_front_stream_args): the launch produces rows [r0, r0 + nr) of utterances whose feature
+// frames arrive in chunks; T2 is then r0 + nr, T / T1 are T_OPEN unless the call ends the utterance, and the tile walk starts at
+// row r0 (tile k = rows r0 + 4 k ..: a slot is the padded row index mod NR, whatever the start).  Only the feature addresses,
+// the clamp of the padded row index and the output row differ: block1_row, the MFMA chain and both LayerNorms are the same
+// statements for both instantiations, so a row has the same bits.
+template <bool STREAM, typename ARGS>
+__global__ __launch_bounds__(512) void cnn_front_kernel(const ARGS p, int T, int T1, int T2, int tiles_per_utt, int chunk, int chunks_per_utt,
                                                         int nchunks) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     front_lds &L = *reinterpret_cast<front_lds *>(smem);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, lq = lane >> 4;
-    const int T = p.T, T1P = T1 + 2;
+    int rbase, tp_last;                                           // first row of the launch; last padded block-1 row a fetch may name
+    if constexpr (STREAM) { rbase = p.r0; tp_last = 2 * T2; }     // (row T2 - 1 reads the padded rows up to 2 T2)
+    else { rbase = 0; tp_last = T1 + 1; }
 
     // ---- constants held in registers for the whole kernel
     const uint16_t *W2 = reinterpret_cast<const uint16_t *>(p.w2);                    // (32, 3, 3, 64) bf16
@@ -87,15 +98,24 @@ __global__ __launch_bounds__(512) void cnn_front_kernel(const cm_cnn_front_args 
     uint16_t *out = reinterpret_cast<uint16_t *>(p.out);
 
     // feature rows of padded block-1 row tp of utterance b: 3 rows x 82 reflect-padded bins, 4 values per lane
+    [[maybe_unused]] const float *hist = nullptr;                 // STREAM: the utterance's FH feature rows in front of feats
     auto fetch_rows = [&](const float *feats, int tp, float (&r)[4]) {
-        const int t1 = reflect_idx(min(tp, T1P - 1) - 1, T1);
+        const int t1 = reflect_idx(min(tp, tp_last) - 1, T1);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int idx = lane + 64 * k;
             r[k] = 0.f;
             if (idx < 3 * 82) {
                 const int rr = idx / 82, fc = idx - rr * 82;
-                r[k] = feats[(int64_t)reflect_idx(2 * t1 + rr - 1, T) * F0 + reflect_idx(fc - 1, F0)];
+                const int fr = reflect_idx(2 * t1 + rr - 1, T), bin = reflect_idx(fc - 1, F0);
+                if constexpr (STREAM) {
+                    // frame fr of the utterance: in this call's rows from f0 on, in the history behind it.  The clamps hold the address
+                    // inside the two arrays for any argument; the entry point's checks make them idle
+                    const int c = fr - p.f0;
+                    r[k] = (c >= 0 || !hist) ? feats[(int64_t)min(max(c, 0), p.nf - 1) * F0 + bin] : hist[(int64_t)max(c + FH, 0) * F0 + bin];
+                } else {
+                    r[k] = feats[(int64_t)fr * F0 + bin];
+                }
             }
         }
     };
@@ -153,18 +173,25 @@ __global__ __launch_bounds__(512) void cnn_front_kernel(const cm_cnn_front_args 
     for (int ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
         const int b = ch / chunks_per_utt, tile0 = (ch % chunks_per_utt) * chunk;
         const int tile1 = min(tile0 + chunk, tiles_per_utt);
-        const float *feats = p.feats + (int64_t)b * T * F0;
+        const float *feats;
+        if constexpr (STREAM) {
+            feats = p.feats + (int64_t)b * p.nf * F0;
+            hist = p.feat_hist ? p.feat_hist + (int64_t)b * FH * F0 : nullptr;
+        } else {
+            feats = p.feats + (int64_t)b * T * F0;
+        }
         float pre[4];
         __syncthreads();                                          // previous chunk's tile is dead (and ln1 is staged)
         // chunk prologue: padded row 8*tile0 (the row every later tile inherits) by wave 0
+        const int tpc = 2 * (rbase + TT * tile0);
         if (wave == 0) {
-            fetch_rows(feats, 2 * TT * tile0, pre);
+            fetch_rows(feats, tpc, pre);
             stage_rows(pre);
-            block1_row((2 * TT * tile0) % NR);
+            block1_row(tpc % NR);
         }
-        fetch_rows(feats, 2 * TT * tile0 + 1 + wave, pre);
+        fetch_rows(feats, tpc + 1 + wave, pre);
         for (int tile = tile0; tile < tile1; ++tile) {
-            const int tp0 = 2 * TT * tile, r0 = TT * tile;
+            const int r0 = rbase + TT * tile, tp0 = 2 * r0;
             // ---- block 1: wave w -> padded row tp0 + 1 + w
             stage_rows(pre);
             if (tile + 1 < tile1) fetch_rows(feats, tp0 + 2 * TT + 1 + wave, pre);      // next tile's rows, one tile ahead
@@ -208,7 +235,7 @@ __global__ __launch_bounds__(512) void cnn_front_kernel(const cm_cnn_front_args 
                     sq = fmaf(vv[k].x, vv[k].x, fmaf(vv[k].y, vv[k].y, sq));
                 }
                 const float rstd = rsqrtf(wave_sum64(sq) * (1.f / nfeat) + p.eps2);
-                uint16_t *dst = out + ((int64_t)b * T2 + r0 + wave) * nfeat;
+                uint16_t *dst = out + ((int64_t)b * (T2 - rbase) + (r0 - rbase) + wave) * nfeat;
 #pragma unroll
                 for (int k = 0; k < nfeat / 128; ++k) {
                     const int i = lane + 64 * k;
@@ -246,7 +273,8 @@ extern "C" int cm_cnn_front(const cm_cnn_front_args *args) {
     CM_REQUIRE(nchunks <= 2147483647, CM_EINVAL, "cnn_front: too many chunks");
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(cnn_front_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(cnn_front_kernel<false, cm_cnn_front_args>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         if (e != hipSuccess) {
             cm_set_error("cnn_front: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
             return (int)e;
@@ -254,7 +282,52 @@ extern "C" int cm_cnn_front(const cm_cnn_front_args *args) {
         attr_done = true;
     }
     const int64_t grid = nchunks < 256 ? nchunks : 256;
-    hipLaunchKernelGGL(cnn_front_kernel, dim3((unsigned)grid), dim3(512), sizeof(front_lds), reinterpret_cast<hipStream_t>(a.stream), a, T1, T2,
-                       tiles_per_utt, chunk, chunks_per_utt, (int)nchunks);
+    hipLaunchKernelGGL((cnn_front_kernel<false, cm_cnn_front_args>), dim3((unsigned)grid), dim3(512), sizeof(front_lds),
+                       reinterpret_cast<hipStream_t>(a.stream), a, a.T, T1, T2, tiles_per_utt, chunk, chunks_per_utt, (int)nchunks);
     return cm_launch_status("cm_cnn_front");
+}
+
+extern "C" int cm_cnn_front_stream(const cm_cnn_front_stream_args *args) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "cnn_front_stream: args is NULL");
+    const cm_cnn_front_stream_args &a = *args;
+    CM_REQUIRE(a.batch > 0 && a.nf > 0 && a.nr > 0 && a.f0 >= 0 && a.r0 >= 0 && a.feats && a.w1 && a.ln1_g && a.ln1_b && a.w2 && a.ln2_g && a.ln2_b &&
+                   a.out, CM_EINVAL, "cnn_front_stream: bad sizes or NULL tensor");
+    CM_REQUIRE(a.F == F0 && a.C1 == C1 && a.C2 == C2, CM_EUNSUPPORTED, "cnn_front_stream: only 80 bins, channels (64, 32) (got F %d, C %d, %d)", a.F,
+               a.C1, a.C2);
+    CM_REQUIRE(cm_aligned(a.w2, 16) && cm_aligned(a.out, 4) && cm_aligned(a.ln1_g, 8) && cm_aligned(a.ln1_b, 8) && cm_aligned(a.ln2_g, 8) &&
+                   cm_aligned(a.ln2_b, 8) && (!a.b2 || cm_aligned(a.b2, 16)),
+               CM_EALIGN, "cnn_front_stream: w2 / b2 must be 16-byte aligned, LayerNorm parameters 8-byte aligned");
+    const int64_t fend = (int64_t)a.f0 + a.nf, rend = (int64_t)a.r0 + a.nr;
+    CM_REQUIRE(fend < T_OPEN, CM_EUNSUPPORTED, "cnn_front_stream: frame index too large");
+    int T = T_OPEN, T1 = T_OPEN;
+    if (a.T_total >= 0) {                                         // the call ends the utterance: rows up to T2 - 1, reflected at T and T1
+        CM_REQUIRE(a.T_total >= 5 && a.T_total == fend, CM_EINVAL, "cnn_front_stream: T_total must be f0 + nf and at least 5");
+        T = a.T_total;
+        T1 = (T + 1) / 2;
+        CM_REQUIRE(rend <= (T1 + 1) / 2, CM_EINVAL, "cnn_front_stream: row %d is past the utterance's last", (int)rend - 1);
+    } else {
+        CM_REQUIRE(4 * (rend - 1) + 3 < fend, CM_EINVAL, "cnn_front_stream: row %d needs frames that have not arrived", (int)rend - 1);
+    }
+    // the lowest frame a row of the launch names: 4 r0 - 3 (reflected at 0), or T - 5 through the reflections at the end
+    const int64_t lowest = std::min<int64_t>(std::max<int64_t>(4 * (int64_t)a.r0 - 3, 0), a.T_total >= 0 ? (int64_t)a.T_total - 5 : fend);
+    CM_REQUIRE(lowest >= (a.feat_hist ? (int64_t)a.f0 - FH : (int64_t)a.f0), CM_EINVAL, "cnn_front_stream: row %d reaches behind the feature history", a.r0);
+    const int tiles_per_utt = (a.nr + TT - 1) / TT;
+    const int chunk = 16;
+    const int chunks_per_utt = (tiles_per_utt + chunk - 1) / chunk;
+    const int64_t nchunks = (int64_t)a.batch * chunks_per_utt;
+    CM_REQUIRE(nchunks <= 2147483647, CM_EINVAL, "cnn_front_stream: too many chunks");
+    static bool attr_done = false;
+    if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(cnn_front_kernel<true, cm_cnn_front_stream_args>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        if (e != hipSuccess) {
+            cm_set_error("cnn_front_stream: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+            return (int)e;
+        }
+        attr_done = true;
+    }
+    const int64_t grid = nchunks < 256 ? nchunks : 256;
+    hipLaunchKernelGGL((cnn_front_kernel<true, cm_cnn_front_stream_args>), dim3((unsigned)grid), dim3(512), sizeof(front_lds),
+                       reinterpret_cast<hipStream_t>(a.stream), a, T, T1, (int)rend, tiles_per_utt, chunk, chunks_per_utt, (int)nchunks);
+    return cm_launch_status("cm_cnn_front_stream");
 }

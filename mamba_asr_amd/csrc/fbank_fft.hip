@@ -22,6 +22,8 @@ constexpr int FT = 16;            // frames per workgroup (4 per wave)
 constexpr int PWS = FT + 1;       // power-tile row stride (odd: conflict-free mel loop)
 constexpr int NF = 512;           // n_fft
 constexpr int NH = NF / 2;        // complex FFT length
+constexpr int HS = NF;            // cm_fbank_wav_stream: samples of history per stream (a frame reaches back fewer than n_fft)
+constexpr int FH = 8;             // cm_fbank_finish_stream: feature rows of history per stream (a row reaches back at most 6)
 constexpr int BWCAP = 1024;       // band weights staged in LDS (triangular filters: <= 2 per bin = 514 for 257 bins); a larger
                                   // table is read from global memory instead.  4 KB instead of the table's 16 KB bound: a
                                   // workgroup holds 32.5 KB of LDS and four of them (16 waves) share a CU
@@ -55,15 +57,40 @@ __device__ __forceinline__ int rev4_8bit(int k) {                     // reverse
 }
 
 // floor_db = 10 log10(amin) rounded once from double on the host: log10f is an ulp or two off, and silence must sit ON the floor
-__global__ __launch_bounds__(256) void fbank_wav_kernel(const cm_fbank_args p, const float floor_db) {
+//
+// STREAM (cm_fbank_wav_stream; ARGS = cm_fbank_stream_args): the launch covers frames [f0, f0 + nf) of an utterance whose samples
+// arrive in chunks.  Only the sample fetch, the store addresses and the per-frame maxima differ: the window, the four stages,
+// the split step and the mel loop below are the same statements for both instantiations, so a frame has the same bits.
+template <bool STREAM, typename ARGS>
+__global__ __launch_bounds__(256) void fbank_wav_kernel(const ARGS p, const float floor_db) {
     extern __shared__ float sm[];
-    const int b = blockIdx.y, t0 = blockIdx.x * FT;
-    const int F = NH + 1, T = p.frames, M = p.n_mels;
+    const int b = blockIdx.y;
+    int t0, T;                                                    // first frame of this workgroup, end of the valid frames
+    if constexpr (STREAM) { t0 = p.f0 + blockIdx.x * FT; T = p.f0 + p.nf; }
+    else { t0 = blockIdx.x * FT; T = p.frames; }
+    const int F = NH + 1, M = p.n_mels;
     float *pw = sm;                                               // [F][PWS] power tile
     int *band = reinterpret_cast<int *>(pw + F * PWS);            // [3 M + 1]
     float *bw = reinterpret_cast<float *>(band + 3 * M + 1);      // [BWCAP] packed band weights
     cf *zb = reinterpret_cast<cf *>(bw + BWCAP + ((3 * M + 1 + F * PWS) & 1));  // [4 waves][ZN] FFT work buffers (padded), 8-byte aligned
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // sample s of the utterance (STREAM): zero in front of it and past its end, else from [hist | chunk]; an index neither
+    // array holds reads as zero too, so that no address outside them is ever formed
+    [[maybe_unused]] auto sample = [&](int s) -> unsigned int {
+        if constexpr (STREAM) {
+            if (s < 0 || (p.total >= 0 && s >= p.total)) return 0u;
+            const int c = s - p.consumed;
+            if (c >= 0) return c < p.n ? __float_as_uint(p.chunk[(int64_t)b * p.chunk_bs + c]) : 0u;
+            return c >= -HS ? __float_as_uint(p.hist[(int64_t)b * HS + c + HS]) : 0u;
+        } else {
+            return 0u;
+        }
+    };
+    if constexpr (STREAM) {
+        if (blockIdx.x == 0)                                      // the next call's history: the last HS samples of [hist | chunk]
+            for (int j = tid; j < HS; j += 256) p.hist_out[(int64_t)b * HS + j] = __uint_as_float(sample(p.consumed + p.n - HS + j));
+        if (p.nf == 0) return;
+    }
     for (int m = tid; m < M; m += 256) { band[m] = p.band_lo[m]; band[M + m] = p.band_hi[m]; }
     for (int m = tid; m <= M; m += 256) band[2 * M + m] = p.band_off[m];
     const int bw_total = p.band_off[M];
@@ -96,8 +123,9 @@ __global__ __launch_bounds__(256) void fbank_wav_kernel(const cm_fbank_args p, c
         wk[i] = tw[k];
     }
     const int r3 = ((lane & 3) << 4) | (lane & 12) | (lane >> 4);  // Z[lane + 64 i] sits at position 4 r3 + i
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(p.wav + (int64_t)b * p.wav_bs), 0, p.samples * 4, 0x00020000);
+    __amdgpu_buffer_rsrc_t wr;
+    if constexpr (!STREAM)
+        wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.wav + (int64_t)b * p.wav_bs), 0, p.samples * 4, 0x00020000);
     cf *z = zb + wave * ZN;
 
     // positions (padded) of this lane's butterfly operands in stages 0..3 and of its split-step reads
@@ -116,8 +144,18 @@ __global__ __launch_bounds__(256) void fbank_wav_kernel(const cm_fbank_args p, c
     // The 8-byte load never straddles the start: t*hop - 256 and 2m are even.
     auto fetch = [&](int t, u32x2(&raw)[4]) {
         const int s0 = t * p.hop - NH;
+        if constexpr (STREAM) {
+            // 4-byte loads: a chunk boundary at an odd sample leaves no 8-byte alignment to rely on.  Frames past the launch's
+            // last are not fetched (their samples may not have arrived)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) raw[q] = __builtin_amdgcn_raw_buffer_load_b64(wr, (s0 + 2 * (lane + 64 * q)) * 4, 0, 0);
+            for (int q = 0; q < 4; ++q) {
+                const int s = s0 + 2 * (lane + 64 * q);
+                raw[q] = t < T ? u32x2{sample(s), sample(s + 1)} : u32x2{0u, 0u};
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) raw[q] = __builtin_amdgcn_raw_buffer_load_b64(wr, (s0 + 2 * (lane + 64 * q)) * 4, 0, 0);
+        }
     };
     u32x2 raw[4], nxt[4];
     fetch(t0 + wave * (FT / 4), raw);
@@ -192,15 +230,54 @@ __global__ __launch_bounds__(256) void fbank_wav_kernel(const cm_fbank_args p, c
     __syncthreads();
     {
         const int nrow = min(FT, T - t0);                         // rows t0 .. t0 + nrow - 1 are contiguous in db: one linear copy
-        float *dst = p.db + ((int64_t)b * T + t0) * M;
+        float *dst;
+        if constexpr (STREAM) dst = p.db + ((int64_t)b * p.nf + (t0 - p.f0)) * M;
+        else dst = p.db + ((int64_t)b * T + t0) * M;
         for (int i = tid; i < nrow * M; i += 256) dst[i] = dbt[i];
+    }
+    if constexpr (STREAM) {
+        // the causal clamp wants the maximum of every frame, not of the tile: wave w reduces the rows 4 w .. 4 w + 3 of the dB tile
+        for (int j = wave * (FT / 4); j < (wave + 1) * (FT / 4); ++j) {
+            float mx = -INFINITY;
+            for (int m = lane; m < M; m += 64) mx = fmaxf(mx, dbt[j * M + m]);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+            if (lane == 0 && t0 + j < T) p.fmax[(int64_t)b * p.nf + (t0 - p.f0) + j] = mx;
+        }
+        return;
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) local_max = fmaxf(local_max, __shfl_xor(local_max, off, 64));
     __syncthreads();
     if (lane == 0) pw[wave] = local_max;
     __syncthreads();
-    if (tid == 0) p.umax_part[(int64_t)b * gridDim.x + blockIdx.x] = fmaxf(fmaxf(pw[0], pw[1]), fmaxf(pw[2], pw[3]));
+    if constexpr (!STREAM)
+        if (tid == 0) p.umax_part[(int64_t)b * gridDim.x + blockIdx.x] = fmaxf(fmaxf(pw[0], pw[1]), fmaxf(pw[2], pw[3]));
+}
+
+// cm_fbank_finish_stream: one workgroup per stream.  Thread = (frame group g, mel bin m): every thread carries the prefix maximum
+// over all frames (nf broadcast loads) and clamps / normalises the frames of its group; no atomics, no second pass.
+__global__ __launch_bounds__(256) void fbank_finish_stream_kernel(const cm_fbank_stream_args p) {
+    const int b = blockIdx.x, M = p.n_mels, nf = p.nf;
+    const int G = 256 / M, g = threadIdx.x / M, m = threadIdx.x - g * M;
+    float run = p.umax[b];
+    __syncthreads();                                              // everyone holds the carried maximum before thread 0 replaces it
+    const float *fm = p.fmax + (int64_t)b * nf;
+    float *db = p.db + (int64_t)b * nf * M;
+    const float mean = p.mean && g < G ? p.mean[m] : 0.f, sd = p.mean && g < G ? p.std[m] : 1.f;
+    for (int i = 0; i < nf; ++i) {
+        run = fmaxf(run, fm[i]);
+        if (g < G && i % G == g) {
+            float v = fmaxf(db[(int64_t)i * M + m], run - p.top_db);
+            if (p.mean) v = (v - mean) / sd;
+            db[(int64_t)i * M + m] = v;
+            if (p.feat_hist_out && i >= nf - FH) p.feat_hist_out[((int64_t)b * FH + (i - (nf - FH))) * M + m] = v;
+        }
+    }
+    if (p.feat_hist_out && g < G)                                 // rows the call did not fill: the old history moved up, zeros in front of frame 0
+        for (int j = g; j < FH - nf; j += G)
+            p.feat_hist_out[((int64_t)b * FH + j) * M + m] = (p.feat_hist && p.f0 + nf - FH + j >= 0) ? p.feat_hist[((int64_t)b * FH + j + nf) * M + m] : 0.f;
+    if (threadIdx.x == 0) p.umax[b] = run;
 }
 
 }  // namespace
@@ -218,7 +295,60 @@ extern "C" int cm_fbank_wav(const cm_fbank_args *args) {
     CM_REQUIRE(a.batch <= 65535 && a.n_mels <= 128, CM_EUNSUPPORTED, "fbank_wav: batch / n_mels too large");
     const size_t smem = (size_t)(NH + 1) * PWS * 4 + (size_t)(3 * a.n_mels + 1) * 4 + (size_t)BWCAP * 4 + (size_t)4 * ZN * 8 + 4;
     dim3 grid((a.frames + FT - 1) / FT, a.batch);
-    hipLaunchKernelGGL(fbank_wav_kernel, grid, dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), a,
+    hipLaunchKernelGGL((fbank_wav_kernel<false, cm_fbank_args>), grid, dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), a,
                        (float)(10.0 * log10((double)a.amin)));
     return cm_launch_status("cm_fbank_wav");
+}
+
+namespace {
+bool overlap(const void *a, const void *b, size_t bytes) {
+    const char *x = static_cast<const char *>(a), *y = static_cast<const char *>(b);
+    return x < y + bytes && y < x + bytes;
+}
+// the checks both stream entry points share (cm_fbank_finish_stream reads no sample: the sample counts are cm_fbank_wav_stream's);
+// nothing is launched before they pass
+int fbank_stream_check(const cm_fbank_stream_args &a, const char *who, bool samples) {
+    CM_REQUIRE(a.batch > 0 && a.n_mels > 0 && a.nf >= 0 && a.f0 >= 0, CM_EINVAL, "%s: bad sizes", who);
+    CM_REQUIRE(a.n_fft == NF, CM_EUNSUPPORTED, "%s: n_fft %d unsupported (512 only)", who, a.n_fft);
+    CM_REQUIRE(a.n_mels <= 128 && a.batch <= 65535, CM_EUNSUPPORTED, "%s: batch / n_mels too large", who);
+    if (!samples) return CM_OK;
+    CM_REQUIRE(a.n >= 0 && a.consumed >= 0 && a.hop > 0, CM_EINVAL, "%s: bad sample counts", who);
+    CM_REQUIRE(a.hop % 2 == 0, CM_EUNSUPPORTED, "%s: hop must be even", who);
+    CM_REQUIRE((int64_t)a.consumed + a.n < (1 << 30) && (a.total < 0 || a.total == a.consumed + a.n), CM_EINVAL,
+               "%s: total must be -1 or consumed + n, below 2^30", who);
+    // every frame of the launch lies inside what has arrived: its last sample index is below consumed + n unless the utterance ends here
+    CM_REQUIRE(a.nf == 0 || a.total >= 0 || (int64_t)a.hop * (a.f0 + a.nf - 1) + NH <= (int64_t)a.consumed + a.n, CM_EINVAL,
+               "%s: frame %d needs samples that have not arrived", who, a.f0 + a.nf - 1);
+    CM_REQUIRE(a.nf == 0 || (int64_t)a.hop * a.f0 - NH >= (int64_t)a.consumed - HS, CM_EINVAL, "%s: frame %d reaches behind the history", who, a.f0);
+    return CM_OK;
+}
+}  // namespace
+
+extern "C" int cm_fbank_wav_stream(const cm_fbank_stream_args *args) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_wav_stream: args is NULL");
+    const cm_fbank_stream_args &a = *args;
+    if (int rc = fbank_stream_check(a, "fbank_wav_stream", true)) return rc;
+    CM_REQUIRE(a.hist && a.hist_out && (a.n == 0 || a.chunk), CM_EINVAL, "fbank_wav_stream: NULL chunk / hist / hist_out");
+    CM_REQUIRE(!overlap(a.hist, a.hist_out, (size_t)a.batch * HS * 4), CM_EINVAL, "fbank_wav_stream: hist_out overlaps hist");
+    CM_REQUIRE(a.nf == 0 || (a.window && a.twiddle && a.db && a.fmax && a.band_lo && a.band_hi && a.band_off && a.band_w), CM_EINVAL,
+               "fbank_wav_stream: NULL tensor");
+    CM_REQUIRE(a.nf == 0 || (cm_aligned(a.window, 8) && cm_aligned(a.twiddle, 8)), CM_EALIGN, "fbank_wav_stream: window / twiddle must be 8-byte aligned");
+    const size_t smem = (size_t)(NH + 1) * PWS * 4 + (size_t)(3 * a.n_mels + 1) * 4 + (size_t)BWCAP * 4 + (size_t)4 * ZN * 8 + 4;
+    dim3 grid(a.nf ? (a.nf + FT - 1) / FT : 1, a.batch);
+    hipLaunchKernelGGL((fbank_wav_kernel<true, cm_fbank_stream_args>), grid, dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), a,
+                       (float)(10.0 * log10((double)a.amin)));
+    return cm_launch_status("cm_fbank_wav_stream");
+}
+
+extern "C" int cm_fbank_finish_stream(const cm_fbank_stream_args *args) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_finish_stream: args is NULL");
+    const cm_fbank_stream_args &a = *args;
+    if (int rc = fbank_stream_check(a, "fbank_finish_stream", false)) return rc;
+    CM_REQUIRE(a.nf > 0 && a.db && a.fmax && a.umax, CM_EINVAL, "fbank_finish_stream: no frames or NULL db / fmax / umax");
+    CM_REQUIRE(!a.mean == !a.std, CM_EINVAL, "fbank_finish_stream: mean and std go together");
+    CM_REQUIRE(!a.feat_hist_out || !a.feat_hist || !overlap(a.feat_hist, a.feat_hist_out, (size_t)a.batch * FH * a.n_mels * 4), CM_EINVAL,
+               "fbank_finish_stream: feat_hist_out overlaps feat_hist");
+    CM_REQUIRE(a.feat_hist_out || !a.feat_hist, CM_EINVAL, "fbank_finish_stream: feat_hist without feat_hist_out");
+    hipLaunchKernelGGL(fbank_finish_stream_kernel, dim3(a.batch), dim3(256), 0, reinterpret_cast<hipStream_t>(a.stream), a);
+    return cm_launch_status("cm_fbank_finish_stream");
 }

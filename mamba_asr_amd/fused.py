@@ -716,6 +716,204 @@ def asr_encode(model, wavs, wav_lens, dtype: Optional[torch.dtype] = None):
         return encoder_forward(model.Transformer.encoder, x.view(batch, t2, -1), dtype)
 
 
+# ------------------------------------------------------------------------------------------------
+# the front end as a stream: waveform chunks -> the CNN's rows
+# ------------------------------------------------------------------------------------------------
+# Encoder row r reads feature frames 4r - 3 .. 4r + 3 and frame f the samples [hop f - n_fft/2, hop f + n_fft/2): mid-stream the
+# front end has a finite look-ahead, and what a call returns is host arithmetic on the sample count.  The reflect borders of the
+# CNN blocks and the STFT's zero padding are applied at the two ends of the utterance only (reset / last=True).  The top_db clamp
+# is the causal one (floor of frame f = max dB of frames 0..f - top_db; sb_compat.Fbank(causal_top_db=True) is its whole-utterance
+# form).  Native route (GPU, bf16, n_fft 512, the recipes' CNN): cm_fbank_wav_stream, cm_fbank_finish_stream, cm_cnn_front_stream
+# -- three launches, no torch.cat, no torch.stft; the sample and feature histories are double-buffered and swapped.
+# CM_STREAM_FRONT_NATIVE=0 = the generic torch route (also: fp32, n_fft 400, CPU tensors).
+USE_STREAM_FRONT_NATIVE = os.environ.get("CM_STREAM_FRONT_NATIVE", "1") == "1"
+
+
+def frontend_frames_ready(n_samples: int, n_fft: int, hop: int) -> int:
+    """Feature frames that are final after ``n_samples`` samples of an unfinished utterance."""
+    return 0 if n_samples < n_fft // 2 else (n_samples - n_fft // 2) // hop + 1
+
+
+def frontend_rows_ready(n_samples: int, n_fft: int, hop: int) -> int:
+    """CNN front-end rows that are final after ``n_samples`` samples of an unfinished utterance (row r needs frame 4r + 3)."""
+    f = frontend_frames_ready(n_samples, n_fft, hop)
+    return 0 if f < 4 else (f - 4) // 4 + 1
+
+
+def frontend_rows_total(n_samples: int, hop: int) -> int:
+    """Rows of a finished utterance of ``n_samples`` samples: T = 1 + S // hop frames, T1 = ceil(T / 2), T2 = ceil(T1 / 2)."""
+    t1 = (1 + n_samples // hop + 1) // 2
+    return (t1 + 1) // 2
+
+
+class FrontEndStreamingContext:
+    """What the streamed front end carries from one call to the next for ``batch_size`` streams in lock step: the last 512 samples
+    and the last 8 feature rows (each with the spare the native kernels write the new history into), the running dB maximum of
+    the causal top_db clamp, and the host counters samples / frames / rows.  About 9 KB per stream.  The generic route keeps its
+    own (shorter) sample and feature tails in ``tail``.  ``dtype`` is the dtype of the rows that come out."""
+
+    def __init__(self, batch_size, device, dtype):
+        self.batch_size, self.device, self.dtype = int(batch_size), torch.device(device), dtype
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)
+        self.samp_hist, self.samp_spare = z(batch_size, ops.FRONT_HIST_SAMPLES), z(batch_size, ops.FRONT_HIST_SAMPLES)
+        self.feat_hist, self.feat_spare = z(batch_size, ops.FRONT_HIST_FRAMES, 80), z(batch_size, ops.FRONT_HIST_FRAMES, 80)
+        self.umax = torch.full((batch_size,), float("-inf"), dtype=torch.float32, device=self.device)
+        self.reset()
+
+    def reset(self, rows=None):
+        """The start of a new utterance on every stream.  Per-slot resets are not offered: streams that end at different samples
+        would yield different row counts per call, and the encoder behind takes one row count for all slots."""
+        if rows is not None:
+            raise NotImplementedError("FrontEndStreamingContext.reset(rows=...): the streams of a front-end context advance in lock step "
+                                      "(one sample count, one row count per call); reset all of them, or keep one context per stream")
+        for t in (self.samp_hist, self.samp_spare, self.feat_hist, self.feat_spare):
+            t.zero_()
+        self.umax.fill_(float("-inf"))
+        self.samples = self.frames = self.rows = 0
+        self.finished = False
+        self.tail = None
+
+
+class ASRStreamingContext:
+    """ConMambaASR.make_streaming_context: ``frontend`` (FrontEndStreamingContext) and ``encoder`` (what
+    Transformer.make_streaming_context returns); ``reset`` starts a new utterance on every stream of both."""
+
+    def __init__(self, frontend, encoder):
+        self.frontend, self.encoder = frontend, encoder
+
+    def reset(self):
+        self.frontend.reset()
+        self.encoder.encoder_context.reset()
+
+
+def _front_plan(model, ctx, wav_chunk, last):
+    """Host arithmetic of one call: (n_fft, hop, first frame, frames, first row, rows, T or -1)."""
+    fb = model.compute_features
+    if wav_chunk.dim() != 2 or wav_chunk.shape[0] != ctx.batch_size:
+        raise ValueError(f"frontend_streaming: wav_chunk must be (batch, n) with batch = {ctx.batch_size}, the context's; got {tuple(wav_chunk.shape)}")
+    if ctx.finished:
+        raise RuntimeError("frontend_streaming: the utterance was finished (last=True); reset() the context before the next one")
+    total = ctx.samples + wav_chunk.shape[1]
+    if last:
+        T = 1 + total // fb.hop
+        if T < 5:
+            raise RuntimeError(f"frontend_streaming: the finished utterance has {T} feature frames; the CNN front end needs at least 5 frames")
+        f1, r1 = T, frontend_rows_total(total, fb.hop)
+    else:
+        T, f1, r1 = -1, frontend_frames_ready(total, fb.n_fft, fb.hop), frontend_rows_ready(total, fb.n_fft, fb.hop)
+    return fb.n_fft, fb.hop, ctx.frames, f1 - ctx.frames, ctx.rows, r1 - ctx.rows, T
+
+
+def _front_norm(model, n_mels, device):
+    """The frozen global statistics as (n_mels,) fp32 vectors; uncalibrated ones are (1,)-shaped and broadcast."""
+    mean, std = model.normalize.glob_mean, model.normalize.glob_std
+    return (mean.detach().float().to(device).expand(n_mels).contiguous(), std.detach().float().to(device).expand(n_mels).contiguous())
+
+
+def _reflect(i, n):
+    return -i if i < 0 else (2 * n - 2 - i if 0 <= n <= i else i)
+
+
+def _conv_block_rows(blk, x):
+    """One ConvolutionFrontEnd block on rows whose time border is already in place: x (B, L, F, C) -> (B, (L - 3) // 2 + 1, F', C')."""
+    y = F.pad(x.permute(0, 3, 1, 2), (1, 1, 0, 0), mode="reflect")                   # the frequency border only
+    return blk.act(blk.norm(blk.conv(y).permute(0, 2, 3, 1)))
+
+
+def _front_generic(model, wav_chunk, ctx, last, plan):
+    n_fft, hop, f0, nf, r0, nr, T = plan
+    fb, dev, half = model.compute_features, wav_chunk.device, n_fft // 2
+    B = ctx.batch_size
+    if ctx.tail is None:       # samples from index s0 on (the zeros in front of the utterance included), features from frame g0 on
+        ctx.tail = dict(s0=-half, samp=torch.zeros(B, half, dtype=torch.float32, device=dev), g0=0,
+                        feat=torch.zeros(B, 0, fb.n_mels, dtype=torch.float32, device=dev))
+    tl = ctx.tail
+    parts = [tl["samp"], wav_chunk.float()] + ([torch.zeros(B, half, dtype=torch.float32, device=dev)] if last else [])
+    samp = torch.cat(parts, dim=1)
+    feat = tl["feat"]
+    if nf > 0:
+        seg = samp[:, hop * f0 - half - tl["s0"]: hop * (f0 + nf - 1) + half - tl["s0"]]
+        spec = torch.stft(seg, n_fft, hop, fb.win, fb.window.to(dev), center=False, normalized=False, onesided=True, return_complex=True)
+        power = (spec.real ** 2 + spec.imag ** 2).transpose(1, 2)
+        db = 10.0 * torch.log10(torch.clamp(power @ fb.fbank.to(dev), min=fb.amin))                     # (B, nf, n_mels)
+        run = torch.maximum(db.amax(dim=-1).cummax(dim=1).values, ctx.umax.to(dev)[:, None])       # prefix maximum, seeded with the carried one
+        ctx.umax = run[:, -1].contiguous()
+        mean, std = _front_norm(model, fb.n_mels, dev)
+        feat = torch.cat([feat, (torch.maximum(db, run[..., None] - fb.top_db) - mean) / std], dim=1)
+        keep = hop * (f0 + nf) - half - tl["s0"]
+        tl["samp"], tl["s0"] = samp[:, keep:].clone(), tl["s0"] + keep
+    else:
+        tl["samp"] = samp
+    out = torch.zeros(B, 0, 640, dtype=ctx.dtype, device=dev)
+    if nr > 0:
+        b0, b1 = model.CNN.blocks
+        T1 = (T + 1) // 2 if T >= 0 else -1
+        t1s = [_reflect(t, T1) for t in range(2 * r0 - 1, 2 * (r0 + nr))]             # block-1 rows under block 2's taps
+        lo, hi = min(t1s), max(t1s)
+        frames = [_reflect(f, T) - tl["g0"] for f in range(2 * lo - 1, 2 * hi + 2)]   # feature frames under block 1's taps
+        # block 1 in fp32 and its rows rounded once to the compute dtype, block 2's conv in that dtype: cm_cnn_front's precision
+        y1 = _conv_block_rows(b0, feat[:, frames, :, None]).to(ctx.dtype)              # rows lo .. hi
+        with torch.autocast(dev.type, dtype=ctx.dtype, enabled=ctx.dtype != torch.float32):
+            out = _conv_block_rows(b1, y1[:, [t - lo for t in t1s]])
+        out = out.flatten(2).to(ctx.dtype)
+        keep = max(4 * (r0 + nr) - 3, 0) - tl["g0"]
+        feat, tl["g0"] = feat[:, keep:].clone(), tl["g0"] + keep
+    tl["feat"] = feat
+    return out
+
+
+def _front_native(model, wav_chunk, ctx, last, plan):
+    n_fft, hop, f0, nf, r0, nr, T = plan
+    fb, B, n = model.compute_features, ctx.batch_size, wav_chunk.shape[1]
+    if n == 0 and nf == 0:
+        return torch.empty((B, 0, 640), dtype=torch.bfloat16, device=wav_chunk.device)
+    if wav_chunk.dtype != torch.float32 or (n and wav_chunk.stride(1) != 1):
+        wav_chunk = wav_chunk.float().contiguous()
+    db, fmax = ops.fbank_wav_stream(wav_chunk, ctx.samp_hist, ctx.samp_spare, ctx.samples, f0, nf, fb.window, n_fft, hop, fb.fbank, fb.amin,
+                                    total=ctx.samples + n if last else -1)
+    ctx.samp_hist, ctx.samp_spare = ctx.samp_spare, ctx.samp_hist
+    out = torch.empty((B, max(nr, 0), 640), dtype=torch.bfloat16, device=wav_chunk.device)
+    if nf == 0:
+        return out
+    mean, std = _front_norm(model, fb.n_mels, wav_chunk.device)
+    ops.fbank_finish_stream(db, fmax, ctx.umax, f0, fb.top_db, mean, std, ctx.feat_hist, ctx.feat_spare, n_fft=n_fft)
+    if nr > 0:
+        c = _frontend_cache(model, torch.bfloat16)
+        b0 = model.CNN.blocks[0]
+        n0 = b0.norm.norm
+        ops.cnn_front_stream(db, ctx.feat_hist, f0, r0, nr, b0.conv.weight, b0.conv.bias, n0.weight, n0.bias, n0.eps, c["w2_ohwi"], c["b2f"],
+                             c["ln2"][0], c["ln2"][1], c["ln2"][2], 0.01, t_total=T, out=out)
+    ctx.feat_hist, ctx.feat_spare = ctx.feat_spare, ctx.feat_hist
+    return out
+
+
+def frontend_streaming_native(model, ctx) -> bool:
+    """Whether frontend_streaming takes the native route for this model and context."""
+    fb, b0 = model.compute_features, model.CNN.blocks[0]
+    return (USE_STREAM_FRONT_NATIVE and ctx.device.type == "cuda" and ctx.dtype == torch.bfloat16 and fb.n_mels == 80
+            and ops.fbank_wav_supported(fb.n_fft, fb.hop, fb.n_mels) and tuple(b0.conv.weight.shape) == (64, 1, 3, 3)
+            and tuple(model.CNN.blocks[1].conv.weight.shape) == (32, 64, 3, 3) and b0.norm.norm.weight.numel() == 40 * 64)
+
+
+@torch.no_grad()
+def frontend_streaming(model, wav_chunk, ctx: FrontEndStreamingContext, last: bool = False):
+    """The next ``n`` samples (B, n), any n >= 0, of the B streams whose state ``ctx`` holds -> the CNN front end's rows that became
+    final, (B, t, 640) in the context's dtype (t may be 0): rows frontend_rows_ready(before) .. frontend_rows_ready(after) - 1, and
+    with ``last`` every remaining row of the utterance, with the end-of-utterance zero padding and reflections.  Concatenated over
+    the calls of an utterance the rows do not depend on the chunking.  No host synchronisation, no data-dependent shape."""
+    plan = _front_plan(model, ctx, wav_chunk, last)
+    with torch.autocast("cuda", enabled=False):
+        if frontend_streaming_native(model, ctx) and wav_chunk.is_cuda:
+            out = _front_native(model, wav_chunk, ctx, last, plan)
+        else:
+            out = _front_generic(model, wav_chunk, ctx, last, plan)
+    ctx.samples += wav_chunk.shape[1]
+    ctx.frames += plan[3]
+    ctx.rows += plan[5]
+    ctx.finished = bool(last)
+    return out
+
+
 class GraphedEncode:
     """hipGraph capture of ConMambaASR.encode for fixed-shape, device-resident inputs.
 

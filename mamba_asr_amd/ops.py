@@ -2166,6 +2166,92 @@ def fbank_from_wav(wav, window, n_fft, hop, fbank, amin=1e-10, top_db=80.0, mean
     return db
 
 
+FRONT_HIST_SAMPLES, FRONT_HIST_FRAMES = 512, 8      # per-stream history of cm_fbank_wav_stream / cm_cnn_front_stream
+
+
+def fbank_wav_stream(chunk, hist, hist_out, consumed, f0, nf, window, n_fft, hop, fbank, amin=1e-10, total=-1, bufs=None):
+    """The frames [f0, f0 + nf) of every stream of an utterance that arrives in chunks (cm_fbank_wav_stream): chunk (batch, n) fp32,
+    the samples ``consumed`` .. ``consumed + n`` of the utterance; hist / hist_out (batch, 512) fp32, the samples in front of the
+    chunk and the buffer that receives the next call's (another one: the caller swaps); ``total``: the utterance's length when the
+    chunk ends it (zero padding past it), else -1.  -> (db (batch, nf, n_mels) fp32 before the top_db clamp, fmax (batch, nf)
+    per-frame maxima), or (None, None) for nf = 0, which only rolls the history.  ``bufs``: caller-supplied ``db`` / ``fmax``."""
+    _dev_check(chunk, hist, hist_out, window, fbank)
+    b, n = chunk.shape
+    if chunk.dtype != torch.float32 or (n and chunk.stride(1) != 1):
+        raise RuntimeError("fbank_wav_stream: chunk must be fp32 (batch, n) with the sample axis contiguous")
+    _hist_rows(hist, (b, FRONT_HIST_SAMPLES), torch.float32, "fbank_wav_stream: hist")
+    _hist_rows(hist_out, (b, FRONT_HIST_SAMPLES), torch.float32, "fbank_wav_stream: hist_out")
+    fb = _f32c(fbank)
+    m = fb.shape[1]
+    a = N.FbankStreamArgs()
+    a.batch, a.n_mels, a.n_fft, a.hop, a.n, a.consumed, a.total, a.f0, a.nf = b, m, int(n_fft), int(hop), n, int(consumed), int(total), int(f0), int(nf)
+    a.chunk, a.chunk_bs, a.hist, a.hist_out = (_ptr(chunk) if n else None), chunk.stride(0), _ptr(hist), _ptr(hist_out)
+    db = fmax = None
+    if nf:
+        win, tw = _fft_tables(window, n_fft)
+        lo, hi, off, packed = _mel_bands(fb)
+        if packed is None:
+            raise RuntimeError("fbank_wav_stream: filterbank is not banded (no packed band weights)")
+        take = _bufs(bufs, ("db", "fmax"), "fbank_wav_stream")
+        db = take("db", (b, nf, m), torch.float32, chunk.device)
+        fmax = take("fmax", (b, nf), torch.float32, chunk.device)
+        a.window, a.twiddle, a.band_lo, a.band_hi, a.band_off, a.band_w = _ptr(win), _ptr(tw), _ptr(lo), _ptr(hi), _ptr(off), _ptr(packed)
+        a.db, a.fmax = _ptr(db), _ptr(fmax)
+    a.amin, a.stream = float(amin), _stream()
+    _launch("cm_fbank_wav_stream", N.lib().cm_fbank_wav_stream, a, units=b * nf)
+    return db, fmax
+
+
+def fbank_finish_stream(db, fmax, umax, f0, top_db=80.0, mean=None, std=None, feat_hist=None, feat_hist_out=None, n_fft=512):
+    """The causal top_db clamp and the global normalisation of fbank_wav_stream's frames, in place (cm_fbank_finish_stream): the
+    floor of frame f is max(umax[b], fmax[b, :f + 1]) - top_db, and umax (batch) fp32 -- -inf at the start of an utterance --
+    becomes the maximum over all frames so far.  feat_hist / feat_hist_out (batch, 8, n_mels) fp32: the feature rows in front of
+    ``db`` and the buffer that receives the last 8 rows of [feat_hist | db] (another one).  -> db."""
+    _dev_check(db, fmax, umax, mean, std, feat_hist, feat_hist_out)
+    b, nf, m = db.shape
+    if db.dtype != torch.float32 or not db.is_contiguous():
+        raise RuntimeError("fbank_finish_stream: db must be contiguous fp32 (batch, frames, n_mels)")
+    _hist_rows(fmax, (b, nf), torch.float32, "fbank_finish_stream: fmax")
+    _hist_rows(umax, (b,), torch.float32, "fbank_finish_stream: umax")
+    _hist_rows(feat_hist, (b, FRONT_HIST_FRAMES, m), torch.float32, "fbank_finish_stream: feat_hist")
+    _hist_rows(feat_hist_out, (b, FRONT_HIST_FRAMES, m), torch.float32, "fbank_finish_stream: feat_hist_out")
+    mean, std = _f32c(mean), _f32c(std)
+    if mean is not None and (mean.numel() != m or std.numel() != m):
+        raise RuntimeError(f"fbank_finish_stream: mean / std must have {m} elements")
+    a = N.FbankStreamArgs()
+    a.batch, a.n_mels, a.n_fft, a.f0, a.nf, a.total = b, m, int(n_fft), int(f0), nf, -1
+    a.db, a.fmax, a.umax, a.top_db, a.mean, a.std = _ptr(db), _ptr(fmax), _ptr(umax), float(top_db), _ptr(mean), _ptr(std)
+    a.feat_hist, a.feat_hist_out, a.stream = _ptr(feat_hist), _ptr(feat_hist_out), _stream()
+    _launch("cm_fbank_finish_stream", N.lib().cm_fbank_finish_stream, a, units=b * nf)
+    return db
+
+
+def cnn_front_stream(feats, feat_hist, f0, r0, nr, w1, b1, ln1_w, ln1_b, eps1, w2_ohwi, b2, ln2_w, ln2_b, eps2, slope=0.01, t_total=-1,
+                     out=None):
+    """The rows [r0, r0 + nr) of cnn_front for utterances whose features arrive in chunks (cm_cnn_front_stream): feats (batch, nf, 80)
+    fp32 holds the frames from f0 on, feat_hist (batch, 8, 80) the 8 in front of them (None: there are none).  ``t_total``: the
+    utterance's number of frames when this call ends it (the reflection at the end is taken), else -1.  -> (batch, nr, 640) bf16."""
+    _dev_check(feats, feat_hist, w1, b1, ln1_w, ln1_b, w2_ohwi, b2, ln2_w, ln2_b, out)
+    if feats.dtype != torch.float32 or not feats.is_contiguous() or feats.dim() != 3:
+        raise RuntimeError("cnn_front_stream: feats must be contiguous fp32 (batch, frames, bins)")
+    b, nf, f = feats.shape
+    if not (tuple(w1.shape) == (64, 1, 3, 3) and tuple(w2_ohwi.shape) == (32, 3, 3, 64) and w2_ohwi.dtype == torch.bfloat16 and w2_ohwi.is_contiguous()):
+        raise RuntimeError("cnn_front_stream: needs a (64, 1, 3, 3) first conv and a contiguous bf16 (32, 3, 3, 64) second conv")
+    _hist_rows(feat_hist, (b, FRONT_HIST_FRAMES, f), torch.float32, "cnn_front_stream: feat_hist")
+    w1f, b1f, g1, bt1 = _f32c(w1), _f32c(b1), _f32c(ln1_w).reshape(-1), _f32c(ln1_b).reshape(-1)
+    b2f, g2, bt2 = _f32c(b2), _f32c(ln2_w).reshape(-1), _f32c(ln2_b).reshape(-1)
+    if g1.numel() != 40 * 64 or g2.numel() != 20 * 32:
+        raise RuntimeError("cnn_front_stream: LayerNorm parameters must have 40*64 and 20*32 elements")
+    out = _out_rows(out, (b, nr, 640), torch.bfloat16, feats.device, "cnn_front_stream: out")
+    a = N.CnnFrontStreamArgs()
+    a.batch, a.F, a.C1, a.C2, a.f0, a.nf, a.r0, a.nr, a.T_total = b, f, 64, 32, int(f0), nf, int(r0), int(nr), int(t_total)
+    a.feats, a.feat_hist, a.w1, a.b1, a.ln1_g, a.ln1_b = _ptr(feats), _ptr(feat_hist), _ptr(w1f), _ptr(b1f), _ptr(g1), _ptr(bt1)
+    a.w2, a.b2, a.ln2_g, a.ln2_b = _ptr(w2_ohwi), _ptr(b2f), _ptr(g2), _ptr(bt2)
+    a.eps1, a.eps2, a.slope, a.out, a.stream = float(eps1), float(eps2), float(slope), _ptr(out), _stream()
+    _launch("cm_cnn_front_stream", N.lib().cm_cnn_front_stream, a, units=b * nr)
+    return out
+
+
 def spec_drop_(feats, start, length, dim, fill):
     """In-place SpecAugment masking (cm_spec_drop): feats (batch, frames, n_mels) fp32; start/length int32
     (batch, n_masks); dim 1 = time, 2 = frequency; fill = 0-dim device tensor."""

@@ -217,9 +217,19 @@ class Fbank(nn.Module):
         self.register_buffer("fbank", mel_filterbank(n_mels, n_fft, sample_rate, f_min, f_max), persistent=False)
 
     @torch.no_grad()
-    def forward(self, wav, norm=None):
-        """``norm`` = (mean, std) folds the global normalisation into the native back end (GPU only)."""
+    def forward(self, wav, norm=None, causal_top_db: bool = False):
+        """``norm`` = (mean, std) folds the global normalisation into the native back end (GPU only).
+        ``causal_top_db``: the floor of frame f is max(dB of frames 0..f) - top_db instead of the utterance's maximum - top_db: the
+        clamp a streamed front end can apply (fused.frontend_streaming), which is the default one whenever no value of the utterance
+        lies under its maximum - top_db.  Computed in torch on any device (the features a causal model is trained on)."""
         with torch.autocast(device_type=wav.device.type, enabled=False):          # speechbrain forces fp32 here
+            if causal_top_db:
+                spec = torch.stft(wav.float(), self.n_fft, self.hop, self.win, self.window, center=True,
+                                  pad_mode="constant", normalized=False, onesided=True, return_complex=True)
+                power = (spec.real ** 2 + spec.imag ** 2).transpose(1, 2)
+                db = 10.0 * torch.log10(torch.clamp(power @ self.fbank, min=self.amin))
+                db = torch.maximum(db, db.amax(dim=-1).cummax(dim=1).values[..., None] - self.top_db)
+                return db if norm is None else (db - norm[0]) / norm[1]
             if wav.is_cuda and USE_FBANK_WAV:
                 from . import ops
                 if ops.fbank_wav_supported(self.n_fft, self.hop, self.n_mels):     # STFT + mel in one native kernel
