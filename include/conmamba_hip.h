@@ -276,6 +276,13 @@ typedef struct cm_scan_cl_args {
 } cm_scan_cl_args;
 
 int cm_scan_cl_fwd(const cm_scan_cl_args *args);
+/* The same launch with per-slot lengths: sequence b runs its first min(max(lens[b], 0), seqlen) steps from h0 and
+ * leaves the state behind them in h_last; lens[b] == 0: h_last = h0 (zeros without h0), decay = 1.  The steps it runs give the
+ * bits of cm_scan_cl_fwd on that sequence alone with seqlen = lens[b]; inputs at and past step lens[b] are not loaded, `out` rows
+ * there are not written.  lens: `batch` int32 in DEVICE memory, read by the kernel (no host read-back).  xdbl mode, one
+ * direction in forward time, unchunked (time_chunks <= 1), lanes_per_channel 0 or 4, no ckpt; anything else, NULL lens
+ * included, is refused before anything is launched. */
+int cm_scan_cl_fwd_slots(const cm_scan_cl_args *args, const int32_t *lens);
 /* bytes of workspace the launch described by args needs (0 unless time_chunks > 1) */
 int64_t cm_scan_cl_fwd_workspace_bytes(const cm_scan_cl_args *args);
 /* the chunk count that fills 256 CUs for this problem size (1 = do not chunk); a pure function of the sizes */
@@ -734,6 +741,14 @@ typedef struct cm_conv_xproj_uni_args {
 } cm_conv_xproj_uni_args;
 
 int cm_conv_xproj_uni(const cm_conv_xproj_uni_args *args);
+/* The same launch with per-slot lengths: x_hist_out[b] receives the last three rows of [x_hist[b] | x[b, :L]],
+ * L = min(max(lens[b], 0), seqlen) -- x_hist[b] itself for L == 0 -- written by the workgroup whose tile holds row L - 1.  y and
+ * xdbl are computed for all seqlen rows as by cm_conv_xproj_uni; rows at and past L are unspecified, and nothing at or past row
+ * L of x reaches a row in front of it or x_hist_out.  lens: `batch` int32 in DEVICE memory; NULL is refused (CM_EINVAL).
+ * The tile shape follows cm_conv_xproj_uni's rule on (batch, seqlen): at batch * ceil(seqlen / 32) >= 512 the 32-step tiles run, and
+ * xdbl then carries the bits of cm_conv_xproj_uni at the same (batch, seqlen), which differ from those of a batch-1 call (16-step
+ * tiles) within bf16 rounding; y and x_hist_out are the same bits under either shape. */
+int cm_conv_xproj_uni_slots(const cm_conv_xproj_uni_args *args, const int32_t *lens);
 
 /* ---------------------------------------------------------------------------------------
  * Residual add + LayerNorm(s) over the last axis (rows x dim), fused:
@@ -824,6 +839,12 @@ typedef struct cm_glu_dwconv_causal_args {
 } cm_glu_dwconv_causal_args;
 
 int cm_glu_dwconv_ln_gelu_causal(const cm_glu_dwconv_causal_args *args);
+/* The same launch with per-slot lengths: hist_out[b] receives the last ksize - 1 rows of
+ * [hist[b] | gated rows [0, L) of utterance b], L = min(max(lens[b], 0), seqlen) -- hist[b] itself for L == 0 -- written by the
+ * workgroup whose tile holds gated row L - 1 from its staged rows.  `out` is computed for all seqlen rows; rows at and past L are
+ * unspecified, and nothing at or past row L of `in` reaches a row in front of it or hist_out.  lens: `batch` int32 in DEVICE
+ * memory; NULL is refused (CM_EINVAL). */
+int cm_glu_dwconv_ln_gelu_causal_slots(const cm_glu_dwconv_causal_args *args, const int32_t *lens);
 
 /* ---------------------------------------------------------------------------------------
  * Single-step (decode-time) updates of a Mamba mixer: the two calls of bimamba.Mamba.step (reference
@@ -1358,6 +1379,20 @@ typedef struct cm_cnn_front_stream_args {
 } cm_cnn_front_stream_args;
 
 int cm_cnn_front_stream(const cm_cnn_front_stream_args *args);
+
+/* The three streamed front-end launches with per-slot counts: every stream of the batch is at its own sample, ends
+ * its utterance in its own call and may idle.  plan is a (batch, 8) int32 table, row b = {n, consumed, total, f0, nf, r0, nr,
+ * T_total} of stream b with the meanings of the struct fields of the same names; the structs' own n, nf and nr are then the MAXIMA
+ * over the streams -- the widths of chunk (batch, n), db (batch, nf, n_mels), fmax (batch, nf), feats (batch, nf, 80) and out
+ * (batch, nr, 640) -- and their consumed / total / f0 / r0 / T_total are ignored.  plan_host is the table in host memory, checked
+ * here stream by stream with the lock-step entry point's conditions before anything is launched; plan_dev is the same table in
+ * DEVICE memory, read by the kernels.  Grids are sized by the maxima; workgroups past a stream's own frames or rows exit; rows of
+ * db / out past a stream's own count are not written.  A stream with n = 0 or nf = 0 still has its sample history (and, when
+ * cm_fbank_finish_stream_slots runs, its feature history) carried into the spare buffer.  Samples of chunk[b] at and past n[b] are
+ * never read.  Per frame and per row the arithmetic and its bits are those of the lock-step kernels. */
+int cm_fbank_wav_stream_slots(const cm_fbank_stream_args *args, const int32_t *plan_host, const int32_t *plan_dev);
+int cm_fbank_finish_stream_slots(const cm_fbank_stream_args *args, const int32_t *plan_host, const int32_t *plan_dev);
+int cm_cnn_front_stream_slots(const cm_cnn_front_stream_args *args, const int32_t *plan_host, const int32_t *plan_dev);
 
 /* ---------------------------------------------------------------------------------------
  * SpecAugment masking (speechbrain SpectrogramDrop, reference hparams/CTC/conmamba_large.yaml:273-320 and

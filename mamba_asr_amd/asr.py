@@ -117,14 +117,15 @@ class ConMambaASR(nn.Module):
         src = self.CNN(self.features(wavs, wav_lens, epoch, augment))
         return self.Transformer.encode(src, wav_lens)
 
-    def encode_streaming(self, src, context):
+    def encode_streaming(self, src, context, lens=None):
         """The next chunk of the CNN front end's output rows (B, t, F, C) or (B, t, F * C) of the streams in ``context``
         (self.Transformer.make_streaming_context(None, dict(batch_size=B))) -> encoder output (B, t, d_model).  The rows come
         from the whole-utterance front end or, chunk by chunk from the waveform, from frontend_streaming; encode_wav_streaming
-        does both steps."""
-        return self.Transformer.encode_streaming(src, context)
+        does both steps.  ``lens``: a device int32 (B,) tensor, slot b advances by its first lens[b] <= t rows only (0: it idles);
+        output rows at and past lens[b] are unspecified (fused.forward_streaming)."""
+        return self.Transformer.encode_streaming(src, context, lens)
 
-    def make_streaming_context(self, batch_size, dtype=None):
+    def make_streaming_context(self, batch_size, dtype=None, per_slot=False):
         """A blank context for streaming ``batch_size`` utterances in lock step from the waveform: ``.frontend``
         (fused.FrontEndStreamingContext) and ``.encoder`` (self.Transformer.make_streaming_context(None, dict(batch_size=B))), with
         ``reset()`` for the start of the next utterance on all streams.  ``dtype``: the compute dtype of both (default: the
@@ -133,8 +134,10 @@ class ConMambaASR(nn.Module):
         p = self.ctc_lin.w.weight
         if dtype is None:
             dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else p.dtype
-        return fused.ASRStreamingContext(fused.FrontEndStreamingContext(batch_size, p.device, dtype),
-                                         self.Transformer.make_streaming_context(None, dict(batch_size=batch_size, dtype=dtype)))
+        enc = self.Transformer.make_streaming_context(None, dict(batch_size=batch_size, dtype=dtype))
+        if per_slot:       # every slot at its own sample, ending and restarting on its own: encode_wav_slots / log_probs_wav_slots, reset(rows)
+            return fused.SlotASRStreamingContext(fused.SlotFrontEndStreamingContext(batch_size, p.device, dtype), enc)
+        return fused.ASRStreamingContext(fused.FrontEndStreamingContext(batch_size, p.device, dtype), enc)
 
     def frontend_streaming(self, wav_chunk, ctx, last=False):
         """The next samples (B, n), any n >= 0, of the streams in ``ctx`` (make_streaming_context) -> the CNN front end's rows that
@@ -151,14 +154,32 @@ class ConMambaASR(nn.Module):
             return torch.zeros((rows.shape[0], 0, self.cfg.d_model), dtype=torch.float32, device=rows.device)
         return self.encode_streaming(rows, ctx.encoder)
 
+    def encode_wav_slots(self, wav_chunk, n_valid, ctx, last=False):
+        """Every slot at its own pace from the waveform: fused.frontend_streaming_slots (wav_chunk (B, n_max), slot b hands over its
+        first n_valid[b] samples, last[b] ends its utterance) through encode_streaming with the per-slot row counts ->
+        (enc (B, t_max, d_model), row_lens); rows at and past row_lens[b] are unspecified.  ``ctx``: make_streaming_context(B,
+        per_slot=True).  No encoder launch when no slot has a row."""
+        from . import fused
+        rows, row_lens = fused.frontend_streaming_slots(self, wav_chunk, n_valid, ctx.frontend, last)
+        if rows.shape[1] == 0:
+            return torch.zeros((rows.shape[0], 0, self.cfg.d_model), dtype=torch.float32, device=rows.device), row_lens
+        return self.encode_streaming(rows, ctx.encoder, lens=row_lens.dev), row_lens
+
+    def log_probs_wav_slots(self, wav_chunk, n_valid, ctx, last=False):
+        """encode_wav_slots through the CTC head -> (log-probabilities (B, t_max, vocab), row_lens):
+        StreamingCTCBeamSearcher.step(lp, state, lengths=row_lens) takes both as they are."""
+        enc, row_lens = self.encode_wav_slots(wav_chunk, n_valid, ctx, last)
+        return torch.log_softmax(self.ctc_lin(enc), dim=-1), row_lens
+
     def log_probs_wav_streaming(self, wav_chunk, ctx, last=False):
         """encode_wav_streaming's chunk through the CTC head, (B, t, vocab): what ctc_decode.StreamingCTCBeamSearcher.step consumes."""
         return torch.log_softmax(self.ctc_lin(self.encode_wav_streaming(wav_chunk, ctx, last)), dim=-1)
 
-    def log_probs_streaming(self, src, context):
+    def log_probs_streaming(self, src, context, lens=None):
         """encode_streaming's chunk through the CTC head: log_softmax(ctc_lin(encode_streaming(src, context))), (B, t, vocab) --
-        what ctc_decode.StreamingCTCBeamSearcher.step consumes."""
-        return torch.log_softmax(self.ctc_lin(self.encode_streaming(src, context)), dim=-1)
+        what ctc_decode.StreamingCTCBeamSearcher.step consumes; with ``lens`` (per-slot row counts) hand the same tensor to it as
+        ``lengths``."""
+        return torch.log_softmax(self.ctc_lin(self.encode_streaming(src, context, lens)), dim=-1)
 
     def forward_ctc(self, wavs, wav_lens, epoch=0, augment=None, feats=None):
         """-> log-probabilities (B, T', vocab), train_CTC.py:296-302."""

@@ -18,6 +18,8 @@
 // HBM traffic: the features once (each input row is read by the 1-2 waves that need it) and the output once.
 #include "cm_common.h"
 
+#include <type_traits>
+
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -63,9 +65,20 @@ constexpr int T_OPEN = 1 << 29;           // ... and its T / T1 while the uttera
 // row r0 (tile k = rows r0 + 4 k ..: a slot is the padded row index mod NR, whatever the start).  Only the feature addresses,
 // the clamp of the padded row index and the output row differ: block1_row, the MFMA chain and both LayerNorms are the same
 // statements for both instantiations, so a row has the same bits.
+//
+// Per slot (cm_cnn_front_stream_slots; ARGS = cf_slot_args): f0, nf, r0, nr and T_total of stream b come from row b of the (batch, 8)
+// int32 plan table of the front end's per-slot entry points (columns 3 .. 7); the struct's nf and nr are then the maxima over the
+// slots, the row strides of feats and out, and the launch's T / T1 / T2 / tiles_per_utt are replaced per stream.  Chunks of tiles
+// past a stream's own rows are skipped.
+struct cf_slot_args : cm_cnn_front_stream_args {
+    const int32_t *plan;
+};
+
 template <bool STREAM, typename ARGS>
 __global__ __launch_bounds__(512) void cnn_front_kernel(const ARGS p, int T, int T1, int T2, int tiles_per_utt, int chunk, int chunks_per_utt,
                                                         int nchunks) {
+    constexpr bool SLOT = std::is_same<ARGS, cf_slot_args>::value;
+    [[maybe_unused]] int f0s = 0, nfs = 1;                        // SLOT: this stream's first frame and frame count
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     front_lds &L = *reinterpret_cast<front_lds *>(smem);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -111,8 +124,10 @@ __global__ __launch_bounds__(512) void cnn_front_kernel(const ARGS p, int T, int
                 if constexpr (STREAM) {
                     // frame fr of the utterance: in this call's rows from f0 on, in the history behind it.  The clamps hold the address
                     // inside the two arrays for any argument; the entry point's checks make them idle
-                    const int c = fr - p.f0;
-                    r[k] = (c >= 0 || !hist) ? feats[(int64_t)min(max(c, 0), p.nf - 1) * F0 + bin] : hist[(int64_t)max(c + FH, 0) * F0 + bin];
+                    int c, nfl;
+                    if constexpr (SLOT) { c = fr - f0s; nfl = nfs; }
+                    else { c = fr - p.f0; nfl = p.nf; }
+                    r[k] = (c >= 0 || !hist) ? feats[(int64_t)min(max(c, 0), nfl - 1) * F0 + bin] : hist[(int64_t)max(c + FH, 0) * F0 + bin];
                 } else {
                     r[k] = feats[(int64_t)fr * F0 + bin];
                 }
@@ -172,6 +187,16 @@ __global__ __launch_bounds__(512) void cnn_front_kernel(const ARGS p, int T, int
 
     for (int ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
         const int b = ch / chunks_per_utt, tile0 = (ch % chunks_per_utt) * chunk;
+        [[maybe_unused]] int out_rows = 0;                        // SLOT: rows of out per stream (the widest slot's)
+        if constexpr (SLOT) {
+            const int32_t *s = p.plan + (int64_t)b * 8;
+            const int nr = s[6], Tt = s[7];
+            f0s = s[3], nfs = max(s[4], 1), rbase = s[5];
+            T = Tt >= 0 ? Tt : T_OPEN, T1 = Tt >= 0 ? (Tt + 1) / 2 : T_OPEN, T2 = rbase + nr, tp_last = 2 * T2;
+            tiles_per_utt = (nr + TT - 1) / TT;
+            out_rows = p.nr;
+            if (tile0 >= tiles_per_utt) continue;                 // uniform over the workgroup: b depends on ch only
+        }
         const int tile1 = min(tile0 + chunk, tiles_per_utt);
         const float *feats;
         if constexpr (STREAM) {
@@ -235,7 +260,7 @@ __global__ __launch_bounds__(512) void cnn_front_kernel(const ARGS p, int T, int
                     sq = fmaf(vv[k].x, vv[k].x, fmaf(vv[k].y, vv[k].y, sq));
                 }
                 const float rstd = rsqrtf(wave_sum64(sq) * (1.f / nfeat) + p.eps2);
-                uint16_t *dst = out + ((int64_t)b * (T2 - rbase) + (r0 - rbase) + wave) * nfeat;
+                uint16_t *dst = out + ((int64_t)b * (SLOT ? out_rows : T2 - rbase) + (r0 - rbase) + wave) * nfeat;
 #pragma unroll
                 for (int k = 0; k < nfeat / 128; ++k) {
                     const int i = lane + 64 * k;
@@ -330,4 +355,57 @@ extern "C" int cm_cnn_front_stream(const cm_cnn_front_stream_args *args) {
     hipLaunchKernelGGL((cnn_front_kernel<true, cm_cnn_front_stream_args>), dim3((unsigned)grid), dim3(512), sizeof(front_lds),
                        reinterpret_cast<hipStream_t>(a.stream), a, T, T1, (int)rend, tiles_per_utt, chunk, chunks_per_utt, (int)nchunks);
     return cm_launch_status("cm_cnn_front_stream");
+}
+
+extern "C" int cm_cnn_front_stream_slots(const cm_cnn_front_stream_args *args, const int32_t *plan_host, const int32_t *plan_dev) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "cnn_front_stream_slots: args is NULL");
+    CM_REQUIRE(plan_host != nullptr && plan_dev != nullptr, CM_EINVAL, "cnn_front_stream_slots: plan is NULL (host copy and device copy)");
+    CM_REQUIRE(cm_aligned(plan_host, 4) && cm_aligned(plan_dev, 4), CM_EALIGN, "cnn_front_stream_slots: plan must be 4-byte aligned");
+    const cm_cnn_front_stream_args &a = *args;
+    CM_REQUIRE(a.batch > 0 && a.nf > 0 && a.nr > 0 && a.feats && a.w1 && a.ln1_g && a.ln1_b && a.w2 && a.ln2_g && a.ln2_b && a.out, CM_EINVAL,
+               "cnn_front_stream_slots: bad sizes or NULL tensor");
+    CM_REQUIRE(a.F == F0 && a.C1 == C1 && a.C2 == C2, CM_EUNSUPPORTED, "cnn_front_stream_slots: only 80 bins, channels (64, 32) (got F %d, C %d, %d)",
+               a.F, a.C1, a.C2);
+    CM_REQUIRE(cm_aligned(a.w2, 16) && cm_aligned(a.out, 4) && cm_aligned(a.ln1_g, 8) && cm_aligned(a.ln1_b, 8) && cm_aligned(a.ln2_g, 8) &&
+                   cm_aligned(a.ln2_b, 8) && (!a.b2 || cm_aligned(a.b2, 16)),
+               CM_EALIGN, "cnn_front_stream_slots: w2 / b2 must be 16-byte aligned, LayerNorm parameters 8-byte aligned");
+    for (int b = 0; b < a.batch; ++b) {                           // cm_cnn_front_stream's conditions on every slot that has a row
+        const int32_t *s = plan_host + (int64_t)b * 8;
+        const int64_t f0 = s[3], nf = s[4], r0 = s[5], nr = s[6], Tt = s[7];
+        CM_REQUIRE(f0 >= 0 && nf >= 0 && r0 >= 0 && nr >= 0 && nf <= a.nf && nr <= a.nr, CM_EINVAL,
+                   "cnn_front_stream_slots: slot %d: counts below 0 or above the maxima (nf %d of %d, nr %d of %d)", b, (int)nf, a.nf, (int)nr, a.nr);
+        if (nr == 0) continue;
+        const int64_t fend = f0 + nf, rend = r0 + nr;
+        CM_REQUIRE(nf > 0 && fend < T_OPEN, CM_EINVAL, "cnn_front_stream_slots: slot %d has rows but no frames, or a frame index too large", b);
+        if (Tt >= 0) {
+            CM_REQUIRE(Tt >= 5 && Tt == fend, CM_EINVAL, "cnn_front_stream_slots: slot %d: T_total must be f0 + nf and at least 5", b);
+            CM_REQUIRE(rend <= ((Tt + 1) / 2 + 1) / 2, CM_EINVAL, "cnn_front_stream_slots: slot %d: row %d is past the utterance's last", b, (int)rend - 1);
+        } else {
+            CM_REQUIRE(4 * (rend - 1) + 3 < fend, CM_EINVAL, "cnn_front_stream_slots: slot %d: row %d needs frames that have not arrived", b, (int)rend - 1);
+        }
+        const int64_t lowest = std::min<int64_t>(std::max<int64_t>(4 * r0 - 3, 0), Tt >= 0 ? Tt - 5 : fend);
+        CM_REQUIRE(lowest >= (a.feat_hist ? f0 - FH : f0), CM_EINVAL, "cnn_front_stream_slots: slot %d: row %d reaches behind the feature history", b, (int)r0);
+    }
+    const int tiles_per_utt = (a.nr + TT - 1) / TT;
+    const int chunk = 16;
+    const int chunks_per_utt = (tiles_per_utt + chunk - 1) / chunk;
+    const int64_t nchunks = (int64_t)a.batch * chunks_per_utt;
+    CM_REQUIRE(nchunks <= 2147483647, CM_EINVAL, "cnn_front_stream_slots: too many chunks");
+    static bool attr_done = false;
+    if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(cnn_front_kernel<true, cf_slot_args>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        if (e != hipSuccess) {
+            cm_set_error("cnn_front_stream_slots: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+            return (int)e;
+        }
+        attr_done = true;
+    }
+    cf_slot_args k{};
+    static_cast<cm_cnn_front_stream_args &>(k) = a;
+    k.plan = plan_dev;
+    const int64_t grid = nchunks < 256 ? nchunks : 256;
+    hipLaunchKernelGGL((cnn_front_kernel<true, cf_slot_args>), dim3((unsigned)grid), dim3(512), sizeof(front_lds),
+                       reinterpret_cast<hipStream_t>(a.stream), k, T_OPEN, T_OPEN, 0, tiles_per_utt, chunk, chunks_per_utt, (int)nchunks);
+    return cm_launch_status("cm_cnn_front_stream_slots");
 }

@@ -55,11 +55,16 @@ struct cx_uni_args : cm_conv_xproj_args {
     const void *x_hist;
     void *x_hist_out;
 };
+// ... and of its per-slot form (cm_conv_xproj_uni_slots): utterance b has lens[b] valid rows, clamped to [0, seqlen]
+struct cx_slot_args : cx_uni_args {
+    const int32_t *lens;
+};
 
 // NB: 16-column bands of x_dbl per direction: 3 = [dt16 | B | C], 4 = [dt32 | B | C] (dt_rank 17..32: the S2S-large encoder)
 template <int TT, int NB, typename P = cm_conv_xproj_args>
 __global__ __launch_bounds__(256, (TT == 16 && NB == 3) ? 4 : 2) void conv_xproj_kernel(const P p, const int ntile, const int stamp_arg = 0) {
-    constexpr bool UNI = std::is_same<P, cx_uni_args>::value;     // one direction, rows in front of the chunk from p.x_hist
+    constexpr bool UNI = std::is_base_of<cx_uni_args, P>::value;  // one direction, rows in front of the chunk from p.x_hist
+    constexpr bool SLOT = std::is_same<P, cx_slot_args>::value;   // the new history is cut behind row lens[b] - 1, not behind row T - 1
     constexpr int HR = UNI ? 0 : W - 1;                           // rows behind a step that its outputs read
     constexpr int NR = (W - 1) + HR, NWIN = NR + 1;               // halo rows per run of steps; rows of the sliding window
 #ifdef CM_ABLATE
@@ -98,10 +103,17 @@ __global__ __launch_bounds__(256, (TT == 16 && NB == 3) ? 4 : 2) void conv_xproj
         hr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(reinterpret_cast<const uint16_t *>(p.x_hist) + (int64_t)b * (W - 1) * E), 0,
                                                p.x_hist ? (W - 1) * E * 2 : 0, 0x00020000);
         // the last W-1 rows of [x_hist | x], by the workgroup of the utterance's last tile (x_hist_out never aliases x_hist: checked at entry)
-        if (p.x_hist_out && id % ntile == ntile - 1) {
+        // SLOT: of [x_hist | x[:lens[b]]], by the workgroup whose tile holds row lens[b] - 1 (tile 0 for an idle slot, which so carries
+        // its history over into the spare buffer); rows at and past lens[b] are not read here
+        int TL = T, writer = ntile - 1;
+        if constexpr (SLOT) {
+            TL = min(max(p.lens[b], 0), T);
+            writer = TL > 0 ? (TL - 1) / TT : 0;
+        }
+        if (p.x_hist_out && id % ntile == writer) {
             uint16_t *ho = reinterpret_cast<uint16_t *>(p.x_hist_out) + (int64_t)b * (W - 1) * E;
             for (int idx = tid; idx < (W - 1) * (E / 4); idx += 256) {
-                const int j = idx / (E / 4), c0 = (idx % (E / 4)) * 4, t = T - (W - 1) + j;
+                const int j = idx / (E / 4), c0 = (idx % (E / 4)) * 4, t = TL - (W - 1) + j;
                 const u32x2 v = t >= 0 ? __builtin_amdgcn_raw_buffer_load_b64(xr, c0 * 2, t * x_ts, 0)
                                        : __builtin_amdgcn_raw_buffer_load_b64(hr, c0 * 2, (t + W - 1) * E * 2, 0);
                 *reinterpret_cast<u32x2 *>(ho + j * E + c0) = v;
@@ -294,7 +306,7 @@ __global__ __launch_bounds__(256, (TT == 16 && NB == 3) ? 4 : 2) void conv_xproj
 
 template <int TT, int NB, typename P>
 int launch_cx(const P &a) {
-    constexpr int ND = std::is_same<P, cx_uni_args>::value ? 1 : 2;
+    constexpr int ND = std::is_base_of<cx_uni_args, P>::value ? 1 : 2;
     // the token tiles, and at least the K halves' exchange area that overlays them (64 lanes x TT / 16 x NB accumulators per direction)
     const size_t tiles = (size_t)ND * TT * (a.dim + 16) * sizeof(uint16_t), xch = (size_t)ND * 64 * (TT / 16) * NB * 16;
     const size_t smem = tiles > xch ? tiles : xch;
@@ -311,7 +323,7 @@ int launch_cx(const P &a) {
     const int ntile = (a.seqlen + TT - 1) / TT;
     CM_REQUIRE((long)ntile * a.batch < (1L << 31), CM_EINVAL, "conv_xproj: grid too large");
     hipLaunchKernelGGL((conv_xproj_kernel<TT, NB, P>), dim3((unsigned)(ntile * a.batch)), dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), a, ntile, cm_debug_get() == 18 ? 1 : (cm_debug_get() == 19 ? 2 : 0));
-    return cm_launch_status(ND == 1 ? "cm_conv_xproj_uni" : "cm_conv_xproj");
+    return cm_launch_status(std::is_same<P, cx_slot_args>::value ? "cm_conv_xproj_uni_slots" : ND == 1 ? "cm_conv_xproj_uni" : "cm_conv_xproj");
 }
 
 }  // namespace
@@ -344,9 +356,8 @@ extern "C" int cm_conv_xproj(const cm_conv_xproj_args *args) {
     return wide ? launch_cx<32, 3>(a) : launch_cx<16, 3>(a);
 }
 
-extern "C" int cm_conv_xproj_uni(const cm_conv_xproj_uni_args *args) {
-    CM_REQUIRE(args != nullptr, CM_EINVAL, "conv_xproj_uni: args is NULL");
-    const cm_conv_xproj_uni_args &u = *args;
+// cm_conv_xproj_uni (lens == NULL) and cm_conv_xproj_uni_slots: one set of checks, one choice of tile shape
+static int conv_xproj_uni_entry(const cm_conv_xproj_uni_args &u, const int32_t *lens) {
     CM_REQUIRE(u.batch > 0 && u.seqlen > 0 && u.dim > 0 && u.x && u.weight && u.wx && u.y && u.xdbl, CM_EINVAL,
                "conv_xproj_uni: bad sizes or NULL tensor");
     CM_REQUIRE(u.width == W, CM_EUNSUPPORTED, "conv_xproj_uni: conv width %d unsupported (4 only)", u.width);
@@ -369,6 +380,25 @@ extern "C" int cm_conv_xproj_uni(const cm_conv_xproj_uni_args *args) {
     a.x_hist = u.x_hist, a.x_hist_out = u.x_hist_out;
     // tile shape by cm_conv_xproj's rule, on one direction's LDS tile
     const bool wide = a.variant != 1 && (size_t)32 * (a.dim + 16) * 2 <= 36 * 1024 && (long)a.batch * ((a.seqlen + 31) / 32) >= 512;
+    if (lens) {
+        cx_slot_args s{};
+        static_cast<cx_uni_args &>(s) = a;
+        s.lens = lens;
+        if (a.dt_pad == 32) return wide ? launch_cx<32, 4>(s) : launch_cx<16, 4>(s);
+        return wide ? launch_cx<32, 3>(s) : launch_cx<16, 3>(s);
+    }
     if (a.dt_pad == 32) return wide ? launch_cx<32, 4>(a) : launch_cx<16, 4>(a);
     return wide ? launch_cx<32, 3>(a) : launch_cx<16, 3>(a);
+}
+
+extern "C" int cm_conv_xproj_uni(const cm_conv_xproj_uni_args *args) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "conv_xproj_uni: args is NULL");
+    return conv_xproj_uni_entry(*args, nullptr);
+}
+
+extern "C" int cm_conv_xproj_uni_slots(const cm_conv_xproj_uni_args *args, const int32_t *lens) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "conv_xproj_uni_slots: args is NULL");
+    CM_REQUIRE(lens != nullptr, CM_EINVAL, "conv_xproj_uni_slots: lens is NULL (cm_conv_xproj_uni is the lock-step form)");
+    CM_REQUIRE(cm_aligned(lens, 4), CM_EALIGN, "conv_xproj_uni_slots: lens must be 4-byte aligned");
+    return conv_xproj_uni_entry(*args, lens);
 }

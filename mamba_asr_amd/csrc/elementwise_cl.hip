@@ -196,6 +196,24 @@ struct dw_causal_args : cm_glu_dwconv_args {
     const void *hist;
     void *hist_out;
 };
+// ... and of its per-slot form (cm_glu_dwconv_ln_gelu_causal_slots): utterance b has lens[b] valid rows, clamped to [0, seqlen]
+struct dw_slot_args : dw_causal_args {
+    const int32_t *lens;
+};
+
+// Whether this workgroup (time tile `tile` of TT steps) writes utterance b's hist_out, and the row count T_cut the history is cut
+// behind.  Lock step: the last tile, seqlen.  Per slot: the tile that holds gated row lens[b] - 1 -- it has the K - 1 rows in front
+// staged as its halo -- and lens[b]; tile 0 for an idle slot, which so copies hist to hist_out.
+template <typename P>
+__device__ __forceinline__ bool dw_hist_writer(const P &p, int b, int tile, int ntile, int TT, int &T_cut) {
+    if constexpr (std::is_same<P, dw_slot_args>::value) {
+        T_cut = min(max(p.lens[b], 0), p.seqlen);
+        return tile == (T_cut > 0 ? (T_cut - 1) / TT : 0);
+    } else {
+        T_cut = p.seqlen;
+        return tile == ntile - 1;
+    }
+}
 
 // hist_out <- the staged rows T - (K - 1) .. T - 1 (history rows where T < K - 1) of the utterance's LAST tile, which holds rows
 // t0 - (K - 1) .. t0 + TT - 1 in LDS at g (row stride D elements): row j of hist_out is staged row T - t0 + j.
@@ -211,7 +229,7 @@ __device__ __forceinline__ void dw_store_hist(const EL *g, EL *hist_out, int b, 
 
 template <typename IO, int K, int TT, typename P = cm_glu_dwconv_args>
 __global__ __launch_bounds__(256) void glu_dwconv_kernel(const P p) {
-    constexpr bool CAUSAL = std::is_same<P, dw_causal_args>::value;
+    constexpr bool CAUSAL = std::is_base_of<dw_causal_args, P>::value;
     constexpr int PL = CAUSAL ? K - 1 : K / 2;                    // padding rows in front
     constexpr int tt = TT;
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -275,7 +293,8 @@ __global__ __launch_bounds__(256) void glu_dwconv_kernel(const P p) {
     }
     __syncthreads();
     if constexpr (CAUSAL) {
-        if (p.hist_out && blockIdx.x == gridDim.x - 1) dw_store_hist<IO, K>(g, reinterpret_cast<IO *>(p.hist_out), b, D, T, t0);
+        int T_cut;
+        if (p.hist_out && dw_hist_writer(p, b, blockIdx.x, gridDim.x, tt, T_cut)) dw_store_hist<IO, K>(g, reinterpret_cast<IO *>(p.hist_out), b, D, T_cut, t0);
     }
     // phase 2: depthwise conv along time
     for (int c = threadIdx.x; c < D; c += blockDim.x) {
@@ -377,7 +396,7 @@ typedef __attribute__((ext_vector_type(4))) float dw_f32x4;
 
 template <int K, int TT, int DV, bool LIN = false, typename P = cm_glu_dwconv_args>
 __global__ __launch_bounds__(256, DV == 4 ? 4 : 2) void dwconv_rows_kernel(const P p) {
-    constexpr bool CAUSAL = std::is_same<P, dw_causal_args>::value;
+    constexpr bool CAUSAL = std::is_base_of<dw_causal_args, P>::value;
     constexpr int PL = CAUSAL ? K - 1 : K / 2;                    // padding rows in front
     constexpr int D = DV * 64, NIN = TT + K - 1, TH = TT / 2, CS = D + 16, NIT = (D / 2 + 127) / 128;
     constexpr int XS = D + 8;                                     // LIN: activation row stride in bf16 elements
@@ -440,7 +459,8 @@ __global__ __launch_bounds__(256, DV == 4 ? 4 : 2) void dwconv_rows_kernel(const
     }
     __syncthreads();
     if constexpr (CAUSAL) {                                       // g is read only until the barrier behind phase 2
-        if (p.hist_out && blockIdx.x == gridDim.x - 1) dw_store_hist<uint16_t, K>(g, reinterpret_cast<uint16_t *>(p.hist_out), b, D, T, t0);
+        int T_cut;
+        if (p.hist_out && dw_hist_writer(p, b, blockIdx.x, gridDim.x, TT, T_cut)) dw_store_hist<uint16_t, K>(g, reinterpret_cast<uint16_t *>(p.hist_out), b, D, T_cut, t0);
     }
     // phase 2: depthwise conv, two channels x TH steps per thread, accumulated by input row
     const int rh = tid >> 7;                                      // wave-uniform
@@ -778,10 +798,12 @@ extern "C" int cm_add_layernorm(const cm_add_ln_args *args) {
 
 namespace {
 
-// cm_glu_dwconv_ln_gelu (P = cm_glu_dwconv_args) and cm_glu_dwconv_ln_gelu_causal (P = dw_causal_args): one selection of kernels
+// cm_glu_dwconv_ln_gelu (P = cm_glu_dwconv_args), cm_glu_dwconv_ln_gelu_causal (P = dw_causal_args) and
+// cm_glu_dwconv_ln_gelu_causal_slots (P = dw_slot_args): one selection of kernels
 template <typename P>
 int glu_dwconv_dispatch(const P &a) {
-    constexpr bool CAUSAL = std::is_same<P, dw_causal_args>::value;
+    constexpr bool CAUSAL = std::is_base_of<dw_causal_args, P>::value;
+    constexpr bool SLOT = std::is_same<P, dw_slot_args>::value;
     CM_REQUIRE(a.batch > 0 && a.seqlen > 0 && a.dim > 0 && a.in && a.out && a.weight && a.ln_g && a.ln_b, CM_EINVAL,
                "glu_dwconv: bad sizes or NULL tensor");
     CM_REQUIRE(a.ksize == 31, CM_EUNSUPPORTED, "glu_dwconv: kernel size %d unsupported (31 only)", a.ksize);
@@ -815,7 +837,7 @@ int glu_dwconv_dispatch(const P &a) {
                 if (e != hipSuccess) { cm_set_error("glu_dwconv: LDS attribute failed: %s", hipGetErrorString(e)); return (int)e; }
             }
             hipLaunchKernelGGL(kern, grid, dim3(256), smem, st0, a);
-            return cm_launch_status(CAUSAL ? "cm_glu_dwconv_ln_gelu_causal(rows)" : "cm_glu_dwconv_ln_gelu(rows)");
+            return cm_launch_status(SLOT ? "cm_glu_dwconv_ln_gelu_causal_slots(rows)" : CAUSAL ? "cm_glu_dwconv_ln_gelu_causal(rows)" : "cm_glu_dwconv_ln_gelu(rows)");
         };
         if (lin) return run(dwconv_rows_kernel<31, TT, 4, true, P>);
         return a.dim == 256 ? run(dwconv_rows_kernel<31, TT, 4, false, P>) : run(dwconv_rows_kernel<31, TT, 8, false, P>);
@@ -836,7 +858,7 @@ int glu_dwconv_dispatch(const P &a) {
             if (e != hipSuccess) { cm_set_error("glu_dwconv: LDS attribute failed: %s", hipGetErrorString(e)); return (int)e; }
         }
         hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, a);
-        return cm_launch_status(CAUSAL ? "cm_glu_dwconv_ln_gelu_causal" : "cm_glu_dwconv_ln_gelu");
+        return cm_launch_status(SLOT ? "cm_glu_dwconv_ln_gelu_causal_slots" : CAUSAL ? "cm_glu_dwconv_ln_gelu_causal" : "cm_glu_dwconv_ln_gelu");
     };
     if (a.io_dtype == CM_BF16) {
         if (tt == 16) return go(glu_dwconv_kernel<cm_bf16, 31, 16, P>);
@@ -855,13 +877,26 @@ extern "C" int cm_glu_dwconv_ln_gelu(const cm_glu_dwconv_args *args) {
     return glu_dwconv_dispatch(*args);
 }
 
-extern "C" int cm_glu_dwconv_ln_gelu_causal(const cm_glu_dwconv_causal_args *args) {
-    CM_REQUIRE(args != nullptr, CM_EINVAL, "glu_dwconv: args is NULL");
-    const cm_glu_dwconv_causal_args &u = *args;
-    dw_causal_args a{};
+static void dw_causal_fill(dw_causal_args &a, const cm_glu_dwconv_causal_args &u) {
     a.batch = u.batch, a.seqlen = u.seqlen, a.dim = u.dim, a.ksize = u.ksize, a.io_dtype = u.io_dtype, a.glu_done = u.glu_done;
     a.in = u.in, a.weight = u.weight, a.bias = u.bias, a.ln_g = u.ln_g, a.ln_b = u.ln_b, a.eps = u.eps, a.variant = u.variant;
     a.out = u.out, a.stream = u.stream, a.weight_t = u.weight_t, a.lin_w = u.lin_w, a.lin_b = u.lin_b;
     a.hist = u.hist, a.hist_out = u.hist_out;
+}
+
+extern "C" int cm_glu_dwconv_ln_gelu_causal(const cm_glu_dwconv_causal_args *args) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "glu_dwconv: args is NULL");
+    dw_causal_args a{};
+    dw_causal_fill(a, *args);
+    return glu_dwconv_dispatch(a);
+}
+
+extern "C" int cm_glu_dwconv_ln_gelu_causal_slots(const cm_glu_dwconv_causal_args *args, const int32_t *lens) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "glu_dwconv_causal_slots: args is NULL");
+    CM_REQUIRE(lens != nullptr, CM_EINVAL, "glu_dwconv_causal_slots: lens is NULL (cm_glu_dwconv_ln_gelu_causal is the lock-step form)");
+    CM_REQUIRE(cm_aligned(lens, 4), CM_EALIGN, "glu_dwconv_causal_slots: lens must be 4-byte aligned");
+    dw_slot_args a{};
+    dw_causal_fill(a, *args);
+    a.lens = lens;
     return glu_dwconv_dispatch(a);
 }

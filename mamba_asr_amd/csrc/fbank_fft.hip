@@ -16,6 +16,8 @@
 //   * |X[k]|^2 goes to the [bin][frame] power tile in LDS and the mel / dB stage of cm_fbank_mel_db runs unchanged.
 #include "cm_common.h"
 
+#include <type_traits>
+
 namespace {
 
 constexpr int FT = 16;            // frames per workgroup (4 per wave)
@@ -61,10 +63,32 @@ __device__ __forceinline__ int rev4_8bit(int k) {                     // reverse
 // STREAM (cm_fbank_wav_stream; ARGS = cm_fbank_stream_args): the launch covers frames [f0, f0 + nf) of an utterance whose samples
 // arrive in chunks.  Only the sample fetch, the store addresses and the per-frame maxima differ: the window, the four stages,
 // the split step and the mel loop below are the same statements for both instantiations, so a frame has the same bits.
+//
+// Per slot (cm_fbank_wav_stream_slots; ARGS = fb_slot_args): n, consumed, total, f0 and nf of stream b come from row b of a (batch, 8)
+// int32 plan table instead of the struct, whose n and nf are then the maxima over the slots: the widths of chunk and of db / fmax
+// and the size of the grid.  Workgroups past a slot's own frames exit; workgroup 0 rolls the sample history of every slot, idle or not.
+struct fb_slot_args : cm_fbank_stream_args {
+    const int32_t *plan;
+};
+enum { PL_N = 0, PL_CONSUMED = 1, PL_TOTAL = 2, PL_F0 = 3, PL_NF = 4, PL_R0 = 5, PL_NR = 6, PL_TTOTAL = 7, PL_W = 8 };
+template <typename ARGS>
+__device__ __forceinline__ ARGS fb_view(const ARGS &pk, int b) {      // the arguments as stream b sees them
+    if constexpr (std::is_same<ARGS, fb_slot_args>::value) {
+        ARGS q = pk;
+        const int32_t *s = pk.plan + (int64_t)b * PL_W;
+        q.n = s[PL_N], q.consumed = s[PL_CONSUMED], q.total = s[PL_TOTAL], q.f0 = s[PL_F0], q.nf = s[PL_NF];
+        return q;
+    } else {
+        return pk;
+    }
+}
+
 template <bool STREAM, typename ARGS>
-__global__ __launch_bounds__(256) void fbank_wav_kernel(const ARGS p, const float floor_db) {
+__global__ __launch_bounds__(256) void fbank_wav_kernel(const ARGS pk, const float floor_db) {
     extern __shared__ float sm[];
+    constexpr bool SLOT = std::is_same<ARGS, fb_slot_args>::value;
     const int b = blockIdx.y;
+    const ARGS p = fb_view(pk, b);
     int t0, T;                                                    // first frame of this workgroup, end of the valid frames
     if constexpr (STREAM) { t0 = p.f0 + blockIdx.x * FT; T = p.f0 + p.nf; }
     else { t0 = blockIdx.x * FT; T = p.frames; }
@@ -89,7 +113,7 @@ __global__ __launch_bounds__(256) void fbank_wav_kernel(const ARGS p, const floa
     if constexpr (STREAM) {
         if (blockIdx.x == 0)                                      // the next call's history: the last HS samples of [hist | chunk]
             for (int j = tid; j < HS; j += 256) p.hist_out[(int64_t)b * HS + j] = __uint_as_float(sample(p.consumed + p.n - HS + j));
-        if (p.nf == 0) return;
+        if (p.nf == 0 || (SLOT && t0 >= T)) return;
     }
     for (int m = tid; m < M; m += 256) { band[m] = p.band_lo[m]; band[M + m] = p.band_hi[m]; }
     for (int m = tid; m <= M; m += 256) band[2 * M + m] = p.band_off[m];
@@ -231,7 +255,7 @@ __global__ __launch_bounds__(256) void fbank_wav_kernel(const ARGS p, const floa
     {
         const int nrow = min(FT, T - t0);                         // rows t0 .. t0 + nrow - 1 are contiguous in db: one linear copy
         float *dst;
-        if constexpr (STREAM) dst = p.db + ((int64_t)b * p.nf + (t0 - p.f0)) * M;
+        if constexpr (STREAM) dst = p.db + ((int64_t)b * pk.nf + (t0 - p.f0)) * M;
         else dst = p.db + ((int64_t)b * T + t0) * M;
         for (int i = tid; i < nrow * M; i += 256) dst[i] = dbt[i];
     }
@@ -242,7 +266,7 @@ __global__ __launch_bounds__(256) void fbank_wav_kernel(const ARGS p, const floa
             for (int m = lane; m < M; m += 64) mx = fmaxf(mx, dbt[j * M + m]);
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-            if (lane == 0 && t0 + j < T) p.fmax[(int64_t)b * p.nf + (t0 - p.f0) + j] = mx;
+            if (lane == 0 && t0 + j < T) p.fmax[(int64_t)b * pk.nf + (t0 - p.f0) + j] = mx;
         }
         return;
     }
@@ -275,6 +299,33 @@ __global__ __launch_bounds__(256) void fbank_finish_stream_kernel(const cm_fbank
         }
     }
     if (p.feat_hist_out && g < G)                                 // rows the call did not fill: the old history moved up, zeros in front of frame 0
+        for (int j = g; j < FH - nf; j += G)
+            p.feat_hist_out[((int64_t)b * FH + j) * M + m] = (p.feat_hist && p.f0 + nf - FH + j >= 0) ? p.feat_hist[((int64_t)b * FH + j + nf) * M + m] : 0.f;
+    if (threadIdx.x == 0) p.umax[b] = run;
+}
+
+// cm_fbank_finish_stream_slots: the same per stream with f0 and nf from the plan table; db and fmax rows are pk.nf (the maximum) apart.
+// A slot without frames still rolls its feature history: the loop below then copies feat_hist to feat_hist_out.
+__global__ __launch_bounds__(256) void fbank_finish_slots_kernel(const fb_slot_args pk) {
+    const int b = blockIdx.x;
+    const fb_slot_args p = fb_view(pk, b);
+    const int M = p.n_mels, nf = p.nf;
+    const int G = 256 / M, g = threadIdx.x / M, m = threadIdx.x - g * M;
+    float run = p.umax[b];
+    __syncthreads();
+    const float *fm = p.fmax + (int64_t)b * pk.nf;
+    float *db = p.db + (int64_t)b * pk.nf * M;
+    const float mean = p.mean && g < G ? p.mean[m] : 0.f, sd = p.mean && g < G ? p.std[m] : 1.f;
+    for (int i = 0; i < nf; ++i) {
+        run = fmaxf(run, fm[i]);
+        if (g < G && i % G == g) {
+            float v = fmaxf(db[(int64_t)i * M + m], run - p.top_db);
+            if (p.mean) v = (v - mean) / sd;
+            db[(int64_t)i * M + m] = v;
+            if (p.feat_hist_out && i >= nf - FH) p.feat_hist_out[((int64_t)b * FH + (i - (nf - FH))) * M + m] = v;
+        }
+    }
+    if (p.feat_hist_out && g < G)
         for (int j = g; j < FH - nf; j += G)
             p.feat_hist_out[((int64_t)b * FH + j) * M + m] = (p.feat_hist && p.f0 + nf - FH + j >= 0) ? p.feat_hist[((int64_t)b * FH + j + nf) * M + m] : 0.f;
     if (threadIdx.x == 0) p.umax[b] = run;
@@ -351,4 +402,64 @@ extern "C" int cm_fbank_finish_stream(const cm_fbank_stream_args *args) {
     CM_REQUIRE(a.feat_hist_out || !a.feat_hist, CM_EINVAL, "fbank_finish_stream: feat_hist without feat_hist_out");
     hipLaunchKernelGGL(fbank_finish_stream_kernel, dim3(a.batch), dim3(256), 0, reinterpret_cast<hipStream_t>(a.stream), a);
     return cm_launch_status("cm_fbank_finish_stream");
+}
+
+
+namespace {
+// the per-slot entry points' view of slot b for the host checks: the lock-step struct with that slot's scalars
+cm_fbank_stream_args fb_host_view(const cm_fbank_stream_args &a, const int32_t *plan, int b) {
+    cm_fbank_stream_args q = a;
+    const int32_t *s = plan + (int64_t)b * PL_W;
+    q.n = s[PL_N], q.consumed = s[PL_CONSUMED], q.total = s[PL_TOTAL], q.f0 = s[PL_F0], q.nf = s[PL_NF];
+    return q;
+}
+}  // namespace
+
+extern "C" int cm_fbank_wav_stream_slots(const cm_fbank_stream_args *args, const int32_t *plan_host, const int32_t *plan_dev) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_wav_stream_slots: args is NULL");
+    CM_REQUIRE(plan_host != nullptr && plan_dev != nullptr, CM_EINVAL, "fbank_wav_stream_slots: plan is NULL (host copy and device copy)");
+    CM_REQUIRE(cm_aligned(plan_host, 4) && cm_aligned(plan_dev, 4), CM_EALIGN, "fbank_wav_stream_slots: plan must be 4-byte aligned");
+    const cm_fbank_stream_args &a = *args;
+    CM_REQUIRE(a.batch > 0 && a.n >= 0 && a.nf >= 0, CM_EINVAL, "fbank_wav_stream_slots: bad sizes");
+    for (int b = 0; b < a.batch; ++b) {                           // every slot passes the lock-step checks on its own counts
+        const cm_fbank_stream_args q = fb_host_view(a, plan_host, b);
+        if (int rc = fbank_stream_check(q, "fbank_wav_stream_slots", true)) return rc;
+        CM_REQUIRE(q.n <= a.n && q.nf <= a.nf, CM_EINVAL, "fbank_wav_stream_slots: slot %d has n %d / nf %d above the maxima %d / %d", b, q.n, q.nf, a.n, a.nf);
+    }
+    CM_REQUIRE(a.hist && a.hist_out && (a.n == 0 || a.chunk), CM_EINVAL, "fbank_wav_stream_slots: NULL chunk / hist / hist_out");
+    CM_REQUIRE(!overlap(a.hist, a.hist_out, (size_t)a.batch * HS * 4), CM_EINVAL, "fbank_wav_stream_slots: hist_out overlaps hist");
+    CM_REQUIRE(a.nf == 0 || (a.window && a.twiddle && a.db && a.fmax && a.band_lo && a.band_hi && a.band_off && a.band_w), CM_EINVAL,
+               "fbank_wav_stream_slots: NULL tensor");
+    CM_REQUIRE(a.nf == 0 || (cm_aligned(a.window, 8) && cm_aligned(a.twiddle, 8)), CM_EALIGN, "fbank_wav_stream_slots: window / twiddle must be 8-byte aligned");
+    fb_slot_args k{};
+    static_cast<cm_fbank_stream_args &>(k) = a;
+    k.plan = plan_dev;
+    const size_t smem = (size_t)(NH + 1) * PWS * 4 + (size_t)(3 * a.n_mels + 1) * 4 + (size_t)BWCAP * 4 + (size_t)4 * ZN * 8 + 4;
+    dim3 grid(a.nf ? (a.nf + FT - 1) / FT : 1, a.batch);
+    hipLaunchKernelGGL((fbank_wav_kernel<true, fb_slot_args>), grid, dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), k,
+                       (float)(10.0 * log10((double)a.amin)));
+    return cm_launch_status("cm_fbank_wav_stream_slots");
+}
+
+extern "C" int cm_fbank_finish_stream_slots(const cm_fbank_stream_args *args, const int32_t *plan_host, const int32_t *plan_dev) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_finish_stream_slots: args is NULL");
+    CM_REQUIRE(plan_host != nullptr && plan_dev != nullptr, CM_EINVAL, "fbank_finish_stream_slots: plan is NULL (host copy and device copy)");
+    CM_REQUIRE(cm_aligned(plan_host, 4) && cm_aligned(plan_dev, 4), CM_EALIGN, "fbank_finish_stream_slots: plan must be 4-byte aligned");
+    const cm_fbank_stream_args &a = *args;
+    CM_REQUIRE(a.batch > 0, CM_EINVAL, "fbank_finish_stream_slots: bad sizes");
+    for (int b = 0; b < a.batch; ++b) {
+        const cm_fbank_stream_args q = fb_host_view(a, plan_host, b);
+        if (int rc = fbank_stream_check(q, "fbank_finish_stream_slots", false)) return rc;
+        CM_REQUIRE(q.nf <= a.nf, CM_EINVAL, "fbank_finish_stream_slots: slot %d has nf %d above the maximum %d", b, q.nf, a.nf);
+    }
+    CM_REQUIRE(a.nf > 0 && a.db && a.fmax && a.umax, CM_EINVAL, "fbank_finish_stream_slots: no frames or NULL db / fmax / umax");
+    CM_REQUIRE(!a.mean == !a.std, CM_EINVAL, "fbank_finish_stream_slots: mean and std go together");
+    CM_REQUIRE(!a.feat_hist_out || !a.feat_hist || !overlap(a.feat_hist, a.feat_hist_out, (size_t)a.batch * FH * a.n_mels * 4), CM_EINVAL,
+               "fbank_finish_stream_slots: feat_hist_out overlaps feat_hist");
+    CM_REQUIRE(a.feat_hist_out || !a.feat_hist, CM_EINVAL, "fbank_finish_stream_slots: feat_hist without feat_hist_out");
+    fb_slot_args k{};
+    static_cast<cm_fbank_stream_args &>(k) = a;
+    k.plan = plan_dev;
+    hipLaunchKernelGGL(fbank_finish_slots_kernel, dim3(a.batch), dim3(256), 0, reinterpret_cast<hipStream_t>(a.stream), k);
+    return cm_launch_status("cm_fbank_finish_stream_slots");
 }

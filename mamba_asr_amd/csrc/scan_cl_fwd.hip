@@ -403,7 +403,7 @@ int by_split(const cm_scan_cl_args &a, int ns) {
 
 }  // namespace
 
-int cm_scan_rows_fwd(const cm_scan_cl_args &a);      // scan_rows_fwd.hip
+int cm_scan_rows_fwd(const cm_scan_cl_args &a, const int32_t *lens);      // scan_rows_fwd.hip; lens: per-slot lengths or NULL
 
 #ifdef CM_ABLATE
 extern "C" int cm_debug_set(int v) { return g_debug.exchange(v); }
@@ -424,7 +424,7 @@ extern "C" int cm_scan_cl_fwd(const cm_scan_cl_args *args) {
         int with_rows = 0;
         for (int i = 0; i < a.ndir; ++i) with_rows += a.dir[i].xdbl != nullptr;
         CM_REQUIRE(with_rows == 0 || with_rows == a.ndir, CM_EINVAL, "scan_cl_fwd: xdbl must be set for every direction or none");
-        if (with_rows) return cm_scan_rows_fwd(a);
+        if (with_rows) return cm_scan_rows_fwd(a, nullptr);
     }
     CM_REQUIRE(a.time_chunks <= 1, CM_EUNSUPPORTED, "scan_cl_fwd: time_chunks is built for the xdbl mode only");
     CM_REQUIRE(a.batch <= 65535, CM_EINVAL, "scan_cl_fwd: batch %d exceeds the grid limit", a.batch);
@@ -447,4 +447,16 @@ extern "C" int cm_scan_cl_fwd(const cm_scan_cl_args *args) {
             cm_set_error("scan_cl_fwd: unsupported io dtype %d", a.io_dtype);
             return CM_EUNSUPPORTED;
     }
+}
+
+extern "C" int cm_scan_cl_fwd_slots(const cm_scan_cl_args *args, const int32_t *lens) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "scan_cl_fwd_slots: args is NULL");
+    CM_REQUIRE(lens != nullptr, CM_EINVAL, "scan_cl_fwd_slots: lens is NULL (cm_scan_cl_fwd is the lock-step form)");
+    const cm_scan_cl_args &a = *args;
+    CM_REQUIRE(a.batch > 0 && a.dim > 0 && a.seqlen > 0, CM_EINVAL, "scan_cl_fwd_slots: bad sizes batch=%d dim=%d seqlen=%d",
+               a.batch, a.dim, a.seqlen);
+    CM_REQUIRE(a.dstate == 16, CM_EUNSUPPORTED, "scan_cl_fwd_slots: dstate %d unsupported (16 only)", a.dstate);
+    CM_REQUIRE(a.ndir == 1 || a.ndir == 2, CM_EINVAL, "scan_cl_fwd_slots: ndir must be 1 or 2");
+    CM_REQUIRE(a.dir[0].xdbl != nullptr, CM_EUNSUPPORTED, "scan_cl_fwd_slots: built for the xdbl mode (the row-group kernel) only");
+    return cm_scan_rows_fwd(a, lens);
 }

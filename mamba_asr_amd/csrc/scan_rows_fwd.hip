@@ -47,6 +47,11 @@ struct rows_plan {
     int need_last;           // pass 1 also runs the last chunk in scan order (the caller asked for h_last / decay)
     float *h0, *hl, *dc;     // workspace, each (ndir, batch, chunks, dim, 16) fp32
 };
+// the per-slot launch (cm_scan_cl_fwd_slots; single pass, one direction): sequence b runs its first lens[b] steps, clamped to
+// [0, seqlen], from h0 and leaves the state behind them in h_last
+struct rows_slot_plan : rows_plan {
+    const int32_t *lens;
+};
 
 // FULL: z gate and softplus present (the BiMamba layer's call), resolved at compile time
 // SUM: summary pass of a chunked launch -- no output contraction, gate, z or stores
@@ -392,6 +397,35 @@ __global__ __launch_bounds__(256, sizeof(IO) == 2 ? 4 : 3) void scan_rows_fwd_ke
     }
 }
 
+// The per-slot form of the single-pass launch (one direction, forward time): sequence b runs steps [0, T), T = lens[b] clamped to
+// [0, seqlen].  scan_rows bounds its buffer descriptors by T, so inputs at and past step T are never loaded and no output row there is
+// written: the steps it runs see what a launch with seqlen = T sees.
+template <typename IO, int DTR>
+__global__ __launch_bounds__(256, sizeof(IO) == 2 ? 4 : 3) void scan_rows_slots_kernel(const cm_scan_cl_args p, const rows_slot_plan pl) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[rows_lds<IO>::kBytes];
+    const int total = gridDim.x, nx = pl.nx;
+    int id = blockIdx.x;
+    if ((total & 7) == 0) id = (id & 7) * (total >> 3) + (id >> 3);
+    const int cx = id % nx, b = id / nx;
+    const cm_scan_cl_dir &d = p.dir[0];
+    const int T = min(max(pl.lens[b], 0), p.seqlen);
+    const int64_t slab = (int64_t)b * p.dim * 16;
+    const float *h0 = d.h0 ? d.h0 + slab : nullptr;
+    float *h_last = d.h_last ? d.h_last + slab : nullptr, *decay = d.decay ? d.decay + slab : nullptr;
+    if (T == 0) {                                                 // an idle slot: the state passes through, the decay factor is 1
+        const int lane = threadIdx.x & 63, c = cx * 64 + 16 * (int)(threadIdx.x >> 6) + (lane & 15);
+        const int64_t at = (int64_t)c * 16 + 4 * (lane >> 4);
+        if (c < p.dim) {
+            const float4 h = h0 ? *reinterpret_cast<const float4 *>(h0 + at) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (h_last) *reinterpret_cast<float4 *>(h_last + at) = h;
+            if (decay) *reinterpret_cast<float4 *>(decay + at) = make_float4(1.f, 1.f, 1.f, 1.f);
+        }
+        return;
+    }
+    if (p.z != nullptr && p.delta_softplus != 0) scan_rows<IO, false, true, 0, DTR, false>(p, d, lds, cx, b, 0, T, h0, h_last, decay);
+    else scan_rows<IO, false, false, 0, DTR, false>(p, d, lds, cx, b, 0, T, h0, h_last, decay);
+}
+
 // Entry state of every chunk from the chunk summaries, in scan order; the caller's h0 enters the first chunk, the caller's
 // h_last / decay (whole-sequence values) leave the last.  One thread per (direction, sequence, channel, 4 states).
 __global__ __launch_bounds__(256) void rows_carry_kernel(const cm_scan_cl_args p, const rows_plan pl) {
@@ -440,7 +474,7 @@ int cm_scan_rows_fwd2(const cm_scan_cl_args &a);        // scan_rows_fwd2.hip: 2
 namespace {
 
 template <typename IO>
-int launch_rows(const cm_scan_cl_args &a) {
+int launch_rows(const cm_scan_cl_args &a, const int32_t *lens) {
     rows_plan pl{};
     pl.nx = (a.dim + 63) / 64;
     pl.chunks = 1;
@@ -461,6 +495,21 @@ int launch_rows(const cm_scan_cl_args &a) {
         return launch_rows_chunked<IO, 16>(a, pl);
     }
     const long total = (long)pl.nx * a.batch * a.ndir;
+    if (lens) {                                             // per-slot lengths: the 4-states-per-lane kernel, unchunked (checked at entry)
+        rows_slot_plan sp{};
+        static_cast<rows_plan &>(sp) = pl;
+        sp.lens = lens;
+        const dim3 sgrid((unsigned)total), sblock(256);
+        hipStream_t sst = reinterpret_cast<hipStream_t>(a.stream);
+        if constexpr (sizeof(IO) == 2) {
+            if (a.dir[0].dt_rank > 16) {
+                hipLaunchKernelGGL((scan_rows_slots_kernel<IO, 32>), sgrid, sblock, 0, sst, a, sp);
+                return cm_launch_status("cm_scan_cl_fwd_slots(rows, dt_rank 32)");
+            }
+        }
+        hipLaunchKernelGGL((scan_rows_slots_kernel<IO, 16>), sgrid, sblock, 0, sst, a, sp);
+        return cm_launch_status("cm_scan_cl_fwd_slots(rows)");
+    }
     // lanes_per_channel == 8: the 2-states-per-lane kernel (scan_rows_fwd2.hip: twice the waves for the same launch).  Measured
     // (tools/bench_scan_small.py, profiles/r03/scan_small_batches.log) it is SLOWER at every size -- 16 x 1000 x 512: 133.7 vs
     // 110.6 us, 32 x: 191.6 vs 145.4 -- because what a SIMD with one 4-state wave lacks is independent recurrence chains, and
@@ -511,14 +560,21 @@ extern "C" int32_t cm_scan_cl_fwd_auto_chunks(int32_t batch, int32_t seqlen, int
     return c < 2 ? 1 : (int32_t)c;
 }
 
-// called by cm_scan_cl_fwd (scan_cl_fwd.hip) when every direction carries xdbl
-int cm_scan_rows_fwd(const cm_scan_cl_args &a) {
+// called by cm_scan_cl_fwd (scan_cl_fwd.hip) when every direction carries xdbl, and by cm_scan_cl_fwd_slots with lens
+int cm_scan_rows_fwd(const cm_scan_cl_args &a, const int32_t *lens) {
     const int vec = a.io_dtype == CM_BF16 ? 8 : 4;
     CM_REQUIRE(a.io_dtype == CM_BF16 || a.io_dtype == CM_F32, CM_EUNSUPPORTED, "scan_cl_fwd(xdbl): io dtype %d unsupported", a.io_dtype);
     CM_REQUIRE(a.dim % vec == 0, CM_EUNSUPPORTED, "scan_cl_fwd(xdbl): dim %d must be a multiple of %d", a.dim, vec);
     CM_REQUIRE(!a.z || (cm_aligned(a.z, 16) && a.z_bs % vec == 0 && a.z_ts % vec == 0), CM_EALIGN,
                "scan_cl_fwd(xdbl): z must be 16-byte aligned with strides that are multiples of %d", vec);
     CM_REQUIRE(a.time_chunks >= 0 && a.time_chunks <= 4096, CM_EINVAL, "scan_cl_fwd(xdbl): time_chunks %d out of range", a.time_chunks);
+    if (lens) {
+        CM_REQUIRE(a.time_chunks <= 1, CM_EUNSUPPORTED, "scan_cl_fwd_slots: per-slot lengths with time_chunks %d: the unchunked launch only", a.time_chunks);
+        CM_REQUIRE(a.ndir == 1, CM_EUNSUPPORTED, "scan_cl_fwd_slots: per-slot lengths with two directions are not built");
+        CM_REQUIRE(a.lanes_per_channel == 0 || a.lanes_per_channel == 4, CM_EUNSUPPORTED, "scan_cl_fwd_slots: lanes_per_channel %d (0 or 4)", a.lanes_per_channel);
+        CM_REQUIRE(!a.dir[0].reverse_time && !a.dir[0].ckpt, CM_EUNSUPPORTED, "scan_cl_fwd_slots: forward time, no training checkpoints");
+        CM_REQUIRE(cm_aligned(lens, 4), CM_EALIGN, "scan_cl_fwd_slots: lens must be 4-byte aligned");
+    }
     const int chunks = a.time_chunks > 1 ? (a.seqlen + rows_chunk_len(a.seqlen, a.time_chunks) - 1) / rows_chunk_len(a.seqlen, a.time_chunks) : 1;
     CM_REQUIRE((long)((a.dim + 63) / 64) * a.batch * a.ndir * chunks < (1L << 31), CM_EINVAL, "scan_cl_fwd(xdbl): grid too large");
     if (chunks > 1) {
@@ -538,5 +594,5 @@ int cm_scan_rows_fwd(const cm_scan_cl_args &a) {
                        d.xdbl_bs % vec == 0 && d.xdbl_ts % vec == 0 && cm_aligned(d.A, 16) && cm_aligned(d.dt_weight, 16),
                    CM_EALIGN, "scan_cl_fwd(xdbl): dir %d: u / xdbl / A / dt_weight must be 16-byte aligned, strides multiples of %d", i, vec);
     }
-    return a.io_dtype == CM_BF16 ? launch_rows<cm_bf16>(a) : launch_rows<float>(a);
+    return a.io_dtype == CM_BF16 ? launch_rows<cm_bf16>(a, lens) : launch_rows<float>(a, lens);
 }

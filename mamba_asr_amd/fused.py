@@ -259,18 +259,18 @@ def _conv_forms_xdbl(c: _LayerCache) -> bool:
     return USE_CONV_XPROJ and USE_SCAN_ROWS and c.rows_mode and c.wx_packed is not None and c.dtype == torch.bfloat16
 
 
-def _conv(c: _LayerCache, xz, ucat, xdbl=None, xproj=True, hist=None):
+def _conv(c: _LayerCache, xz, ucat, xdbl=None, xproj=True, hist=None, lens=None):
     """Both directions' causal conv + SiLU of xz's x half (batch, seqlen, 2E views) into ucat = [u_fwd | u_bwd].  With
     cm_conv_xproj the same kernel forms x_proj's rows (into ``xdbl`` when given) and they are returned, else None.
     The unidirectional mixer: one direction into ucat (E wide); ``hist`` = (x_hist, x_hist_out) of cm_conv_xproj_uni, the
-    native streaming route's carry."""
+    native streaming route's carry, ``lens`` its per-slot row counts (cm_conv_xproj_uni_slots)."""
     E = c.d_inner
     if c.uni:
         w0 = (c.dirs[0]["conv_w"], c.dirs[0]["conv_b"])
         if xproj and _conv_forms_xdbl(c):
             x_hist, x_hist_out = hist or (None, None)
-            return ops.conv_xproj_uni(xz[:, :, :E], *w0, c.wx_packed[0], out=ucat, xdbl=xdbl, x_hist=x_hist, x_hist_out=x_hist_out)
-        assert hist is None
+            return ops.conv_xproj_uni(xz[:, :, :E], *w0, c.wx_packed[0], out=ucat, xdbl=xdbl, x_hist=x_hist, x_hist_out=x_hist_out, lens=lens)
+        assert hist is None and lens is None
         ops.conv_cl_fwd(xz[:, :, :E], *w0, silu=True, out_f=ucat)
         return None
     w = (c.dirs[0]["conv_w"], c.dirs[0]["conv_b"], c.dirs[1]["conv_w"], c.dirs[1]["conv_b"])
@@ -280,18 +280,18 @@ def _conv(c: _LayerCache, xz, ucat, xdbl=None, xproj=True, hist=None):
     return None
 
 
-def _scan(c: _LayerCache, xz, ucat, ycat, xdbl, batch, seqlen, state=None):
+def _scan(c: _LayerCache, xz, ucat, ycat, xdbl, batch, seqlen, state=None, lens=None):
     """Both directions' selective scan of ucat, gated by xz's z half, into ycat (all (batch, seqlen, 2E)): one launch.
     ``state`` (batch, E, 16) fp32, streaming: the unidirectional scan starts from it and leaves its last state there (each workgroup
     reads its channels' entry state before it writes them), unchunked -- the recurrence then visits the same values in the same
-    order as over the whole sequence."""
+    order as over the whole sequence.  ``lens`` (with ``state``): per-slot step counts (cm_scan_cl_fwd_slots)."""
     dirs = _scan_dirs(c, ucat, ycat, batch, seqlen, xdbl)
     if state is None:
         ops.scan_cl_fwd(dirs, z=xz[:, :, c.d_inner:], delta_softplus=True)
         return
     if len(dirs) != 1 or "xdbl" not in dirs[0]:
         raise NotImplementedError("streaming needs the row-group scan (dt_rank <= 16, or <= 32 in bf16) of a unidirectional mixer")
-    ops.scan_cl_fwd([dict(dirs[0], h0=state, h_last=state)], z=xz[:, :, c.d_inner:], delta_softplus=True, time_chunks=1)
+    ops.scan_cl_fwd([dict(dirs[0], h0=state, h_last=state)], z=xz[:, :, c.d_inner:], delta_softplus=True, time_chunks=1, lens=lens)
 
 
 def bimamba_fused(c: _LayerCache, h, batch, seqlen):
@@ -327,7 +327,7 @@ def _ffn_images(c: _LayerCache, small: bool):
             getattr(c, "in_packed_s", None))
 
 
-def _head(c: _LayerCache, x, xz, ucat, xdbl=None, small=False, hist=None):
+def _head(c: _LayerCache, x, xz, ucat, xdbl=None, small=False, hist=None, lens=None):
     """A layer in front of the scan, on the rows of whole utterances: x (rows, D) fp32 += 0.5 ffn1(x); norm1; in_proj -> xz;
     both causal convs -> ucat; x_proj -> xdbl.  xz / ucat (batch, seqlen, 2E) and xdbl (batch, seqlen, 2 RW) or None are
     these rows' slices of the forward's buffers.  Returns x_proj's rows when cm_conv_xproj formed them, else None."""
@@ -336,7 +336,7 @@ def _head(c: _LayerCache, x, xz, ucat, xdbl=None, small=False, hist=None):
         _ffn_call(x, f1, norm2=c.norm1, proj_w=inp, proj_out=xz.view(x.shape[0], -1))
     else:
         _in_proj(c, _ffn_call(x, f1, norm2=c.norm1)[1], out=xz.view(x.shape[0], -1))
-    return _conv(c, xz, ucat, xdbl, hist=hist)
+    return _conv(c, xz, ucat, xdbl, hist=hist, lens=lens)
 
 
 def _ffn2(c: _LayerCache, x, addend, final_ln=None, f2=None):
@@ -346,19 +346,19 @@ def _ffn2(c: _LayerCache, x, addend, final_ln=None, f2=None):
                      h_dtype=torch.float32)[1]
 
 
-def _tail(c: _LayerCache, x, ycat, batch, seqlen, final_ln=None, small=False, hist=None):
+def _tail(c: _LayerCache, x, ycat, batch, seqlen, final_ln=None, small=False, hist=None, lens=None):
     """A layer behind the scan, on the rows of whole utterances: x (rows, D) fp32 += out_proj(ycat (rows, 2E)); the
     convolution module; FFN2 + norm2 (-> _ffn2).  ``hist`` = (hist, hist_out) of cm_glu_dwconv_ln_gelu_causal, the native
-    streaming route's carry."""
+    streaming route's carry, ``lens`` its per-slot row counts (cm_glu_dwconv_ln_gelu_causal_slots)."""
     D = x.shape[-1]
     dw = (c.dw_w, c.dw_b, c.cm_ln2[0], c.cm_ln2[1], c.cm_ln2[2])
-    kw = dict(causal=True, hist=hist[0], hist_out=hist[1]) if hist is not None else dict(causal=c.causal)
+    kw = dict(causal=True, hist=hist[0], hist_out=hist[1], lens=lens) if hist is not None else dict(causal=c.causal)
     if USE_LN_PW_GLU and c.pw_packed is not None:
         # x += mamba ; conv-module LN ; pointwise conv ; GLU -- one kernel, the 2D-wide tensor never exists
         gl = mixer_tail(c, x, ycat)
         g = ops.glu_dwconv_ln_gelu(gl.view(batch, seqlen, D), *dw, weight_t=c.dw_wt, glu_done=True, lin_w=c.lin_packed, lin_b=c.lin_bf, **kw)
     else:
-        assert hist is None                                      # the carried rows are the gated ones
+        assert hist is None and lens is None                     # the carried rows are the gated ones
         _, h = ops.add_layernorm(x, _out_proj(c, ycat), 1.0, x_out=x, norm2=c.cm_ln, out_dtype=c.dtype)   # x += mamba ; conv-module LN
         pw = torch.addmm(c.pw_b, h, c.pw_w.t()).view(batch, seqlen, 2 * D)
         g = ops.glu_dwconv_ln_gelu(pw, *dw, weight_t=c.dw_wt, lin_w=c.lin_packed, lin_b=c.lin_bf, **kw)
@@ -593,24 +593,33 @@ def encoder_forward(encoder, src, dtype: Optional[torch.dtype] = None, streams: 
 USE_STREAM_NATIVE = os.environ.get("CM_STREAM_NATIVE", "1") == "1"
 
 
-def _stream_layer_generic(c: _LayerCache, st, x, batch, t, dtype, final_ln=None):
-    """layer_forward for one chunk: the convs run on [history | chunk] rows, the scan from the carried state."""
+def _rows_behind(rows, first, n):
+    """rows (B, R, W), first (B,) int64 -> (B, n, W): rows [first[b], first[b] + n) of slot b, gathered on the device."""
+    idx = first[:, None] + torch.arange(n, device=rows.device)
+    return torch.gather(rows, 1, idx[:, :, None].expand(-1, -1, rows.shape[2]))
+
+
+def _stream_layer_generic(c: _LayerCache, st, x, batch, t, dtype, final_ln=None, lens=None):
+    """layer_forward for one chunk: the convs run on [history | chunk] rows, the scan from the carried state.  ``lens`` (B,) int32,
+    already clamped to [0, t]: slot b's new histories are the rows behind its row lens[b] - 1 and its scan stops there; both convs
+    are causal and everything else is row-local, so rows at and past lens[b] reach no valid row."""
     D, E = x.shape[-1], c.d_inner
+    first = None if lens is None else lens.long()
     _, h = ops.add_layernorm(x, None, norm2=c.ffn1["ln"], out_dtype=dtype)
     y = _ffn(x, h, c.ffn1, dtype)
     _, h = ops.add_layernorm(x, y, 0.5, x_out=x, norm2=c.norm1, out_dtype=dtype)
     xz = _in_proj(c, h).view(batch, t, 2 * E)
     xe = torch.cat([st.conv_state, xz[:, :, :E]], dim=1)                                    # (batch, 3 + t, E)
-    st.conv_state.copy_(xe[:, t:])
+    st.conv_state.copy_(xe[:, t:] if first is None else _rows_behind(xe, first, 3))
     ue = torch.empty_like(xe)
     ops.conv_cl_fwd(xe, c.dirs[0]["conv_w"], c.dirs[0]["conv_b"], silu=True, out_f=ue)
     u = ue[:, 3:].contiguous()
     ycat = torch.empty_like(u)
-    _scan(c, xz, u, ycat, None, batch, t, state=st.ssm_state)
+    _scan(c, xz, u, ycat, None, batch, t, state=st.ssm_state, lens=lens)
     _, h = ops.add_layernorm(x, _out_proj(c, ycat.view(batch * t, E)), 1.0, x_out=x, norm2=c.cm_ln, out_dtype=dtype)
     gl = F.glu(torch.addmm(c.pw_b, h, c.pw_w.t()), dim=-1).view(batch, t, D)
     ge = torch.cat([st.dw_state, gl], dim=1)                                                # (batch, 30 + t, D)
-    st.dw_state.copy_(ge[:, t:])
+    st.dw_state.copy_(ge[:, t:] if first is None else _rows_behind(ge, first, c.kernel_size - 1))
     g = ops.glu_dwconv_ln_gelu(ge, c.dw_w, c.dw_b, c.cm_ln2[0], c.cm_ln2[1], c.cm_ln2[2], weight_t=c.dw_wt, glu_done=True,
                                causal=True)[:, c.kernel_size - 1:]
     y = torch.addmm(c.lin_b, g.reshape(-1, D), c.lin_w.t())
@@ -623,12 +632,18 @@ def _stream_layer_generic(c: _LayerCache, st, x, batch, t, dtype, final_ln=None)
 
 
 @torch.no_grad()
-def forward_streaming(encoder, src, context):
+def forward_streaming(encoder, src, context, lens=None):
     """ConmambaEncoder.forward_streaming: src (B, t, D), any t >= 1, continues the B streams whose state ``context`` holds ->
     (B, t, D) fp32; the context is updated in place.  The outputs over the chunks of an utterance, concatenated, are the causal
     whole-utterance forward.  The compute dtype is the context's.  No host synchronisation and no data-dependent allocation: a
-    fixed (B, t) step can be captured in a hipGraph."""
+    fixed (B, t) step can be captured in a hipGraph.
+
+    ``lens``: a device int32 (B,) tensor, 0 <= lens[b] <= t (larger values are clamped on the device; it is never
+    read on the host).  Slot b consumes rows [0, lens[b]) of src[b]: its output rows there and its state after the call are, bit for
+    bit, those of a lock-step call on that slot alone with t = lens[b]; lens[b] == 0 leaves its state as it was.  Output rows at
+    and past lens[b] are unspecified, and what src holds there (NaN included) reaches no valid row and no state of any slot."""
     batch, t, D = src.shape
+    sl = None if lens is None else ops.slot_lens(lens, batch, src.device, "forward_streaming")    # the one check of lens, for every launch of the call
     dtype = context.layers[0].conv_state.dtype
     caches = [_cache(layer, dtype) for layer in encoder.layers]
     if not all(c.uni and c.causal and c.rows_mode and c.kernel_size == 31 for c in caches):
@@ -640,8 +655,9 @@ def forward_streaming(encoder, src, context):
     with torch.autocast("cuda", enabled=False):
         out = x = _residual_rows(src)
         if not native:
+            clamped = None if lens is None else lens.clamp(0, t)
             for i, (c, st) in enumerate(zip(caches, context.layers)):
-                out = _stream_layer_generic(c, st, x, batch, t, dtype, fin if i == n - 1 else None)
+                out = _stream_layer_generic(c, st, x, batch, t, dtype, fin if i == n - 1 else None, clamped)
             return out.view(batch, t, D)
         E, dev = caches[0].d_inner, src.device
         xz = torch.empty((batch, t, 2 * E), dtype=dtype, device=dev)
@@ -650,9 +666,9 @@ def forward_streaming(encoder, src, context):
         xdbl = torch.empty((batch, t, caches[0].row_width), dtype=dtype, device=dev)
         small = 0 < batch * t <= ops.SMALL_FFN_ROWS
         for i, (c, st) in enumerate(zip(caches, context.layers)):
-            _head(c, x, xz, ucat, xdbl, small, hist=(st.conv_state, st.conv_spare))
-            _scan(c, xz, ucat, ycat, xdbl, batch, t, state=st.ssm_state)
-            out = _tail(c, x, ycat.view(batch * t, E), batch, t, fin if i == n - 1 else None, small, hist=(st.dw_state, st.dw_spare))
+            _head(c, x, xz, ucat, xdbl, small, hist=(st.conv_state, st.conv_spare), lens=sl)
+            _scan(c, xz, ucat, ycat, xdbl, batch, t, state=st.ssm_state, lens=sl)
+            out = _tail(c, x, ycat.view(batch * t, E), batch, t, fin if i == n - 1 else None, small, hist=(st.dw_state, st.dw_spare), lens=sl)
             st.swap()
         return out.view(batch, t, D)
 
@@ -912,6 +928,163 @@ def frontend_streaming(model, wav_chunk, ctx: FrontEndStreamingContext, last: bo
     ctx.rows += plan[5]
     ctx.finished = bool(last)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# the front end with every slot at its own pace: per-slot sample counts, ends and resets
+# ------------------------------------------------------------------------------------------------
+class RowLens(list):
+    """The rows every slot got from one frontend_streaming_slots call: a host list of ints (what StreamingCTCBeamSearcher.step takes
+    as ``lengths``) whose ``dev`` is the same as a device int32 (B,) tensor (what encode_streaming takes as ``lens``)."""
+
+    def __init__(self, values, dev):
+        super().__init__(values)
+        self.dev = dev
+
+
+class SlotFrontEndStreamingContext:
+    """FrontEndStreamingContext for ``batch_size`` slots that advance independently: the same device state (sample history, feature
+    history, each with its spare, and umax), and the host counters samples / frames / rows / finished as lists, one entry per slot.
+    ``reset(rows)`` starts a new utterance in the listed slots (default all) with device index_fill_, no synchronisation."""
+
+    def __init__(self, batch_size, device, dtype):
+        self.batch_size, self.device, self.dtype = int(batch_size), torch.device(device), dtype
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)
+        self.samp_hist, self.samp_spare = z(batch_size, ops.FRONT_HIST_SAMPLES), z(batch_size, ops.FRONT_HIST_SAMPLES)
+        self.feat_hist, self.feat_spare = z(batch_size, ops.FRONT_HIST_FRAMES, 80), z(batch_size, ops.FRONT_HIST_FRAMES, 80)
+        self.umax = torch.full((batch_size,), float("-inf"), dtype=torch.float32, device=self.device)
+        self.samples, self.frames, self.rows, self.finished = ([0] * self.batch_size for _ in range(4))
+        self.subs = None                  # generic route: one lock-step context of one stream per slot
+        self.reset()
+
+    def reset(self, rows=None):
+        rows = list(range(self.batch_size)) if rows is None else [int(r) for r in rows]
+        if any(not 0 <= r < self.batch_size for r in rows):
+            raise ValueError(f"SlotFrontEndStreamingContext.reset: rows {rows} outside a context of {self.batch_size} slots")
+        if rows:
+            idx = torch.as_tensor(rows, dtype=torch.long).to(self.device, non_blocking=True)
+            self.samp_hist.index_fill_(0, idx, 0.0)
+            self.feat_hist.index_fill_(0, idx, 0.0)
+            self.umax.index_fill_(0, idx, float("-inf"))
+        for r in rows:
+            self.samples[r] = self.frames[r] = self.rows[r] = 0
+            self.finished[r] = False
+            if self.subs is not None:
+                self.subs[r].reset()
+
+
+class SlotASRStreamingContext:
+    """ConMambaASR.make_streaming_context(per_slot=True): ``frontend`` (SlotFrontEndStreamingContext) and ``encoder``; ``reset(rows)``
+    starts a new utterance in the listed slots (default all) of both."""
+
+    def __init__(self, frontend, encoder):
+        self.frontend, self.encoder = frontend, encoder
+
+    def reset(self, rows=None):
+        self.frontend.reset(rows)
+        self.encoder.encoder_context.reset(rows)
+
+
+def _slot_plan(model, ctx, wav_chunk, n_valid, last):
+    """Host arithmetic of one per-slot call, nothing changed: -> (rows of the plan table {n, consumed, total, f0, nf, r0, nr, T}, ends).
+    Every refusal is raised here, before anything is launched or any counter moves."""
+    fb, B = model.compute_features, ctx.batch_size
+    if wav_chunk.dim() != 2 or wav_chunk.shape[0] != B:
+        raise ValueError(f"frontend_streaming_slots: wav_chunk must be (batch, n_max) with batch = {B}, the context's; got {tuple(wav_chunk.shape)}")
+    n_max = wav_chunk.shape[1]
+    n_valid = [int(n) for n in n_valid]
+    ends = [bool(last)] * B if isinstance(last, (bool, int)) else [bool(x) for x in last]
+    if len(n_valid) != B or len(ends) != B:
+        raise ValueError(f"frontend_streaming_slots: n_valid and last must have {B} entries (got {len(n_valid)} and {len(ends)})")
+    plan = []
+    for b, n in enumerate(n_valid):
+        if not 0 <= n <= n_max:
+            raise ValueError(f"frontend_streaming_slots: n_valid[{b}] = {n} outside [0, {n_max}]")
+        if ctx.finished[b]:
+            if n != 0:
+                raise ValueError(f"frontend_streaming_slots: slot {b} has finished its utterance and takes no samples until it is reset (got {n})")
+            ends[b] = False
+            plan.append([0, ctx.samples[b], -1, ctx.frames[b], 0, ctx.rows[b], 0, -1])
+            continue
+        total = ctx.samples[b] + n
+        if ends[b]:
+            T = 1 + total // fb.hop
+            if T < 5:
+                raise RuntimeError(f"frontend_streaming_slots: slot {b} ends its utterance with {T} feature frames; the CNN front end needs at least 5 frames")
+            f1, r1 = T, frontend_rows_total(total, fb.hop)
+        else:
+            T, f1, r1 = -1, frontend_frames_ready(total, fb.n_fft, fb.hop), frontend_rows_ready(total, fb.n_fft, fb.hop)
+        plan.append([n, ctx.samples[b], total if ends[b] else -1, ctx.frames[b], f1 - ctx.frames[b], ctx.rows[b], r1 - ctx.rows[b], T])
+    return plan, ends
+
+
+def _front_native_slots(model, wav_chunk, ctx, plan):
+    fb, B, dev = model.compute_features, ctx.batch_size, wav_chunk.device
+    n_max, nf_max, nr_max = max(p[0] for p in plan), max(p[4] for p in plan), max(p[6] for p in plan)
+    host = torch.tensor(plan, dtype=torch.int32).pin_memory()
+    table = (host, host.to(dev, non_blocking=True))
+    lens_dev = table[1][:, 6].contiguous()
+    if n_max == 0 and nf_max == 0:                         # nothing arrived and no slot ends: no launch
+        return torch.zeros((B, 0, 640), dtype=torch.bfloat16, device=dev), lens_dev
+    if wav_chunk.dtype != torch.float32 or (wav_chunk.shape[1] and wav_chunk.stride(1) != 1):
+        wav_chunk = wav_chunk.float().contiguous()
+    db, fmax = ops.fbank_wav_stream(wav_chunk, ctx.samp_hist, ctx.samp_spare, 0, 0, nf_max, fb.window, fb.n_fft, fb.hop, fb.fbank, fb.amin, plan=table)
+    ctx.samp_hist, ctx.samp_spare = ctx.samp_spare, ctx.samp_hist
+    out = torch.zeros((B, nr_max, 640), dtype=torch.bfloat16, device=dev)          # rows past a slot's own count stay zero
+    if nf_max == 0:
+        return out, lens_dev
+    mean, std = _front_norm(model, fb.n_mels, dev)
+    ops.fbank_finish_stream(db, fmax, ctx.umax, 0, fb.top_db, mean, std, ctx.feat_hist, ctx.feat_spare, n_fft=fb.n_fft, plan=table)
+    if nr_max > 0:
+        c = _frontend_cache(model, torch.bfloat16)
+        b0 = model.CNN.blocks[0]
+        n0 = b0.norm.norm
+        ops.cnn_front_stream(db, ctx.feat_hist, 0, 0, nr_max, b0.conv.weight, b0.conv.bias, n0.weight, n0.bias, n0.eps, c["w2_ohwi"], c["b2f"],
+                             c["ln2"][0], c["ln2"][1], c["ln2"][2], 0.01, out=out, plan=table)
+    ctx.feat_hist, ctx.feat_spare = ctx.feat_spare, ctx.feat_hist
+    return out, lens_dev
+
+
+def _front_generic_slots(model, wav_chunk, ctx, plan, ends):
+    """The lock-step generic route per slot, on one single-stream context each; the rows padded with zeros to the widest slot."""
+    B, dev = ctx.batch_size, wav_chunk.device
+    if ctx.subs is None:
+        ctx.subs = [FrontEndStreamingContext(1, ctx.device, ctx.dtype) for _ in range(B)]
+    nr_max = max(p[6] for p in plan)
+    out = torch.zeros((B, nr_max, 640), dtype=ctx.dtype, device=dev)
+    for b, p in enumerate(plan):
+        if p[0] == 0 and not ends[b]:
+            continue
+        sub = ctx.subs[b]
+        lock = _front_plan(model, sub, wav_chunk[b:b + 1, :p[0]], ends[b])
+        rows = _front_generic(model, wav_chunk[b:b + 1, :p[0]], sub, ends[b], lock)
+        sub.samples, sub.frames, sub.rows, sub.finished = sub.samples + p[0], sub.frames + lock[3], sub.rows + lock[5], ends[b]
+        assert rows.shape[1] == p[6], (b, rows.shape, p)
+        out[b, :p[6]] = rows[0]
+    return out, torch.tensor([p[6] for p in plan], dtype=torch.int32).to(dev, non_blocking=True)
+
+
+@torch.no_grad()
+def frontend_streaming_slots(model, wav_chunk, n_valid, ctx: SlotFrontEndStreamingContext, last=False):
+    """The next samples of B slots that advance independently: wav_chunk (B, n_max), of which slot b hands over its first n_valid[b]
+    (a host sequence of ints, 0 allowed; samples at and past it are never read by the native route); ``last`` a bool or a sequence of
+    B bools, last[b] ending slot b's utterance at samples[b] + n_valid[b] with the whole-utterance treatment of the end.  ->
+    (rows (B, t_max, 640), row_lens): row_lens[b] is what frontend_streaming gives that slot alone (a RowLens: host list, ``.dev`` the
+    device int32 tensor), t_max its maximum, rows at and past row_lens[b] zeros.  A finished slot takes only n_valid[b] = 0 until it
+    is reset (ValueError names it); a slot that ends under 5 frames raises; both before anything is launched or any counter moves.
+    Native route: three launches, two when no slot has a row, one when none has a frame, none when nothing arrived and no slot ends."""
+    plan, ends = _slot_plan(model, ctx, wav_chunk, n_valid, last)
+    with torch.autocast("cuda", enabled=False):
+        if frontend_streaming_native(model, ctx) and wav_chunk.is_cuda:
+            out, lens_dev = _front_native_slots(model, wav_chunk, ctx, plan)
+        else:
+            out, lens_dev = _front_generic_slots(model, wav_chunk, ctx, plan, ends)
+    for b, p in enumerate(plan):
+        ctx.samples[b] += p[0]
+        ctx.frames[b] += p[4]
+        ctx.rows[b] += p[6]
+        ctx.finished[b] = ctx.finished[b] or ends[b]
+    return out, RowLens([p[6] for p in plan], lens_dev)
 
 
 class GraphedEncode:

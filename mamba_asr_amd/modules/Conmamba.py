@@ -215,10 +215,12 @@ class ConmambaEncoder(nn.Module):
                                                   z(batch_size, l.convolution_module.kernel_size - 1, l.mamba.d_model, dt=dtype))
              for l in self.layers])
 
-    def forward_streaming(self, src, context, pos_embs=None):
+    def forward_streaming(self, src, context, pos_embs=None, lens=None):
         """src (B, t, D), the next t >= 1 frames of B streams -> (out (B, t, D) fp32, None); ``context`` (make_streaming_context)
         is updated in place.  Concatenating the outputs over an utterance's chunks gives ``forward`` on the whole utterance.
-        Eval mode, no grad, GPU (fused.forward_streaming).  ``pos_embs`` is ignored, as in ``forward``."""
+        Eval mode, no grad, GPU (fused.forward_streaming).  ``pos_embs`` is ignored, as in ``forward``.  ``lens``: a device int32
+        (B,) tensor, slot b advances by its first lens[b] <= t rows only (0: the slot idles and keeps its state); output rows at
+        and past lens[b] are unspecified.  None: every slot advances by t rows."""
         self._require_causal("forward_streaming")
         if len(context.layers) != len(self.layers) or context.batch_size != src.shape[0]:
             raise ValueError(f"forward_streaming: the context holds {context.batch_size} streams of {len(context.layers)} layers, "
@@ -228,7 +230,7 @@ class ConmambaEncoder(nn.Module):
         from .. import fused
         if not all(fused.supports(layer) for layer in self.layers):
             raise NotImplementedError("forward_streaming: a layer is outside the fused path (fused.supports)")
-        return fused.forward_streaming(self, src, context), None
+        return fused.forward_streaming(self, src, context, lens), None
 
 
 class MambaDecoderLayer(nn.Module):

@@ -139,10 +139,11 @@ class TransformerASR(nn.Module):
                               dynchunktrain_config=dynchunktrain_config)
         return out
 
-    def encode_streaming(self, src, context: TransformerASRStreamingContext):
+    def encode_streaming(self, src, context: TransformerASRStreamingContext, lens=None):
         """The next chunk of frames (B, t, F[, C]) of the streams in ``context`` -> encoder_out (B, t, D) (reference :931-1022);
-        ``context`` is updated in place.  Causal ConMamba encoders only (ConmambaEncoder.forward_streaming)."""
-        out, _ = self.encoder.forward_streaming(src=self._prep_src(src), pos_embs=None, context=context.encoder_context)
+        ``context`` is updated in place.  Causal ConMamba encoders only (ConmambaEncoder.forward_streaming).  ``lens``: per-slot
+        row counts, a device int32 (B,) tensor (ConmambaEncoder.forward_streaming)."""
+        out, _ = self.encoder.forward_streaming(src=self._prep_src(src), pos_embs=None, context=context.encoder_context, lens=lens)
         return out
 
     def make_streaming_context(self, dynchunktrain_config=None, encoder_kwargs={}):
@@ -215,8 +216,8 @@ class EncoderWrapper(nn.Module):
     def forward(self, x, wav_lens=None, pad_idx=0, **kwargs):
         return self.transformer.encode(x, wav_lens, pad_idx, **kwargs)
 
-    def forward_streaming(self, x, context):
-        return self.transformer.encode_streaming(x, context)
+    def forward_streaming(self, x, context, lens=None):
+        return self.transformer.encode_streaming(x, context, lens)
 
     def make_streaming_context(self, *args, **kwargs):
         return self.transformer.make_streaming_context(*args, **kwargs)

@@ -509,9 +509,11 @@ def _scan_cl_dir_rows(x, dd, u0, z, keep):
 SCAN_CHUNKS = os.environ.get("CM_SCAN_CHUNKS", "auto")
 
 
-def scan_cl_fwd(directions, z=None, delta_softplus=True, time_chunks=None, split: int = 0):
+def scan_cl_fwd(directions, z=None, delta_softplus=True, time_chunks=None, split: int = 0, lens=None):
     """Channels-last selective scan, 1 or 2 directions in one launch (cm_scan_cl_fwd).
     ``time_chunks`` (xdbl mode): None = the CM_SCAN_CHUNKS policy, else the chunk count.
+    ``lens`` (cm_scan_cl_fwd_slots; xdbl mode, one direction, unchunked): int32 (batch,) device tensor, sequence b runs its first
+    lens[b] steps only (h_last = h0 for 0); ``out`` rows at and past lens[b] are not written.
 
     ``directions``: list of dicts with u, delta (batch, seqlen, dim), A (dim, 16), B, C (16, batch, seqlen) fp32
     time-contiguous (see alloc_bc), D, delta_bias (dim) or None, out (batch, seqlen, dim) view or None, reverse.
@@ -572,8 +574,8 @@ def scan_cl_fwd(directions, z=None, delta_softplus=True, time_chunks=None, split
     a.lanes_per_channel = int(split)                     # tuning of the state-split kernel: 4, 8, 16 lanes per channel; 0 = automatic
     if "xdbl" in directions[0]:
         if time_chunks is None:
-            time_chunks = (N.lib().cm_scan_cl_fwd_auto_chunks(b, l, d, len(directions)) if SCAN_CHUNKS == "auto"
-                           else int(SCAN_CHUNKS))
+            time_chunks = 1 if lens is not None else (N.lib().cm_scan_cl_fwd_auto_chunks(b, l, d, len(directions)) if SCAN_CHUNKS == "auto"
+                                                      else int(SCAN_CHUNKS))
         a.time_chunks = int(time_chunks)
         nbytes = N.lib().cm_scan_cl_fwd_workspace_bytes(ct.byref(a))
         if nbytes:
@@ -582,6 +584,10 @@ def scan_cl_fwd(directions, z=None, delta_softplus=True, time_chunks=None, split
             a.workspace, a.workspace_bytes = _ptr(ws), nbytes
     elif time_chunks not in (None, 0, 1):
         raise RuntimeError("time_chunks needs the xdbl mode")
+    if lens is not None:
+        lp, fn = _slot_lens(lens, b, u0.device, "scan_cl_fwd"), N.lib().cm_scan_cl_fwd_slots
+        _launch("cm_scan_cl_fwd_slots", lambda ref: fn(ref, lp), a, units=b * l)
+        return outs
     _launch("cm_scan_cl_fwd", N.lib().cm_scan_cl_fwd, a, units=b * l * len(directions))
     return outs
 
@@ -1281,18 +1287,46 @@ def _out_rows(t, shape, dtype, device, what):
     return t
 
 
+class SlotLens:
+    """Per-slot lengths that were checked once (slot_lens) for the many launches of one streamed call: the tensor, kept alive, its
+    device address and what it was checked against."""
+    __slots__ = ("tensor", "ptr", "batch", "device")
+
+    def __init__(self, tensor, batch, device):
+        self.tensor, self.ptr, self.batch, self.device = tensor, tensor.data_ptr(), batch, device
+
+
+def slot_lens(lens, batch, device, what="lens"):
+    """Per-slot lengths of a streamed launch: a contiguous int32 (batch,) tensor on the launch's device.  The kernel reads it (and
+    clamps it to [0, seqlen]); nothing is read back on the host.  -> SlotLens, which the wrappers take in place of the tensor."""
+    if not isinstance(lens, torch.Tensor) or lens.dtype != torch.int32 or tuple(lens.shape) != (batch,) or not lens.is_contiguous() \
+            or lens.device != device:
+        raise RuntimeError(f"{what}: lens must be a contiguous int32 tensor of shape ({batch},) on {device}")
+    return SlotLens(lens, batch, device)
+
+
+def _slot_lens(lens, batch, device, what):
+    """-> the device address of the per-slot lengths: a SlotLens made for this batch and device, or a tensor checked here."""
+    if type(lens) is SlotLens:
+        if lens.batch != batch or lens.device != device:
+            raise RuntimeError(f"{what}: lens was checked for batch {lens.batch} on {lens.device}, the launch has batch {batch} on {device}")
+        return lens.ptr
+    return slot_lens(lens, batch, device, what).ptr
+
+
 def _hist_rows(t, shape, dtype, what):
     if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()):
         raise RuntimeError(f"{what} must be a contiguous {dtype} tensor of shape {shape}")
     return t
 
 
-def conv_xproj_uni(x, weight, bias, wx, out, xdbl=None, x_hist=None, x_hist_out=None, variant: int = 0):
+def conv_xproj_uni(x, weight, bias, wx, out, xdbl=None, x_hist=None, x_hist_out=None, variant: int = 0, lens=None):
     """One causal direction's depthwise conv + SiLU and x_proj GEMM in one kernel (cm_conv_xproj_uni, bf16), whole sequences
     or a stream of chunks.  x (batch, seqlen, dim) view; weight (dim, 4) fp32; wx PackedWeight of the (P + 32, dim) re-rowed
     x_proj weight; out (batch, seqlen, dim) view.  x_hist (batch, 3, dim) bf16: the rows in front of x, None = zeros;
     x_hist_out (batch, 3, dim): receives the last three rows of [x_hist | x], and must be another buffer than x_hist.
-    Returns xdbl (batch, seqlen, P + 32) bf16."""
+    ``lens`` (cm_conv_xproj_uni_slots): int32 (batch,) device tensor, slot b has lens[b] valid rows -- x_hist_out[b] is cut behind
+    row lens[b] - 1, rows at and past it are unspecified in both outputs.  Returns xdbl (batch, seqlen, P + 32) bf16."""
     _dev_check(x, weight, bias, out, x_hist, x_hist_out)
     _rows_ok(x, "x"), _rows_ok(out, "out")
     b, l, d = x.shape
@@ -1315,6 +1349,10 @@ def conv_xproj_uni(x, weight, bias, wx, out, xdbl=None, x_hist=None, x_hist_out=
     a.x_bs, a.x_ts, a.y_bs, a.y_ts = x.stride(0), x.stride(1), out.stride(0), out.stride(1)
     a.xdbl_bs, a.xdbl_ts = xdbl.stride(0), xdbl.stride(1)
     a.stream, a.dt_pad, a.variant = _stream(), rw - 32, int(variant)     # variant 1: always the 16-step tiles
+    if lens is not None:
+        lp, fn = _slot_lens(lens, b, x.device, "conv_xproj_uni"), N.lib().cm_conv_xproj_uni_slots
+        _launch("cm_conv_xproj_uni_slots", lambda ref: fn(ref, lp), a, units=b * l)
+        return xdbl
     _launch("cm_conv_xproj_uni", N.lib().cm_conv_xproj_uni, a, units=b * l)
     return xdbl
 
@@ -1749,16 +1787,18 @@ def ln_pw_glu(x, y, alpha, norm, w, bias, x_out=None, ycat=None, out_w=None, out
 
 
 def glu_dwconv_ln_gelu(inp, weight, bias, ln_weight, ln_bias, eps=1e-5, weight_t=None, glu_done=False, lin_w=None, lin_b=None,
-                       variant: int = 0, causal: bool = False, hist=None, hist_out=None, out=None):
+                       variant: int = 0, causal: bool = False, hist=None, hist_out=None, out=None, lens=None):
     """(batch, seqlen, 2*dim) -> (batch, seqlen, dim): GLU, depthwise conv (k=31, same padding), LayerNorm, GELU
     (cm_glu_dwconv_ln_gelu).  weight (dim, 1, k) or (dim, k); weight_t: optional precomputed fp32 (k, dim) copy of the
     taps (made here per call otherwise) so that the kernel's per-channel tap reads are coalesced.
     ``causal`` (cm_glu_dwconv_ln_gelu_causal): all k - 1 padding rows in front; hist (batch, k - 1, dim) in inp's dtype are
     the gated rows in front of inp (None = zeros), hist_out (another buffer than hist) receives the last k - 1 gated rows of
-    [hist | inp].  ``out``: optional contiguous (batch, seqlen, dim) tensor in inp's dtype to receive the result."""
+    [hist | inp].  ``lens`` (cm_glu_dwconv_ln_gelu_causal_slots): int32 (batch,) device tensor, slot b has lens[b] valid rows --
+    hist_out[b] is cut behind gated row lens[b] - 1, output rows at and past it are unspecified.
+    ``out``: optional contiguous (batch, seqlen, dim) tensor in inp's dtype to receive the result."""
     _dev_check(inp, weight, bias, ln_weight, ln_bias, hist, hist_out)
-    if (hist is not None or hist_out is not None) and not causal:
-        raise RuntimeError("glu_dwconv_ln_gelu: hist / hist_out belong to the causal form")
+    if (hist is not None or hist_out is not None or lens is not None) and not causal:
+        raise RuntimeError("glu_dwconv_ln_gelu: hist / hist_out / lens belong to the causal form")
     if not inp.is_contiguous():
         inp = inp.contiguous()
     b, l, d2 = inp.shape
@@ -1782,7 +1822,10 @@ def glu_dwconv_ln_gelu(inp, weight, bias, ln_weight, ln_bias, eps=1e-5, weight_t
         lb = _f32c(lin_b)
         a.lin_w, a.lin_b = _ptr(lin_w.data), _ptr(lb)
     a.stream, a.variant = _stream(), int(variant)        # variant 1: always the generic 16-step kernel
-    if causal:
+    if lens is not None:
+        lp, fn = _slot_lens(lens, b, inp.device, "glu_dwconv_ln_gelu"), N.lib().cm_glu_dwconv_ln_gelu_causal_slots
+        _launch("cm_glu_dwconv_ln_gelu_causal_slots", lambda ref: fn(ref, lp), a, units=b * l)
+    elif causal:
         _launch("cm_glu_dwconv_ln_gelu_causal", N.lib().cm_glu_dwconv_ln_gelu_causal, a, units=b * l)
     else:
         _launch("cm_glu_dwconv_ln_gelu", N.lib().cm_glu_dwconv_ln_gelu, a, units=b * l)
@@ -2169,12 +2212,24 @@ def fbank_from_wav(wav, window, n_fft, hop, fbank, amin=1e-10, top_db=80.0, mean
 FRONT_HIST_SAMPLES, FRONT_HIST_FRAMES = 512, 8      # per-stream history of cm_fbank_wav_stream / cm_cnn_front_stream
 
 
-def fbank_wav_stream(chunk, hist, hist_out, consumed, f0, nf, window, n_fft, hop, fbank, amin=1e-10, total=-1, bufs=None):
+def _front_plan_ptrs(plan, batch, device, what):
+    """The per-slot plan of the streamed front end: (host, device), two contiguous int32 (batch, 8) tensors with the same content,
+    rows {n, consumed, total, f0, nf, r0, nr, T_total}.  The C entry point checks the host copy, the kernels read the device copy."""
+    host, devt = plan
+    for t, where in ((host, "cpu"), (devt, device.type)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (batch, 8) or not t.is_contiguous() or t.device.type != where:
+            raise RuntimeError(f"{what}: plan must be (host, device) contiguous int32 tensors of shape ({batch}, 8)")
+    return host.data_ptr(), devt.data_ptr()
+
+
+def fbank_wav_stream(chunk, hist, hist_out, consumed, f0, nf, window, n_fft, hop, fbank, amin=1e-10, total=-1, bufs=None, plan=None):
     """The frames [f0, f0 + nf) of every stream of an utterance that arrives in chunks (cm_fbank_wav_stream): chunk (batch, n) fp32,
     the samples ``consumed`` .. ``consumed + n`` of the utterance; hist / hist_out (batch, 512) fp32, the samples in front of the
     chunk and the buffer that receives the next call's (another one: the caller swaps); ``total``: the utterance's length when the
     chunk ends it (zero padding past it), else -1.  -> (db (batch, nf, n_mels) fp32 before the top_db clamp, fmax (batch, nf)
-    per-frame maxima), or (None, None) for nf = 0, which only rolls the history.  ``bufs``: caller-supplied ``db`` / ``fmax``."""
+    per-frame maxima), or (None, None) for nf = 0, which only rolls the history.  ``bufs``: caller-supplied ``db`` / ``fmax``.
+    ``plan`` (cm_fbank_wav_stream_slots): per-slot counts (_front_plan_ptrs); n and ``nf`` are then the maxima over the slots and
+    ``consumed`` / ``f0`` / ``total`` are ignored; rows of db / fmax past a slot's own nf are not written."""
     _dev_check(chunk, hist, hist_out, window, fbank)
     b, n = chunk.shape
     if chunk.dtype != torch.float32 or (n and chunk.stride(1) != 1):
@@ -2198,15 +2253,21 @@ def fbank_wav_stream(chunk, hist, hist_out, consumed, f0, nf, window, n_fft, hop
         a.window, a.twiddle, a.band_lo, a.band_hi, a.band_off, a.band_w = _ptr(win), _ptr(tw), _ptr(lo), _ptr(hi), _ptr(off), _ptr(packed)
         a.db, a.fmax = _ptr(db), _ptr(fmax)
     a.amin, a.stream = float(amin), _stream()
+    if plan is not None:
+        ph, pd = _front_plan_ptrs(plan, b, chunk.device, "fbank_wav_stream")
+        fn = N.lib().cm_fbank_wav_stream_slots
+        _launch("cm_fbank_wav_stream_slots", lambda ref: fn(ref, ph, pd), a, units=b * nf)
+        return db, fmax
     _launch("cm_fbank_wav_stream", N.lib().cm_fbank_wav_stream, a, units=b * nf)
     return db, fmax
 
 
-def fbank_finish_stream(db, fmax, umax, f0, top_db=80.0, mean=None, std=None, feat_hist=None, feat_hist_out=None, n_fft=512):
+def fbank_finish_stream(db, fmax, umax, f0, top_db=80.0, mean=None, std=None, feat_hist=None, feat_hist_out=None, n_fft=512, plan=None):
     """The causal top_db clamp and the global normalisation of fbank_wav_stream's frames, in place (cm_fbank_finish_stream): the
     floor of frame f is max(umax[b], fmax[b, :f + 1]) - top_db, and umax (batch) fp32 -- -inf at the start of an utterance --
     becomes the maximum over all frames so far.  feat_hist / feat_hist_out (batch, 8, n_mels) fp32: the feature rows in front of
-    ``db`` and the buffer that receives the last 8 rows of [feat_hist | db] (another one).  -> db."""
+    ``db`` and the buffer that receives the last 8 rows of [feat_hist | db] (another one).  ``plan``
+    (cm_fbank_finish_stream_slots): per-slot f0 / nf, db's frame axis being the widest slot's.  -> db."""
     _dev_check(db, fmax, umax, mean, std, feat_hist, feat_hist_out)
     b, nf, m = db.shape
     if db.dtype != torch.float32 or not db.is_contiguous():
@@ -2222,15 +2283,22 @@ def fbank_finish_stream(db, fmax, umax, f0, top_db=80.0, mean=None, std=None, fe
     a.batch, a.n_mels, a.n_fft, a.f0, a.nf, a.total = b, m, int(n_fft), int(f0), nf, -1
     a.db, a.fmax, a.umax, a.top_db, a.mean, a.std = _ptr(db), _ptr(fmax), _ptr(umax), float(top_db), _ptr(mean), _ptr(std)
     a.feat_hist, a.feat_hist_out, a.stream = _ptr(feat_hist), _ptr(feat_hist_out), _stream()
+    if plan is not None:
+        ph, pd = _front_plan_ptrs(plan, b, db.device, "fbank_finish_stream")
+        fn = N.lib().cm_fbank_finish_stream_slots
+        _launch("cm_fbank_finish_stream_slots", lambda ref: fn(ref, ph, pd), a, units=b * nf)
+        return db
     _launch("cm_fbank_finish_stream", N.lib().cm_fbank_finish_stream, a, units=b * nf)
     return db
 
 
 def cnn_front_stream(feats, feat_hist, f0, r0, nr, w1, b1, ln1_w, ln1_b, eps1, w2_ohwi, b2, ln2_w, ln2_b, eps2, slope=0.01, t_total=-1,
-                     out=None):
+                     out=None, plan=None):
     """The rows [r0, r0 + nr) of cnn_front for utterances whose features arrive in chunks (cm_cnn_front_stream): feats (batch, nf, 80)
     fp32 holds the frames from f0 on, feat_hist (batch, 8, 80) the 8 in front of them (None: there are none).  ``t_total``: the
-    utterance's number of frames when this call ends it (the reflection at the end is taken), else -1.  -> (batch, nr, 640) bf16."""
+    utterance's number of frames when this call ends it (the reflection at the end is taken), else -1.  -> (batch, nr, 640) bf16.
+    ``plan`` (cm_cnn_front_stream_slots): per-slot f0 / nf / r0 / nr / T_total; ``nr`` and feats' frame axis are then the widest
+    slot's, and rows of out past a slot's own nr are not written."""
     _dev_check(feats, feat_hist, w1, b1, ln1_w, ln1_b, w2_ohwi, b2, ln2_w, ln2_b, out)
     if feats.dtype != torch.float32 or not feats.is_contiguous() or feats.dim() != 3:
         raise RuntimeError("cnn_front_stream: feats must be contiguous fp32 (batch, frames, bins)")
@@ -2248,6 +2316,11 @@ def cnn_front_stream(feats, feat_hist, f0, r0, nr, w1, b1, ln1_w, ln1_b, eps1, w
     a.feats, a.feat_hist, a.w1, a.b1, a.ln1_g, a.ln1_b = _ptr(feats), _ptr(feat_hist), _ptr(w1f), _ptr(b1f), _ptr(g1), _ptr(bt1)
     a.w2, a.b2, a.ln2_g, a.ln2_b = _ptr(w2_ohwi), _ptr(b2f), _ptr(g2), _ptr(bt2)
     a.eps1, a.eps2, a.slope, a.out, a.stream = float(eps1), float(eps2), float(slope), _ptr(out), _stream()
+    if plan is not None:
+        ph, pd = _front_plan_ptrs(plan, b, feats.device, "cnn_front_stream")
+        fn = N.lib().cm_cnn_front_stream_slots
+        _launch("cm_cnn_front_stream_slots", lambda ref: fn(ref, ph, pd), a, units=b * nr)
+        return out
     _launch("cm_cnn_front_stream", N.lib().cm_cnn_front_stream, a, units=b * nr)
     return out
 
