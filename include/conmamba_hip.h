@@ -283,6 +283,14 @@ int cm_scan_cl_fwd(const cm_scan_cl_args *args);
  * direction in forward time, unchunked (time_chunks <= 1), lanes_per_channel 0 or 4, no ckpt; anything else, NULL lens
  * included, is refused before anything is launched. */
 int cm_scan_cl_fwd_slots(const cm_scan_cl_args *args, const int32_t *lens);
+/* Whole utterances of different lengths in one batch: sequence b has L = min(max(lens[b], 0), seqlen) steps, and
+ * every direction of the launch runs exactly the steps [0, L) -- forward time from step 0, reverse time from step L - 1, each from a
+ * zero state, over the 16-step blocks of a launch with seqlen = L.  The `out` rows [0, L) carry the bits of cm_scan_cl_fwd
+ * (time_chunks = 1) on that sequence alone with seqlen = L; inputs at and past step L are not loaded, `out` rows there are not
+ * written; L == 0 reads nothing and writes nothing.  lens: `batch` int32 in DEVICE memory, read by the kernel (no host read-back).
+ * xdbl mode, one or two directions, unchunked (time_chunks <= 1), lanes_per_channel 0 or 4, no ckpt / ypre / h0 / h_last / decay;
+ * anything else, NULL lens included, is refused before anything is launched (CM_EUNSUPPORTED / CM_EINVAL). */
+int cm_scan_cl_fwd_lens(const cm_scan_cl_args *args, const int32_t *lens);
 /* bytes of workspace the launch described by args needs (0 unless time_chunks > 1) */
 int64_t cm_scan_cl_fwd_workspace_bytes(const cm_scan_cl_args *args);
 /* the chunk count that fills 256 CUs for this problem size (1 = do not chunk); a pure function of the sizes */
@@ -714,6 +722,14 @@ typedef struct cm_conv_xproj_args {
 } cm_conv_xproj_args;
 
 int cm_conv_xproj(const cm_conv_xproj_args *args);
+/* Whole utterances of different lengths in one batch: utterance b has L = min(max(lens[b], 0), seqlen) rows.  The
+ * buffer descriptors of x, y_fwd and y_bwd of utterance b end behind row L - 1, so the backward direction's taps past the last row
+ * read the conv's zero padding and stores past it are dropped; xdbl rows at and past L are not written; tiles past row L - 1 exit.
+ * Rows [0, L) of y_fwd, y_bwd and xdbl carry the bits of cm_conv_xproj on that utterance alone with seqlen = L under the same tile
+ * shape; L == 0 reads nothing and writes nothing.  The tile shape follows cm_conv_xproj's rule on (batch, seqlen): at
+ * batch * ceil(seqlen / 32) >= 512 the 32-step tiles run, whose xdbl differs from a batch-1 call's (16-step tiles) within bf16
+ * rounding; y_fwd / y_bwd are the same bits under either shape.  lens: `batch` int32 in DEVICE memory; NULL is refused. */
+int cm_conv_xproj_lens(const cm_conv_xproj_args *args, const int32_t *lens);
 
 /* ---------------------------------------------------------------------------------------
  * ONE causal direction of cm_conv_xproj with a history input (bf16 only): the UniMamba mixer of the causal encoder
@@ -806,6 +822,12 @@ typedef struct cm_glu_dwconv_args {
 } cm_glu_dwconv_args;
 
 int cm_glu_dwconv_ln_gelu(const cm_glu_dwconv_args *args);
+/* Whole utterances of different lengths in one batch (the non-causal 'same'-padding form, every kernel of it, with
+ * and without the Linear epilogue): utterance b has L = min(max(lens[b], 0), seqlen) rows.  Staged rows t >= L are zero -- the
+ * 'same' padding starts behind the utterance's own last row -- rows of `out` at and past L are not written, tiles past row L - 1
+ * exit.  Rows [0, L) carry the bits of cm_glu_dwconv_ln_gelu on that utterance alone with seqlen = L; L == 0 reads nothing and
+ * writes nothing.  lens: `batch` int32 in DEVICE memory; NULL is refused (CM_EINVAL). */
+int cm_glu_dwconv_ln_gelu_lens(const cm_glu_dwconv_args *args, const int32_t *lens);
 
 /* ---------------------------------------------------------------------------------------
  * The same core for ConvolutionModule(causal=True) (reference modules/Conmamba.py:230-238, :445-446: pad both sides by
@@ -1129,6 +1151,13 @@ typedef struct cm_cnn_front_args {
 } cm_cnn_front_args;
 
 int cm_cnn_front(const cm_cnn_front_args *args);
+/* Whole utterances of different lengths in one batch: utterance b has T_b = min(max(frames[b], 0), T) feature
+ * frames, T1_b = ceil(T_b / 2) block-1 rows and T2_b = ceil(T1_b / 2) output rows.  Both reflections happen at the utterance's own
+ * ends (T_b and T1_b), rows at and past T2_b are not computed or written, feature frames at and past T_b are never read.  Rows
+ * [0, T2_b) carry the bits of cm_cnn_front on that utterance alone with T = T_b.  T_b < 5 (0 included) reads nothing and writes
+ * nothing.  feats (batch, T, 80) and out (batch, ceil(ceil(T / 2) / 2), 640) keep the strides of the struct's T.
+ * frames: `batch` int32 in DEVICE memory; NULL is refused (CM_EINVAL). */
+int cm_cnn_front_lens(const cm_cnn_front_args *args, const int32_t *frames);
 
 /* ---------------------------------------------------------------------------------------
  * bf16 MFMA GEMM with fused epilogues for the ConMamba layer's projections:
@@ -1303,6 +1332,16 @@ int cm_fbank_finish(const cm_fbank_args *args);
 /* waveform -> log-mel (before top_db / normalisation: follow with cm_fbank_finish on the same args).  Requires
  * umax_part and the packed band tables (band_lo, band_hi, band_off, band_w).  In-LDS radix-4 real FFT, n_fft = 512. */
 int cm_fbank_wav(const cm_fbank_args *args);
+/* Whole utterances of different lengths in one batch: utterance b has n_b = min(max(n_samples[b], 0), samples)
+ * samples and T_b = 1 + n_b / hop frames (0 frames for n_b == 0).  cm_fbank_wav_lens: samples at and past n_b read as zero (the
+ * waveform's buffer descriptor ends there), frames [0, T_b) are computed and the per-tile maxima in umax_part run over them only;
+ * tiles past T_b store -inf.  cm_fbank_finish_lens (same args, same n_samples): the top_db maximum of utterance b runs over the
+ * tiles of frames [0, T_b) only -- frames T_b and T_b + 1 of the padded batch still overlap real samples and can be the loudest --
+ * and frames [0, T_b) are clamped and normalised.  Those frames carry the bits of cm_fbank_wav + cm_fbank_finish on that utterance
+ * alone with samples = n_b; frames at and past T_b are unspecified (not written).  db (batch, frames, n_mels) and umax_part keep the
+ * strides of the struct's frames.  n_samples: `batch` int32 in DEVICE memory; NULL is refused (CM_EINVAL). */
+int cm_fbank_wav_lens(const cm_fbank_args *args, const int32_t *n_samples);
+int cm_fbank_finish_lens(const cm_fbank_args *args, const int32_t *n_samples);
 
 /* ---------------------------------------------------------------------------------------
  * The Fbank and the CNN front end as a stream: waveform chunks in, encoder rows out.  All `batch` streams

@@ -103,10 +103,17 @@ class ConMambaASR(nn.Module):
         first training batches, train_CTC.py:287; benchmarks / parity runs on random-init models call this once)."""
         self.normalize.update_statistics(self.compute_features(wavs), wav_lens)
 
-    def encode(self, wavs, wav_lens, epoch=0, augment=None, feats=None):
+    def encode(self, wavs, wav_lens, epoch=0, augment=None, feats=None, ragged=False):
         """wav (B, samples) -> encoder output (B, ceil(T/4), d_model): the path the headline metric times.
         ``feats``: features() of the batch computed by the caller (a graphed training step keeps Fbank, the running
-        normalisation statistics and the host-drawn augmentation outside its hipGraph, brain.Brain.graph_prologue)."""
+        normalisation statistics and the host-drawn augmentation outside its hipGraph, brain.Brain.graph_prologue).
+        ``ragged=True`` (inference): every utterance is encoded as if alone -> (enc, row_lens).  ``wav_lens`` gives the
+        utterances' lengths, relative (floating: round(rel * samples) samples) or absolute (integer sample counts); utterance b's rows
+        [0, row_lens[b]) are those of encode on wavs[b:b+1, :n[b]] alone, rows past them are unspecified; row_lens is a fused.RowLens
+        (a host list whose .dev is the device tensor).  An utterance under the front end's 5 frames raises ValueError.  The default
+        keeps the reference's semantics: wav_lens is ignored and padding reaches every utterance of the batch."""
+        if ragged:
+            return self._encode_ragged(wavs, wav_lens, epoch)
         if feats is not None:
             return self.Transformer.encode(self.CNN(feats), wav_lens)
         if (not torch.is_grad_enabled()) and (not self.training) and wavs.is_cuda and augment is None \
@@ -116,6 +123,23 @@ class ConMambaASR(nn.Module):
                 return fused.asr_encode(self, wavs, wav_lens)                    # native inference path
         src = self.CNN(self.features(wavs, wav_lens, epoch, augment))
         return self.Transformer.encode(src, wav_lens)
+
+    def _encode_ragged(self, wavs, wav_lens, epoch=0):
+        from . import fused
+        if torch.is_grad_enabled() or self.training:
+            raise ValueError("encode(ragged=True) is the inference path: call eval() and run under torch.no_grad()")
+        n = fused.ragged_sample_counts(wav_lens, wavs.shape[1], self.compute_features.hop)
+        if wavs.is_cuda and self.normalize.count > 0 and all(fused.supports(layer) for layer in self.Transformer.encoder.layers):
+            return fused.asr_encode(self, wavs, wav_lens, n_samples=n)
+        # no native path (CPU, statistics not calibrated, another layer): each utterance alone through encode, scattered
+        rows = [fused.frontend_rows_total(x, self.compute_features.hop) for x in n]
+        one = torch.ones(1, device=wavs.device)
+        outs = [self.encode(wavs[b:b + 1, :x], one, epoch) for b, x in enumerate(n)]
+        enc = torch.zeros((len(n), max(rows), outs[0].shape[-1]), dtype=outs[0].dtype, device=wavs.device)
+        for b, e in enumerate(outs):
+            assert e.shape[1] == rows[b], (e.shape, rows[b])
+            enc[b, :rows[b]] = e[0]
+        return enc, fused.RowLens(rows, torch.tensor(rows, dtype=torch.int32).to(wavs.device))
 
     def encode_streaming(self, src, context, lens=None):
         """The next chunk of the CNN front end's output rows (B, t, F, C) or (B, t, F * C) of the streams in ``context``
@@ -196,7 +220,7 @@ class ConMambaASR(nn.Module):
 
     @torch.no_grad()
     def transcribe_s2s(self, wavs, wav_lens, searcher=None, ctc_weight=None, beam_size=None, length_normalization=True,
-                       temperature=1.0, topk=1, lm_scorer=None, lm_weight=None):
+                       temperature=1.0, topk=1, lm_scorer=None, lm_weight=None, ragged=False):
         """wav (B, samples) -> (hyps, lengths, scores, log_probs) of the S2S searcher (s2s_decode.S2SGreedySearcher with the
         config's bos / eos indices and decode ratios unless ``searcher`` is given): frontend -> encode -> token loop on
         the stepped decoder (Mamba, or Transformer with the memory frames beyond each utterance's length masked).  What train_S2S.py:382-394 does at its VALID / TEST stages.  ``ctc_weight`` (the recipes'
@@ -204,7 +228,9 @@ class ConMambaASR(nn.Module):
         output)) added with this weight to every token's log-probability; None: the decoder alone.  ``beam_size`` (the recipes'
         valid_beam_size 10 / test_beam_size 66): s2s_decode.S2SBeamSearcher with ``length_normalization``, ``temperature`` and
         ``topk``; None: the greedy searcher.  ``lm_scorer`` / ``lm_weight`` (the recipes' TransformerLMScorer at lm_weight 0.60):
-        a language model as a second scorer of the beam search (s2s_decode.TransformerLMScorer); both need ``beam_size``."""
+        a language model as a second scorer of the beam search (s2s_decode.TransformerLMScorer); both need ``beam_size``.
+        ``ragged=True``: encode(..., ragged=True), every utterance encoded as if alone, and the searcher gets relative lengths that
+        reproduce row_lens exactly (row_lens[b] / rows of the batch)."""
         assert self.cfg.num_decoder_layers > 0, "transcribe_s2s needs a decoder (S2S configuration)"
         assert not self.training, "transcribe_s2s is the inference path: call eval() first"
         if searcher is not None and ctc_weight is not None:
@@ -232,6 +258,13 @@ class ConMambaASR(nn.Module):
                 searcher = S2SBeamSearcher(modules=modules, beam_size=beam_size, length_normalization=length_normalization,
                                            temperature=temperature, topk=topk, lm_scorer=lm_scorer,
                                            lm_weight=0.0 if lm_weight is None else lm_weight, **args)
+        if ragged:
+            enc, row_lens = self.encode(wavs, wav_lens, ragged=True)
+            # the searchers round rel * rows: (r + 0.25) / rows rounds to r for every 0 < r <= rows (no tie, no float edge)
+            rel = torch.tensor([min(1.0, (r + 0.25) / enc.shape[1]) for r in row_lens], dtype=torch.float32, device=enc.device)
+            # rows past an utterance's own are unspecified (NaN included) and the Mamba decoder reads the whole memory: zeros there
+            own = torch.arange(enc.shape[1], device=enc.device)[None, :, None] < row_lens.dev.to(enc.device)[:, None, None]
+            return searcher(torch.where(own, enc, torch.zeros((), dtype=enc.dtype, device=enc.device)), rel)
         return searcher(self.encode(wavs, wav_lens), wav_lens)
 
     def s2s_objective(self, p_ctc, p_seq, tokens, tokens_lens, tokens_eos, tokens_eos_lens, wav_lens, ctc_weight=0.3,

@@ -74,10 +74,19 @@ struct cf_slot_args : cm_cnn_front_stream_args {
     const int32_t *plan;
 };
 
+// Whole utterances of different lengths (cm_cnn_front_lens; ARGS = cf_lens_args, STREAM = false): utterance b has frames[b] feature
+// frames, clamped to [0, p.T]; T / T1 / T2 / tiles_per_utt are replaced per utterance, so both reflections happen at its own ends and
+// its rows past T2 are not computed.  p.T stays the row stride of feats, ceil(ceil(p.T / 2) / 2) that of out.  Under 5 frames the
+// utterance is skipped.
+struct cf_lens_args : cm_cnn_front_args {
+    const int32_t *frames;
+};
+
 template <bool STREAM, typename ARGS>
 __global__ __launch_bounds__(512) void cnn_front_kernel(const ARGS p, int T, int T1, int T2, int tiles_per_utt, int chunk, int chunks_per_utt,
                                                         int nchunks) {
     constexpr bool SLOT = std::is_same<ARGS, cf_slot_args>::value;
+    constexpr bool LENS = std::is_same<ARGS, cf_lens_args>::value;
     [[maybe_unused]] int f0s = 0, nfs = 1;                        // SLOT: this stream's first frame and frame count
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     front_lds &L = *reinterpret_cast<front_lds *>(smem);
@@ -187,7 +196,7 @@ __global__ __launch_bounds__(512) void cnn_front_kernel(const ARGS p, int T, int
 
     for (int ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
         const int b = ch / chunks_per_utt, tile0 = (ch % chunks_per_utt) * chunk;
-        [[maybe_unused]] int out_rows = 0;                        // SLOT: rows of out per stream (the widest slot's)
+        [[maybe_unused]] int out_rows = 0;                        // SLOT / LENS: rows of out per stream (the widest one's)
         if constexpr (SLOT) {
             const int32_t *s = p.plan + (int64_t)b * 8;
             const int nr = s[6], Tt = s[7];
@@ -197,9 +206,18 @@ __global__ __launch_bounds__(512) void cnn_front_kernel(const ARGS p, int T, int
             out_rows = p.nr;
             if (tile0 >= tiles_per_utt) continue;                 // uniform over the workgroup: b depends on ch only
         }
+        if constexpr (LENS) {
+            const int Tb = min(max(p.frames[b], 0), p.T);
+            T = Tb, T1 = (Tb + 1) / 2, T2 = (T1 + 1) / 2, tp_last = T1 + 1;
+            tiles_per_utt = (T2 + TT - 1) / TT;
+            out_rows = ((p.T + 1) / 2 + 1) / 2;
+            if (Tb < 5 || tile0 >= tiles_per_utt) continue;       // uniform over the workgroup: b depends on ch only
+        }
         const int tile1 = min(tile0 + chunk, tiles_per_utt);
         const float *feats;
-        if constexpr (STREAM) {
+        if constexpr (LENS) {
+            feats = p.feats + (int64_t)b * p.T * F0;
+        } else if constexpr (STREAM) {
             feats = p.feats + (int64_t)b * p.nf * F0;
             hist = p.feat_hist ? p.feat_hist + (int64_t)b * FH * F0 : nullptr;
         } else {
@@ -260,7 +278,7 @@ __global__ __launch_bounds__(512) void cnn_front_kernel(const ARGS p, int T, int
                     sq = fmaf(vv[k].x, vv[k].x, fmaf(vv[k].y, vv[k].y, sq));
                 }
                 const float rstd = rsqrtf(wave_sum64(sq) * (1.f / nfeat) + p.eps2);
-                uint16_t *dst = out + ((int64_t)b * (SLOT ? out_rows : T2 - rbase) + (r0 - rbase) + wave) * nfeat;
+                uint16_t *dst = out + ((int64_t)b * (SLOT || LENS ? out_rows : T2 - rbase) + (r0 - rbase) + wave) * nfeat;
 #pragma unroll
                 for (int k = 0; k < nfeat / 128; ++k) {
                     const int i = lane + 64 * k;
@@ -310,6 +328,44 @@ extern "C" int cm_cnn_front(const cm_cnn_front_args *args) {
     hipLaunchKernelGGL((cnn_front_kernel<false, cm_cnn_front_args>), dim3((unsigned)grid), dim3(512), sizeof(front_lds),
                        reinterpret_cast<hipStream_t>(a.stream), a, a.T, T1, T2, tiles_per_utt, chunk, chunks_per_utt, (int)nchunks);
     return cm_launch_status("cm_cnn_front");
+}
+
+extern "C" int cm_cnn_front_lens(const cm_cnn_front_args *args, const int32_t *frames) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "cnn_front_lens: args is NULL");
+    CM_REQUIRE(frames != nullptr, CM_EINVAL, "cnn_front_lens: frames is NULL (cm_cnn_front is the form without lengths)");
+    CM_REQUIRE(cm_aligned(frames, 4), CM_EALIGN, "cnn_front_lens: frames must be 4-byte aligned");
+    const cm_cnn_front_args &a = *args;
+    CM_REQUIRE(a.batch > 0 && a.T >= 5 && a.feats && a.w1 && a.ln1_g && a.ln1_b && a.w2 && a.ln2_g && a.ln2_b && a.out, CM_EINVAL,
+               "cnn_front_lens: bad sizes or NULL tensor");
+    CM_REQUIRE(a.F == F0 && a.C1 == C1 && a.C2 == C2, CM_EUNSUPPORTED, "cnn_front_lens: only 80 bins, channels (64, 32) (got F %d, C %d, %d)", a.F,
+               a.C1, a.C2);
+    CM_REQUIRE(cm_aligned(a.w2, 16) && cm_aligned(a.out, 4) && cm_aligned(a.ln1_g, 8) && cm_aligned(a.ln1_b, 8) && cm_aligned(a.ln2_g, 8) &&
+                   cm_aligned(a.ln2_b, 8) && (!a.b2 || cm_aligned(a.b2, 16)),
+               CM_EALIGN, "cnn_front_lens: w2 / b2 must be 16-byte aligned, LayerNorm parameters 8-byte aligned");
+    // the grid and the chunks are those of the widest utterance; a chunk past an utterance's own tiles is skipped
+    const int T1 = (a.T + 1) / 2, T2 = (T1 + 2 - 3) / 2 + 1;
+    const int tiles_per_utt = (T2 + TT - 1) / TT;
+    const int chunk = 16;
+    const int chunks_per_utt = (tiles_per_utt + chunk - 1) / chunk;
+    const int64_t nchunks = (int64_t)a.batch * chunks_per_utt;
+    CM_REQUIRE(nchunks <= 2147483647, CM_EINVAL, "cnn_front_lens: too many chunks");
+    static bool attr_done = false;
+    if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(cnn_front_kernel<false, cf_lens_args>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        if (e != hipSuccess) {
+            cm_set_error("cnn_front_lens: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+            return (int)e;
+        }
+        attr_done = true;
+    }
+    cf_lens_args k{};
+    static_cast<cm_cnn_front_args &>(k) = a;
+    k.frames = frames;
+    const int64_t grid = nchunks < 256 ? nchunks : 256;
+    hipLaunchKernelGGL((cnn_front_kernel<false, cf_lens_args>), dim3((unsigned)grid), dim3(512), sizeof(front_lds),
+                       reinterpret_cast<hipStream_t>(a.stream), k, a.T, T1, T2, tiles_per_utt, chunk, chunks_per_utt, (int)nchunks);
+    return cm_launch_status("cm_cnn_front_lens");
 }
 
 extern "C" int cm_cnn_front_stream(const cm_cnn_front_stream_args *args) {

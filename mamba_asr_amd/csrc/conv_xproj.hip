@@ -59,12 +59,18 @@ struct cx_uni_args : cm_conv_xproj_args {
 struct cx_slot_args : cx_uni_args {
     const int32_t *lens;
 };
+// the two-direction launch on whole utterances of different lengths (cm_conv_xproj_lens): utterance b has lens[b] rows, clamped to
+// [0, seqlen]; every descriptor and the x_dbl store are cut behind its last row, tiles past it exit
+struct cx_lens_args : cm_conv_xproj_args {
+    const int32_t *lens;
+};
 
 // NB: 16-column bands of x_dbl per direction: 3 = [dt16 | B | C], 4 = [dt32 | B | C] (dt_rank 17..32: the S2S-large encoder)
 template <int TT, int NB, typename P = cm_conv_xproj_args>
 __global__ __launch_bounds__(256, (TT == 16 && NB == 3) ? 4 : 2) void conv_xproj_kernel(const P p, const int ntile, const int stamp_arg = 0) {
     constexpr bool UNI = std::is_base_of<cx_uni_args, P>::value;  // one direction, rows in front of the chunk from p.x_hist
     constexpr bool SLOT = std::is_same<P, cx_slot_args>::value;   // the new history is cut behind row lens[b] - 1, not behind row T - 1
+    constexpr bool LENS = std::is_same<P, cx_lens_args>::value;   // T below is the utterance's own row count
     constexpr int HR = UNI ? 0 : W - 1;                           // rows behind a step that its outputs read
     constexpr int NR = (W - 1) + HR, NWIN = NR + 1;               // halo rows per run of steps; rows of the sliding window
 #ifdef CM_ABLATE
@@ -78,7 +84,8 @@ __global__ __launch_bounds__(256, (TT == 16 && NB == 3) ? 4 : 2) void conv_xproj
     constexpr int TH = TT / 2;
     constexpr int NP = NB * 16;                                   // x_dbl columns per direction
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int E = p.dim, T = p.seqlen;
+    const int E = p.dim;
+    int T = p.seqlen;
     const int XS = E + 16;                                        // LDS row stride in bf16 elements
     uint16_t *ut[2] = {reinterpret_cast<uint16_t *>(smem), reinterpret_cast<uint16_t *>(smem) + TT * XS};
     const int tid = threadIdx.x, lane = tid & 63;
@@ -89,6 +96,10 @@ __global__ __launch_bounds__(256, (TT == 16 && NB == 3) ? 4 : 2) void conv_xproj
     int id = blockIdx.x;
     if ((total & 7) == 0) id = (id & 7) * (total >> 3) + (id >> 3);
     const int b = id / ntile, t0 = (id % ntile) * TT;
+    if constexpr (LENS) {
+        T = min(max(p.lens[b], 0), T);
+        if (t0 >= T) return;                                      // the whole workgroup: nothing to read or write (T == 0 forms no descriptor)
+    }
     // buffer descriptors over this utterance's slices: rows outside [0, T) fall outside the buffer (reads return 0 = the
     // conv's zero padding, stores are dropped) and per-row addresses are an SGPR offset, so no per-access address math
     const int x_ts = (int)p.x_ts * 2, yf_ts = (int)p.yf_ts * 2, yb_ts = (int)p.yb_ts * 2;      // row strides in bytes
@@ -323,7 +334,8 @@ int launch_cx(const P &a) {
     const int ntile = (a.seqlen + TT - 1) / TT;
     CM_REQUIRE((long)ntile * a.batch < (1L << 31), CM_EINVAL, "conv_xproj: grid too large");
     hipLaunchKernelGGL((conv_xproj_kernel<TT, NB, P>), dim3((unsigned)(ntile * a.batch)), dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), a, ntile, cm_debug_get() == 18 ? 1 : (cm_debug_get() == 19 ? 2 : 0));
-    return cm_launch_status(std::is_same<P, cx_slot_args>::value ? "cm_conv_xproj_uni_slots" : ND == 1 ? "cm_conv_xproj_uni" : "cm_conv_xproj");
+    return cm_launch_status(std::is_same<P, cx_slot_args>::value ? "cm_conv_xproj_uni_slots" : ND == 1 ? "cm_conv_xproj_uni"
+                            : std::is_same<P, cx_lens_args>::value ? "cm_conv_xproj_lens" : "cm_conv_xproj");
 }
 
 }  // namespace
@@ -334,9 +346,8 @@ extern "C" int cm_debug_read_stamps_cx(unsigned long long *out) {
 }
 #endif
 
-extern "C" int cm_conv_xproj(const cm_conv_xproj_args *args) {
-    CM_REQUIRE(args != nullptr, CM_EINVAL, "conv_xproj: args is NULL");
-    const cm_conv_xproj_args &a = *args;
+// cm_conv_xproj (lens == NULL) and cm_conv_xproj_lens: one set of checks, one choice of tile shape
+static int conv_xproj_entry(const cm_conv_xproj_args &a, const int32_t *lens) {
     CM_REQUIRE(a.batch > 0 && a.seqlen > 0 && a.dim > 0 && a.x && a.weight_f && a.weight_b && a.wx_f && a.wx_b && a.y_fwd &&
                    a.y_bwd && a.xdbl, CM_EINVAL, "conv_xproj: bad sizes or NULL tensor");
     CM_REQUIRE(a.width == W, CM_EUNSUPPORTED, "conv_xproj: conv width %d unsupported (4 only)", a.width);
@@ -349,11 +360,29 @@ extern "C" int cm_conv_xproj(const cm_conv_xproj_args *args) {
     // 32-step tiles when the LDS tiles fit twice per CU and the sequence is long enough to fill the chip with them
     const bool wide = a.variant != 1 && (size_t)2 * 32 * (a.dim + 16) * 2 <= 72 * 1024 && (long)a.batch * ((a.seqlen + 31) / 32) >= 512;
     CM_REQUIRE(a.dt_pad == 0 || a.dt_pad == 16 || a.dt_pad == 32, CM_EUNSUPPORTED, "conv_xproj: dt_pad %d (16 or 32)", a.dt_pad);
-    if (a.dt_pad == 32) {
+    if (a.dt_pad == 32)
         CM_REQUIRE((size_t)2 * 16 * (a.dim + 16) * 2 <= 80 * 1024, CM_EUNSUPPORTED, "conv_xproj: dim %d too wide for 64-column rows", a.dim);
-        return wide ? launch_cx<32, 4>(a) : launch_cx<16, 4>(a);
+    if (lens) {
+        cx_lens_args s{};
+        static_cast<cm_conv_xproj_args &>(s) = a;
+        s.lens = lens;
+        if (a.dt_pad == 32) return wide ? launch_cx<32, 4>(s) : launch_cx<16, 4>(s);
+        return wide ? launch_cx<32, 3>(s) : launch_cx<16, 3>(s);
     }
+    if (a.dt_pad == 32) return wide ? launch_cx<32, 4>(a) : launch_cx<16, 4>(a);
     return wide ? launch_cx<32, 3>(a) : launch_cx<16, 3>(a);
+}
+
+extern "C" int cm_conv_xproj(const cm_conv_xproj_args *args) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "conv_xproj: args is NULL");
+    return conv_xproj_entry(*args, nullptr);
+}
+
+extern "C" int cm_conv_xproj_lens(const cm_conv_xproj_args *args, const int32_t *lens) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "conv_xproj_lens: args is NULL");
+    CM_REQUIRE(lens != nullptr, CM_EINVAL, "conv_xproj_lens: lens is NULL (cm_conv_xproj is the form without lengths)");
+    CM_REQUIRE(cm_aligned(lens, 4), CM_EALIGN, "conv_xproj_lens: lens must be 4-byte aligned");
+    return conv_xproj_entry(*args, lens);
 }
 
 // cm_conv_xproj_uni (lens == NULL) and cm_conv_xproj_uni_slots: one set of checks, one choice of tile shape

@@ -200,6 +200,17 @@ struct dw_causal_args : cm_glu_dwconv_args {
 struct dw_slot_args : dw_causal_args {
     const int32_t *lens;
 };
+// the non-causal launch on whole utterances of different lengths (cm_glu_dwconv_ln_gelu_lens): utterance b has lens[b] rows, clamped to
+// [0, seqlen]; rows at and past it stage as the 'same' padding's zeros and are not written
+struct dw_lens_args : cm_glu_dwconv_args {
+    const int32_t *lens;
+};
+// rows of utterance b that exist: seqlen, or the utterance's own count (seqlen stays the batch stride of in / out)
+template <typename P>
+__device__ __forceinline__ int dw_valid_rows(const P &p, int b) {
+    if constexpr (std::is_same<P, dw_lens_args>::value) return min(max(p.lens[b], 0), p.seqlen);
+    else return p.seqlen;
+}
 
 // Whether this workgroup (time tile `tile` of TT steps) writes utterance b's hist_out, and the row count T_cut the history is cut
 // behind.  Lock step: the last tile, seqlen.  Per slot: the tile that holds gated row lens[b] - 1 -- it has the K - 1 rows in front
@@ -235,6 +246,8 @@ __global__ __launch_bounds__(256) void glu_dwconv_kernel(const P p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int D = p.dim, T = p.seqlen;
     const int b = blockIdx.y, t0 = blockIdx.x * tt;
+    const int TV = dw_valid_rows(p, b);                           // t < TV: the row exists
+    if constexpr (std::is_same<P, dw_lens_args>::value) { if (t0 >= TV) return; }     // the whole workgroup, before any barrier
     const int nin = tt + K - 1;                                   // input rows t0-K/2 .. t0+tt-1+K/2 (causal: t0-(K-1) .. t0+tt-1)
     const int CS = D + 16;                                        // co row stride: rows of one wave land in different banks
     float *co = sm;                                               // [tt][CS] fp32 conv outputs
@@ -254,7 +267,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_kernel(const P p) {
             const int r = idx / (D / NV), c = (idx % (D / NV)) * NV;
             const int t = t0 - PL + r;
             uint4 v4 = {0u, 0u, 0u, 0u};
-            if (t >= 0 && t < T) v4 = *reinterpret_cast<const uint4 *>(in + (int64_t)t * D + c);
+            if (t >= 0 && t < TV) v4 = *reinterpret_cast<const uint4 *>(in + (int64_t)t * D + c);
             else if (const IO *h = hist_row(t)) v4 = *reinterpret_cast<const uint4 *>(h + c);
             *reinterpret_cast<uint4 *>(g + r * D + c) = v4;
         }
@@ -265,7 +278,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_kernel(const P p) {
             float av[NV], gv[NV];
             if (const IO *h = hist_row(t)) {
                 vec8<IO>::load(h + c, av);
-            } else if (t >= 0 && t < T) {
+            } else if (t >= 0 && t < TV) {
                 const IO *row = in + (int64_t)t * 2 * D;
                 vec8<IO>::load(row + c, av);
                 vec8<IO>::load(row + D + c, gv);
@@ -282,7 +295,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_kernel(const P p) {
             const int r = idx / D, c = idx % D;
             const int t = t0 - PL + r;
             float v0 = 0.f;
-            if (t >= 0 && t < T) {
+            if (t >= 0 && t < TV) {
                 const IO *row = in + (int64_t)t * IW;
                 v0 = pre ? cm_elem<IO>::load(row + c) : cm_elem<IO>::load(row + c) * cm_sigmoid(cm_elem<IO>::load(row + D + c));
             } else if (const IO *h = hist_row(t)) {
@@ -338,7 +351,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_kernel(const P p) {
                 sq = fmaf(v[i].x, v[i].x, fmaf(v[i].y, v[i].y, fmaf(v[i].z, v[i].z, fmaf(v[i].w, v[i].w, sq))));
             }
             const float rstd = rsqrtf(cm_group_sum<16>(sq) * (1.f / 256) + p.eps);
-            if (t < T) {
+            if (t < TV) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int c = 4 * (l15 + 16 * i);
@@ -361,7 +374,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_kernel(const P p) {
     }
     for (int r = wave; r < tt; r += 4) {
         const int t = t0 + r;
-        if (t >= T) break;
+        if (t >= TV) break;
         float s = 0.f;
         for (int c = lane; c < D; c += 64) s += co[r * CS + c];
         const float mean = wave_sum(s) / D;
@@ -407,6 +420,8 @@ __global__ __launch_bounds__(256, DV == 4 ? 4 : 2) void dwconv_rows_kernel(const
     uint16_t *xt = reinterpret_cast<uint16_t *>(sm);              // LIN: [TT][XS] activations, overlays co after phase 3
     const int T = p.seqlen, tid = threadIdx.x;
     const int b = blockIdx.y, t0 = blockIdx.x * TT;
+    const int TV = dw_valid_rows(p, b);                           // t < TV: the row exists
+    if constexpr (std::is_same<P, dw_lens_args>::value) { if (t0 >= TV) return; }     // the whole workgroup, before any barrier
     const bool pre = p.glu_done != 0;
     const int IW = pre ? D : 2 * D;
     const uint16_t *in = reinterpret_cast<const uint16_t *>(p.in) + (int64_t)b * T * IW;
@@ -428,7 +443,7 @@ __global__ __launch_bounds__(256, DV == 4 ? 4 : 2) void dwconv_rows_kernel(const
             const int idx = tid + 256 * i, r = idx / (D / 8), c = (idx % (D / 8)) * 8;
             const int t = t0 - PL + r;
             v[i] = uint4{0u, 0u, 0u, 0u};
-            if (idx < NCH && t >= 0 && t < T) v[i] = *reinterpret_cast<const uint4 *>(in + (int64_t)t * IW + c);
+            if (idx < NCH && t >= 0 && t < TV) v[i] = *reinterpret_cast<const uint4 *>(in + (int64_t)t * IW + c);
             else if (const uint16_t *h = idx < NCH ? hist_row(t) : nullptr) v[i] = *reinterpret_cast<const uint4 *>(h + c);
         }
 #pragma unroll
@@ -443,7 +458,7 @@ __global__ __launch_bounds__(256, DV == 4 ? 4 : 2) void dwconv_rows_kernel(const
         uint4 v = {0u, 0u, 0u, 0u};
         if (const uint16_t *h = hist_row(t)) {
             v = *reinterpret_cast<const uint4 *>(h + c);
-        } else if (t >= 0 && t < T) {
+        } else if (t >= 0 && t < TV) {
             v = *reinterpret_cast<const uint4 *>(in + (int64_t)t * IW + c);
             if (!pre) {                                           // GLU: a * sigmoid(gate), gate = the row's second half
                 const uint4 q = *reinterpret_cast<const uint4 *>(in + (int64_t)t * IW + D + c);
@@ -532,7 +547,7 @@ __global__ __launch_bounds__(256, DV == 4 ? 4 : 2) void dwconv_rows_kernel(const
             sq = fmaf(v[i].x, v[i].x, fmaf(v[i].y, v[i].y, fmaf(v[i].z, v[i].z, fmaf(v[i].w, v[i].w, sq))));
         }
         const float rstd = rsqrtf(cm_group_sum<16>(sq) * (1.f / D) + p.eps);
-        if (LIN || t < T) {
+        if (LIN || t < TV) {
 #pragma unroll
             for (int i = 0; i < DV; ++i) {
                 const int c = 4 * (l15 + 16 * i);
@@ -591,7 +606,7 @@ __global__ __launch_bounds__(256, DV == 4 ? 4 : 2) void dwconv_rows_kernel(const
         for (int i = 0; i < TT * 32 / 256; ++i) {
             const int idx = tid + 256 * i, row = idx >> 5, chunk = idx & 31;
             const uint4 v = *reinterpret_cast<const uint4 *>(xt + row * XS + chunk * 8);
-            if (t0 + row < T) *reinterpret_cast<uint4 *>(out + (int64_t)(t0 + row) * D + chunk * 8) = v;
+            if (t0 + row < TV) *reinterpret_cast<uint4 *>(out + (int64_t)(t0 + row) * D + chunk * 8) = v;
         }
     }
 }
@@ -804,6 +819,7 @@ template <typename P>
 int glu_dwconv_dispatch(const P &a) {
     constexpr bool CAUSAL = std::is_base_of<dw_causal_args, P>::value;
     constexpr bool SLOT = std::is_same<P, dw_slot_args>::value;
+    constexpr bool LENS = std::is_same<P, dw_lens_args>::value;
     CM_REQUIRE(a.batch > 0 && a.seqlen > 0 && a.dim > 0 && a.in && a.out && a.weight && a.ln_g && a.ln_b, CM_EINVAL,
                "glu_dwconv: bad sizes or NULL tensor");
     CM_REQUIRE(a.ksize == 31, CM_EUNSUPPORTED, "glu_dwconv: kernel size %d unsupported (31 only)", a.ksize);
@@ -837,7 +853,7 @@ int glu_dwconv_dispatch(const P &a) {
                 if (e != hipSuccess) { cm_set_error("glu_dwconv: LDS attribute failed: %s", hipGetErrorString(e)); return (int)e; }
             }
             hipLaunchKernelGGL(kern, grid, dim3(256), smem, st0, a);
-            return cm_launch_status(SLOT ? "cm_glu_dwconv_ln_gelu_causal_slots(rows)" : CAUSAL ? "cm_glu_dwconv_ln_gelu_causal(rows)" : "cm_glu_dwconv_ln_gelu(rows)");
+            return cm_launch_status(SLOT ? "cm_glu_dwconv_ln_gelu_causal_slots(rows)" : CAUSAL ? "cm_glu_dwconv_ln_gelu_causal(rows)" : LENS ? "cm_glu_dwconv_ln_gelu_lens(rows)" : "cm_glu_dwconv_ln_gelu(rows)");
         };
         if (lin) return run(dwconv_rows_kernel<31, TT, 4, true, P>);
         return a.dim == 256 ? run(dwconv_rows_kernel<31, TT, 4, false, P>) : run(dwconv_rows_kernel<31, TT, 8, false, P>);
@@ -858,7 +874,7 @@ int glu_dwconv_dispatch(const P &a) {
             if (e != hipSuccess) { cm_set_error("glu_dwconv: LDS attribute failed: %s", hipGetErrorString(e)); return (int)e; }
         }
         hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, a);
-        return cm_launch_status(SLOT ? "cm_glu_dwconv_ln_gelu_causal_slots" : CAUSAL ? "cm_glu_dwconv_ln_gelu_causal" : "cm_glu_dwconv_ln_gelu");
+        return cm_launch_status(SLOT ? "cm_glu_dwconv_ln_gelu_causal_slots" : CAUSAL ? "cm_glu_dwconv_ln_gelu_causal" : LENS ? "cm_glu_dwconv_ln_gelu_lens" : "cm_glu_dwconv_ln_gelu");
     };
     if (a.io_dtype == CM_BF16) {
         if (tt == 16) return go(glu_dwconv_kernel<cm_bf16, 31, 16, P>);
@@ -875,6 +891,16 @@ int glu_dwconv_dispatch(const P &a) {
 extern "C" int cm_glu_dwconv_ln_gelu(const cm_glu_dwconv_args *args) {
     CM_REQUIRE(args != nullptr, CM_EINVAL, "glu_dwconv: args is NULL");
     return glu_dwconv_dispatch(*args);
+}
+
+extern "C" int cm_glu_dwconv_ln_gelu_lens(const cm_glu_dwconv_args *args, const int32_t *lens) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "glu_dwconv_lens: args is NULL");
+    CM_REQUIRE(lens != nullptr, CM_EINVAL, "glu_dwconv_lens: lens is NULL (cm_glu_dwconv_ln_gelu is the form without lengths)");
+    CM_REQUIRE(cm_aligned(lens, 4), CM_EALIGN, "glu_dwconv_lens: lens must be 4-byte aligned");
+    dw_lens_args a{};
+    static_cast<cm_glu_dwconv_args &>(a) = *args;
+    a.lens = lens;
+    return glu_dwconv_dispatch(a);
 }
 
 static void dw_causal_fill(dw_causal_args &a, const cm_glu_dwconv_causal_args &u) {

@@ -70,6 +70,12 @@ __device__ __forceinline__ int rev4_8bit(int k) {                     // reverse
 struct fb_slot_args : cm_fbank_stream_args {
     const int32_t *plan;
 };
+// Whole utterances of different lengths (cm_fbank_wav_lens; ARGS = fb_lens_args, STREAM = false): utterance b has nsamp[b] samples,
+// clamped to [0, samples] -- the waveform's descriptor ends there, so what lies behind reads as zero -- and 1 + nsamp[b] / hop frames
+// (none for 0 samples).  Frames past them are not computed and stay out of the tile maxima; the struct's frames is the row stride of db.
+struct fb_lens_args : cm_fbank_args {
+    const int32_t *nsamp;
+};
 enum { PL_N = 0, PL_CONSUMED = 1, PL_TOTAL = 2, PL_F0 = 3, PL_NF = 4, PL_R0 = 5, PL_NR = 6, PL_TTOTAL = 7, PL_W = 8 };
 template <typename ARGS>
 __device__ __forceinline__ ARGS fb_view(const ARGS &pk, int b) {      // the arguments as stream b sees them
@@ -87,10 +93,20 @@ template <bool STREAM, typename ARGS>
 __global__ __launch_bounds__(256) void fbank_wav_kernel(const ARGS pk, const float floor_db) {
     extern __shared__ float sm[];
     constexpr bool SLOT = std::is_same<ARGS, fb_slot_args>::value;
+    constexpr bool LENS = std::is_same<ARGS, fb_lens_args>::value;
     const int b = blockIdx.y;
     const ARGS p = fb_view(pk, b);
     int t0, T;                                                    // first frame of this workgroup, end of the valid frames
+    [[maybe_unused]] int nsv = 0;                                 // LENS: this utterance's samples
     if constexpr (STREAM) { t0 = p.f0 + blockIdx.x * FT; T = p.f0 + p.nf; }
+    else if constexpr (LENS) {
+        nsv = min(max(p.nsamp[b], 0), p.samples);
+        t0 = blockIdx.x * FT; T = nsv > 0 ? 1 + nsv / p.hop : 0;
+        if (t0 >= T) {                                            // the whole workgroup, before any barrier: no frame of the utterance here
+            if (threadIdx.x == 0) p.umax_part[(int64_t)b * gridDim.x + blockIdx.x] = -INFINITY;
+            return;
+        }
+    }
     else { t0 = blockIdx.x * FT; T = p.frames; }
     const int F = NH + 1, M = p.n_mels;
     float *pw = sm;                                               // [F][PWS] power tile
@@ -149,7 +165,7 @@ __global__ __launch_bounds__(256) void fbank_wav_kernel(const ARGS pk, const flo
     const int r3 = ((lane & 3) << 4) | (lane & 12) | (lane >> 4);  // Z[lane + 64 i] sits at position 4 r3 + i
     __amdgpu_buffer_rsrc_t wr;
     if constexpr (!STREAM)
-        wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.wav + (int64_t)b * p.wav_bs), 0, p.samples * 4, 0x00020000);
+        wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.wav + (int64_t)b * p.wav_bs), 0, (LENS ? nsv : p.samples) * 4, 0x00020000);
     cf *z = zb + wave * ZN;
 
     // positions (padded) of this lane's butterfly operands in stages 0..3 and of its split-step reads
@@ -256,7 +272,7 @@ __global__ __launch_bounds__(256) void fbank_wav_kernel(const ARGS pk, const flo
         const int nrow = min(FT, T - t0);                         // rows t0 .. t0 + nrow - 1 are contiguous in db: one linear copy
         float *dst;
         if constexpr (STREAM) dst = p.db + ((int64_t)b * pk.nf + (t0 - p.f0)) * M;
-        else dst = p.db + ((int64_t)b * T + t0) * M;
+        else dst = p.db + ((int64_t)b * (LENS ? p.frames : T) + t0) * M;
         for (int i = tid; i < nrow * M; i += 256) dst[i] = dbt[i];
     }
     if constexpr (STREAM) {
@@ -277,6 +293,33 @@ __global__ __launch_bounds__(256) void fbank_wav_kernel(const ARGS pk, const flo
     __syncthreads();
     if constexpr (!STREAM)
         if (tid == 0) p.umax_part[(int64_t)b * gridDim.x + blockIdx.x] = fmaxf(fmaxf(pw[0], pw[1]), fmaxf(pw[2], pw[3]));
+}
+
+// cm_fbank_finish_lens: cm_fbank_finish's kernel (frontend.hip) with the utterance's own frame count -- the maximum over the tiles
+// that hold its frames [0, T_b) (fbank_wav_kernel<false, fb_lens_args> kept the frames behind them out of the last one), the clamp
+// and the normalisation on those frames only.  grid (chunks, batch).
+__global__ __launch_bounds__(256) void fbank_finish_lens_kernel(const fb_lens_args p, int ntiles) {
+    __shared__ float red[4];
+    const int b = blockIdx.y;
+    const int nsv = min(max(p.nsamp[b], 0), p.samples), Tb = nsv > 0 ? 1 + nsv / p.hop : 0;
+    if (Tb == 0) return;
+    const int nt = (Tb + FT - 1) / FT;
+    float mx = -INFINITY;
+    for (int i = threadIdx.x; i < nt; i += blockDim.x) mx = fmaxf(mx, p.umax_part[(int64_t)b * ntiles + i]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    const float um = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    if (blockIdx.x == 0 && threadIdx.x == 0) p.umax[b] = um;
+    const float floor_db = um - p.top_db;
+    const int64_t per_utt = (int64_t)Tb * p.n_mels;
+    float *db = p.db + (int64_t)b * p.frames * p.n_mels;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_utt; i += (int64_t)gridDim.x * blockDim.x) {
+        float v = fmaxf(db[i], floor_db);
+        if (p.mean) { const int m = (int)(i % p.n_mels); v = (v - p.mean[m]) / p.std[m]; }
+        db[i] = v;
+    }
 }
 
 // cm_fbank_finish_stream: one workgroup per stream.  Thread = (frame group g, mel bin m): every thread carries the prefix maximum
@@ -333,9 +376,8 @@ __global__ __launch_bounds__(256) void fbank_finish_slots_kernel(const fb_slot_a
 
 }  // namespace
 
-extern "C" int cm_fbank_wav(const cm_fbank_args *args) {
-    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_wav: args is NULL");
-    const cm_fbank_args &a = *args;
+// cm_fbank_wav (nsamp == NULL) and cm_fbank_wav_lens: one set of checks
+static int fbank_wav_entry(const cm_fbank_args &a, const int32_t *nsamp) {
     CM_REQUIRE(a.batch > 0 && a.frames > 0 && a.n_mels > 0 && a.wav && a.window && a.twiddle && a.db && a.umax_part && a.band_lo &&
                    a.band_hi && a.band_off && a.band_w, CM_EINVAL, "fbank_wav: bad sizes or NULL tensor");
     CM_REQUIRE(a.n_fft == NF && a.n_freq == NH + 1, CM_EUNSUPPORTED, "fbank_wav: n_fft %d unsupported (512 only)", a.n_fft);
@@ -346,9 +388,49 @@ extern "C" int cm_fbank_wav(const cm_fbank_args *args) {
     CM_REQUIRE(a.batch <= 65535 && a.n_mels <= 128, CM_EUNSUPPORTED, "fbank_wav: batch / n_mels too large");
     const size_t smem = (size_t)(NH + 1) * PWS * 4 + (size_t)(3 * a.n_mels + 1) * 4 + (size_t)BWCAP * 4 + (size_t)4 * ZN * 8 + 4;
     dim3 grid((a.frames + FT - 1) / FT, a.batch);
+    if (nsamp) {
+        fb_lens_args k{};
+        static_cast<cm_fbank_args &>(k) = a;
+        k.nsamp = nsamp;
+        hipLaunchKernelGGL((fbank_wav_kernel<false, fb_lens_args>), grid, dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), k,
+                           (float)(10.0 * log10((double)a.amin)));
+        return cm_launch_status("cm_fbank_wav_lens");
+    }
     hipLaunchKernelGGL((fbank_wav_kernel<false, cm_fbank_args>), grid, dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), a,
                        (float)(10.0 * log10((double)a.amin)));
     return cm_launch_status("cm_fbank_wav");
+}
+
+extern "C" int cm_fbank_wav(const cm_fbank_args *args) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_wav: args is NULL");
+    return fbank_wav_entry(*args, nullptr);
+}
+
+extern "C" int cm_fbank_wav_lens(const cm_fbank_args *args, const int32_t *n_samples) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_wav_lens: args is NULL");
+    CM_REQUIRE(n_samples != nullptr, CM_EINVAL, "fbank_wav_lens: n_samples is NULL (cm_fbank_wav is the form without lengths)");
+    CM_REQUIRE(cm_aligned(n_samples, 4), CM_EALIGN, "fbank_wav_lens: n_samples must be 4-byte aligned");
+    return fbank_wav_entry(*args, n_samples);
+}
+
+extern "C" int cm_fbank_finish_lens(const cm_fbank_args *args, const int32_t *n_samples) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_finish_lens: args is NULL");
+    CM_REQUIRE(n_samples != nullptr, CM_EINVAL, "fbank_finish_lens: n_samples is NULL (cm_fbank_finish is the form without lengths)");
+    CM_REQUIRE(cm_aligned(n_samples, 4), CM_EALIGN, "fbank_finish_lens: n_samples must be 4-byte aligned");
+    const cm_fbank_args &a = *args;
+    CM_REQUIRE(a.batch > 0 && a.frames > 0 && a.n_mels > 0 && a.db && a.umax && a.umax_part, CM_EINVAL, "fbank_finish_lens: bad sizes or NULL tensor (umax_part included)");
+    CM_REQUIRE(a.hop > 0 && a.samples > 0 && a.frames == 1 + a.samples / a.hop, CM_EINVAL, "fbank_finish_lens: frames must be 1 + samples / hop");
+    CM_REQUIRE(!a.mean || a.std, CM_EINVAL, "fbank_finish_lens: mean without std");
+    CM_REQUIRE(a.batch <= 65535, CM_EINVAL, "fbank_finish_lens: batch %d exceeds the grid limit", a.batch);
+    const int64_t per_utt = (int64_t)a.frames * a.n_mels;
+    int64_t chunks = (per_utt + 256 * 8 - 1) / (256 * 8);
+    if (chunks > 256) chunks = 256;
+    fb_lens_args k{};
+    static_cast<cm_fbank_args &>(k) = a;
+    k.nsamp = n_samples;
+    hipLaunchKernelGGL(fbank_finish_lens_kernel, dim3((unsigned)chunks, a.batch), dim3(256), 0, reinterpret_cast<hipStream_t>(a.stream), k,
+                       (a.frames + FT - 1) / FT);
+    return cm_launch_status("cm_fbank_finish_lens");
 }
 
 namespace {

@@ -403,7 +403,8 @@ int by_split(const cm_scan_cl_args &a, int ns) {
 
 }  // namespace
 
-int cm_scan_rows_fwd(const cm_scan_cl_args &a, const int32_t *lens);      // scan_rows_fwd.hip; lens: per-slot lengths or NULL
+int cm_scan_rows_fwd(const cm_scan_cl_args &a, const int32_t *lens, bool whole);   // scan_rows_fwd.hip; lens: per-slot lengths
+                                                                                    // (whole: per-utterance, every direction) or NULL
 
 #ifdef CM_ABLATE
 extern "C" int cm_debug_set(int v) { return g_debug.exchange(v); }
@@ -424,7 +425,7 @@ extern "C" int cm_scan_cl_fwd(const cm_scan_cl_args *args) {
         int with_rows = 0;
         for (int i = 0; i < a.ndir; ++i) with_rows += a.dir[i].xdbl != nullptr;
         CM_REQUIRE(with_rows == 0 || with_rows == a.ndir, CM_EINVAL, "scan_cl_fwd: xdbl must be set for every direction or none");
-        if (with_rows) return cm_scan_rows_fwd(a, nullptr);
+        if (with_rows) return cm_scan_rows_fwd(a, nullptr, false);
     }
     CM_REQUIRE(a.time_chunks <= 1, CM_EUNSUPPORTED, "scan_cl_fwd: time_chunks is built for the xdbl mode only");
     CM_REQUIRE(a.batch <= 65535, CM_EINVAL, "scan_cl_fwd: batch %d exceeds the grid limit", a.batch);
@@ -458,5 +459,19 @@ extern "C" int cm_scan_cl_fwd_slots(const cm_scan_cl_args *args, const int32_t *
     CM_REQUIRE(a.dstate == 16, CM_EUNSUPPORTED, "scan_cl_fwd_slots: dstate %d unsupported (16 only)", a.dstate);
     CM_REQUIRE(a.ndir == 1 || a.ndir == 2, CM_EINVAL, "scan_cl_fwd_slots: ndir must be 1 or 2");
     CM_REQUIRE(a.dir[0].xdbl != nullptr, CM_EUNSUPPORTED, "scan_cl_fwd_slots: built for the xdbl mode (the row-group kernel) only");
-    return cm_scan_rows_fwd(a, lens);
+    return cm_scan_rows_fwd(a, lens, false);
+}
+
+extern "C" int cm_scan_cl_fwd_lens(const cm_scan_cl_args *args, const int32_t *lens) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "scan_cl_fwd_lens: args is NULL");
+    CM_REQUIRE(lens != nullptr, CM_EINVAL, "scan_cl_fwd_lens: lens is NULL (cm_scan_cl_fwd is the form without lengths)");
+    CM_REQUIRE(cm_aligned(lens, 4), CM_EALIGN, "scan_cl_fwd_lens: lens must be 4-byte aligned");
+    const cm_scan_cl_args &a = *args;
+    CM_REQUIRE(a.batch > 0 && a.dim > 0 && a.seqlen > 0, CM_EINVAL, "scan_cl_fwd_lens: bad sizes batch=%d dim=%d seqlen=%d",
+               a.batch, a.dim, a.seqlen);
+    CM_REQUIRE(a.dstate == 16, CM_EUNSUPPORTED, "scan_cl_fwd_lens: dstate %d unsupported (16 only)", a.dstate);
+    CM_REQUIRE(a.ndir == 1 || a.ndir == 2, CM_EINVAL, "scan_cl_fwd_lens: ndir must be 1 or 2");
+    for (int i = 0; i < a.ndir; ++i)
+        CM_REQUIRE(a.dir[i].xdbl != nullptr, CM_EUNSUPPORTED, "scan_cl_fwd_lens: built for the xdbl mode (the row-group kernel) only");
+    return cm_scan_rows_fwd(a, lens, true);
 }

@@ -426,6 +426,30 @@ __global__ __launch_bounds__(256, sizeof(IO) == 2 ? 4 : 3) void scan_rows_slots_
     else scan_rows<IO, false, false, 0, DTR, false>(p, d, lds, cx, b, 0, T, h0, h_last, decay);
 }
 
+// Whole utterances of different lengths (cm_scan_cl_fwd_lens; single pass, one or two directions, no carried state): every direction
+// of sequence b runs steps [0, T), T = lens[b] clamped to [0, seqlen], from a zero state.  REV starts at block (ceil(T / 16) - 1) and
+// step T - 1 -- scan_rows places its blocks by T -- so both directions walk the 16-step blocks of a launch with seqlen = T, and the
+// descriptors cut at T rows keep every load and store inside the utterance's own rows.  T == 0 returns before any descriptor is formed.
+template <typename IO, int DTR>
+__global__ __launch_bounds__(256, sizeof(IO) == 2 ? 4 : 3) void scan_rows_lens_kernel(const cm_scan_cl_args p, const rows_slot_plan pl) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[rows_lds<IO>::kBytes];
+    const int total = gridDim.x, nx = pl.nx;
+    int id = blockIdx.x;
+    if ((total & 7) == 0) id = (id & 7) * (total >> 3) + (id >> 3);
+    const int cx = id % nx, b = (id / nx) % p.batch, z = id / (nx * p.batch);
+    const cm_scan_cl_dir &d = p.dir[z];
+    const int T = min(max(pl.lens[b], 0), p.seqlen);
+    if (T == 0) return;
+    const bool full = p.z != nullptr && p.delta_softplus != 0;
+    if (full) {
+        if (d.reverse_time) scan_rows<IO, true, true, 0, DTR, false>(p, d, lds, cx, b, 0, T, nullptr, nullptr, nullptr);
+        else scan_rows<IO, false, true, 0, DTR, false>(p, d, lds, cx, b, 0, T, nullptr, nullptr, nullptr);
+    } else {
+        if (d.reverse_time) scan_rows<IO, true, false, 0, DTR, false>(p, d, lds, cx, b, 0, T, nullptr, nullptr, nullptr);
+        else scan_rows<IO, false, false, 0, DTR, false>(p, d, lds, cx, b, 0, T, nullptr, nullptr, nullptr);
+    }
+}
+
 // Entry state of every chunk from the chunk summaries, in scan order; the caller's h0 enters the first chunk, the caller's
 // h_last / decay (whole-sequence values) leave the last.  One thread per (direction, sequence, channel, 4 states).
 __global__ __launch_bounds__(256) void rows_carry_kernel(const cm_scan_cl_args p, const rows_plan pl) {
@@ -474,7 +498,7 @@ int cm_scan_rows_fwd2(const cm_scan_cl_args &a);        // scan_rows_fwd2.hip: 2
 namespace {
 
 template <typename IO>
-int launch_rows(const cm_scan_cl_args &a, const int32_t *lens) {
+int launch_rows(const cm_scan_cl_args &a, const int32_t *lens, const bool whole) {
     rows_plan pl{};
     pl.nx = (a.dim + 63) / 64;
     pl.chunks = 1;
@@ -495,6 +519,21 @@ int launch_rows(const cm_scan_cl_args &a, const int32_t *lens) {
         return launch_rows_chunked<IO, 16>(a, pl);
     }
     const long total = (long)pl.nx * a.batch * a.ndir;
+    if (lens && whole) {                                    // whole utterances of their own lengths: every direction, zero entry state
+        rows_slot_plan sp{};
+        static_cast<rows_plan &>(sp) = pl;
+        sp.lens = lens;
+        const dim3 sgrid((unsigned)total), sblock(256);
+        hipStream_t sst = reinterpret_cast<hipStream_t>(a.stream);
+        if constexpr (sizeof(IO) == 2) {
+            if (a.dir[0].dt_rank > 16) {
+                hipLaunchKernelGGL((scan_rows_lens_kernel<IO, 32>), sgrid, sblock, 0, sst, a, sp);
+                return cm_launch_status("cm_scan_cl_fwd_lens(rows, dt_rank 32)");
+            }
+        }
+        hipLaunchKernelGGL((scan_rows_lens_kernel<IO, 16>), sgrid, sblock, 0, sst, a, sp);
+        return cm_launch_status("cm_scan_cl_fwd_lens(rows)");
+    }
     if (lens) {                                             // per-slot lengths: the 4-states-per-lane kernel, unchunked (checked at entry)
         rows_slot_plan sp{};
         static_cast<rows_plan &>(sp) = pl;
@@ -560,15 +599,23 @@ extern "C" int32_t cm_scan_cl_fwd_auto_chunks(int32_t batch, int32_t seqlen, int
     return c < 2 ? 1 : (int32_t)c;
 }
 
-// called by cm_scan_cl_fwd (scan_cl_fwd.hip) when every direction carries xdbl, and by cm_scan_cl_fwd_slots with lens
-int cm_scan_rows_fwd(const cm_scan_cl_args &a, const int32_t *lens) {
+// called by cm_scan_cl_fwd (scan_cl_fwd.hip) when every direction carries xdbl, by cm_scan_cl_fwd_slots with lens, and by
+// cm_scan_cl_fwd_lens with lens and whole = true
+int cm_scan_rows_fwd(const cm_scan_cl_args &a, const int32_t *lens, bool whole) {
     const int vec = a.io_dtype == CM_BF16 ? 8 : 4;
     CM_REQUIRE(a.io_dtype == CM_BF16 || a.io_dtype == CM_F32, CM_EUNSUPPORTED, "scan_cl_fwd(xdbl): io dtype %d unsupported", a.io_dtype);
     CM_REQUIRE(a.dim % vec == 0, CM_EUNSUPPORTED, "scan_cl_fwd(xdbl): dim %d must be a multiple of %d", a.dim, vec);
     CM_REQUIRE(!a.z || (cm_aligned(a.z, 16) && a.z_bs % vec == 0 && a.z_ts % vec == 0), CM_EALIGN,
                "scan_cl_fwd(xdbl): z must be 16-byte aligned with strides that are multiples of %d", vec);
     CM_REQUIRE(a.time_chunks >= 0 && a.time_chunks <= 4096, CM_EINVAL, "scan_cl_fwd(xdbl): time_chunks %d out of range", a.time_chunks);
-    if (lens) {
+    if (lens && whole) {
+        CM_REQUIRE(a.time_chunks <= 1, CM_EUNSUPPORTED, "scan_cl_fwd_lens: per-utterance lengths with time_chunks %d: the unchunked launch only", a.time_chunks);
+        CM_REQUIRE(a.lanes_per_channel == 0 || a.lanes_per_channel == 4, CM_EUNSUPPORTED, "scan_cl_fwd_lens: lanes_per_channel %d (0 or 4)", a.lanes_per_channel);
+        for (int i = 0; i < a.ndir; ++i)
+            CM_REQUIRE(!a.dir[i].ckpt && !a.dir[i].ypre && !a.dir[i].h0 && !a.dir[i].h_last && !a.dir[i].decay, CM_EUNSUPPORTED,
+                       "scan_cl_fwd_lens: dir %d: no training checkpoints, no carried state (ckpt / ypre / h0 / h_last / decay)", i);
+        CM_REQUIRE(cm_aligned(lens, 4), CM_EALIGN, "scan_cl_fwd_lens: lens must be 4-byte aligned");
+    } else if (lens) {
         CM_REQUIRE(a.time_chunks <= 1, CM_EUNSUPPORTED, "scan_cl_fwd_slots: per-slot lengths with time_chunks %d: the unchunked launch only", a.time_chunks);
         CM_REQUIRE(a.ndir == 1, CM_EUNSUPPORTED, "scan_cl_fwd_slots: per-slot lengths with two directions are not built");
         CM_REQUIRE(a.lanes_per_channel == 0 || a.lanes_per_channel == 4, CM_EUNSUPPORTED, "scan_cl_fwd_slots: lanes_per_channel %d (0 or 4)", a.lanes_per_channel);
@@ -594,5 +641,5 @@ int cm_scan_rows_fwd(const cm_scan_cl_args &a, const int32_t *lens) {
                        d.xdbl_bs % vec == 0 && d.xdbl_ts % vec == 0 && cm_aligned(d.A, 16) && cm_aligned(d.dt_weight, 16),
                    CM_EALIGN, "scan_cl_fwd(xdbl): dir %d: u / xdbl / A / dt_weight must be 16-byte aligned, strides multiples of %d", i, vec);
     }
-    return a.io_dtype == CM_BF16 ? launch_rows<cm_bf16>(a, lens) : launch_rows<float>(a, lens);
+    return a.io_dtype == CM_BF16 ? launch_rows<cm_bf16>(a, lens, whole) : launch_rows<float>(a, lens, whole);
 }

@@ -80,7 +80,8 @@ def _join(a: str, b: str) -> str:
 class CTCBeamSearcher:
     """CTC beam search without a language model, on the GPU (constructor keywords of speechbrain's CTCBeamSearcher).
 
-    __call__(log_probs (batch, T, V) on the GPU, wav_lens (batch) relative lengths or None) -> List[List[CTCHypothesis]]
+    __call__(log_probs (batch, T, V) on the GPU, wav_lens (batch) relative lengths or None, lengths=None: absolute frame counts,
+    which win when given) -> List[List[CTCHypothesis]]
     with at most topk hypotheses per utterance, best first.  There is no host implementation: CPU tensors raise."""
 
     def __init__(self, blank_index: int, vocab_list: Sequence[str], space_token: str = " ", spm_token: str = "▁",
@@ -147,13 +148,21 @@ class CTCBeamSearcher:
             return [steps] * batch
         return [min(max(int(round(rel * steps)), 0), steps) for rel in wav_lens.detach().cpu().tolist()]
 
-    def __call__(self, log_probs: torch.Tensor, wav_lens: Optional[torch.Tensor] = None) -> List[List[CTCHypothesis]]:
+    def __call__(self, log_probs: torch.Tensor, wav_lens: Optional[torch.Tensor] = None, lengths=None) -> List[List[CTCHypothesis]]:
+        """``lengths``: absolute frame counts per utterance (a host sequence of ints, e.g. the fused.RowLens of
+        ConMambaASR.encode(..., ragged=True)); it wins over ``wav_lens``, whose round(rel * T) can miss an utterance's own row count
+        by one."""
         if not log_probs.is_cuda:
             raise RuntimeError("CTCBeamSearcher runs on the GPU only (got a CPU tensor): move log_probs to the GPU")
         if log_probs.dim() != 3 or log_probs.shape[2] != len(self.vocab_list):
             raise ValueError(f"CTCBeamSearcher: log_probs must be (batch, T, {len(self.vocab_list)}), got {tuple(log_probs.shape)}")
         b, steps, _ = log_probs.shape
-        counts = self.frame_counts(steps, wav_lens, b)
+        if lengths is None:
+            counts = self.frame_counts(steps, wav_lens, b)
+        else:
+            counts = [int(x) for x in lengths]
+            if len(counts) != b or any(not 0 <= x <= steps for x in counts):
+                raise ValueError(f"CTCBeamSearcher: lengths must be {b} frame counts in [0, {steps}], got {counts}")
         if steps == 0:
             return [[CTCHypothesis("", None, 0.0, 0.0, None)] for _ in range(b)]
         lengths = torch.tensor(counts, dtype=torch.int32).to(log_probs.device)

@@ -263,7 +263,8 @@ def _conv(c: _LayerCache, xz, ucat, xdbl=None, xproj=True, hist=None, lens=None)
     """Both directions' causal conv + SiLU of xz's x half (batch, seqlen, 2E views) into ucat = [u_fwd | u_bwd].  With
     cm_conv_xproj the same kernel forms x_proj's rows (into ``xdbl`` when given) and they are returned, else None.
     The unidirectional mixer: one direction into ucat (E wide); ``hist`` = (x_hist, x_hist_out) of cm_conv_xproj_uni, the
-    native streaming route's carry, ``lens`` its per-slot row counts (cm_conv_xproj_uni_slots)."""
+    native streaming route's carry, ``lens`` its per-slot row counts (cm_conv_xproj_uni_slots).  ``lens`` with the bidirectional mixer:
+    the utterances' own row counts (cm_conv_xproj_lens; the ragged whole-utterance route)."""
     E = c.d_inner
     if c.uni:
         w0 = (c.dirs[0]["conv_w"], c.dirs[0]["conv_b"])
@@ -275,7 +276,8 @@ def _conv(c: _LayerCache, xz, ucat, xdbl=None, xproj=True, hist=None, lens=None)
         return None
     w = (c.dirs[0]["conv_w"], c.dirs[0]["conv_b"], c.dirs[1]["conv_w"], c.dirs[1]["conv_b"])
     if xproj and _conv_forms_xdbl(c):
-        return ops.conv_xproj(xz[:, :, :E], *w, c.wx_packed[0], c.wx_packed[1], out_f=ucat[:, :, :E], out_b=ucat[:, :, E:], xdbl=xdbl)
+        return ops.conv_xproj(xz[:, :, :E], *w, c.wx_packed[0], c.wx_packed[1], out_f=ucat[:, :, :E], out_b=ucat[:, :, E:], xdbl=xdbl, lens=lens)
+    assert lens is None
     ops.conv_cl_fwd(xz[:, :, :E], *w, True, out_f=ucat[:, :, :E], out_b=ucat[:, :, E:])
     return None
 
@@ -284,8 +286,12 @@ def _scan(c: _LayerCache, xz, ucat, ycat, xdbl, batch, seqlen, state=None, lens=
     """Both directions' selective scan of ucat, gated by xz's z half, into ycat (all (batch, seqlen, 2E)): one launch.
     ``state`` (batch, E, 16) fp32, streaming: the unidirectional scan starts from it and leaves its last state there (each workgroup
     reads its channels' entry state before it writes them), unchunked -- the recurrence then visits the same values in the same
-    order as over the whole sequence.  ``lens`` (with ``state``): per-slot step counts (cm_scan_cl_fwd_slots)."""
+    order as over the whole sequence.  ``lens`` (with ``state``): per-slot step counts (cm_scan_cl_fwd_slots).  ``lens`` without
+    ``state``: the utterances' own step counts, every direction, unchunked (cm_scan_cl_fwd_lens; the ragged whole-utterance route)."""
     dirs = _scan_dirs(c, ucat, ycat, batch, seqlen, xdbl)
+    if state is None and lens is not None:
+        ops.scan_cl_fwd(dirs, z=xz[:, :, c.d_inner:], delta_softplus=True, time_chunks=1, lens=lens, whole=True)
+        return
     if state is None:
         ops.scan_cl_fwd(dirs, z=xz[:, :, c.d_inner:], delta_softplus=True)
         return
@@ -349,16 +355,17 @@ def _ffn2(c: _LayerCache, x, addend, final_ln=None, f2=None):
 def _tail(c: _LayerCache, x, ycat, batch, seqlen, final_ln=None, small=False, hist=None, lens=None):
     """A layer behind the scan, on the rows of whole utterances: x (rows, D) fp32 += out_proj(ycat (rows, 2E)); the
     convolution module; FFN2 + norm2 (-> _ffn2).  ``hist`` = (hist, hist_out) of cm_glu_dwconv_ln_gelu_causal, the native
-    streaming route's carry, ``lens`` its per-slot row counts (cm_glu_dwconv_ln_gelu_causal_slots)."""
+    streaming route's carry, ``lens`` its per-slot row counts (cm_glu_dwconv_ln_gelu_causal_slots).  ``lens`` without ``hist``: the
+    utterances' own row counts under the 'same' padding (cm_glu_dwconv_ln_gelu_lens; the ragged whole-utterance route)."""
     D = x.shape[-1]
     dw = (c.dw_w, c.dw_b, c.cm_ln2[0], c.cm_ln2[1], c.cm_ln2[2])
-    kw = dict(causal=True, hist=hist[0], hist_out=hist[1], lens=lens) if hist is not None else dict(causal=c.causal)
+    kw = dict(causal=True, hist=hist[0], hist_out=hist[1], lens=lens) if hist is not None else dict(causal=c.causal, lens=lens)
     if USE_LN_PW_GLU and c.pw_packed is not None:
         # x += mamba ; conv-module LN ; pointwise conv ; GLU -- one kernel, the 2D-wide tensor never exists
         gl = mixer_tail(c, x, ycat)
         g = ops.glu_dwconv_ln_gelu(gl.view(batch, seqlen, D), *dw, weight_t=c.dw_wt, glu_done=True, lin_w=c.lin_packed, lin_b=c.lin_bf, **kw)
     else:
-        assert hist is None and lens is None                     # the carried rows are the gated ones
+        assert hist is None                                      # the carried rows are the gated ones
         _, h = ops.add_layernorm(x, _out_proj(c, ycat), 1.0, x_out=x, norm2=c.cm_ln, out_dtype=c.dtype)   # x += mamba ; conv-module LN
         pw = torch.addmm(c.pw_b, h, c.pw_w.t()).view(batch, seqlen, 2 * D)
         g = ops.glu_dwconv_ln_gelu(pw, *dw, weight_t=c.dw_wt, lin_w=c.lin_packed, lin_b=c.lin_bf, **kw)
@@ -458,7 +465,14 @@ def _residual_rows(src):
     return x.clone() if x.data_ptr() == src.data_ptr() else x
 
 
-def _encoder_forward_joined(encoder, src, dtype, ns, paired=False):
+def _ragged_native(caches, dtype) -> bool:
+    """The ragged whole-utterance route runs on the kernels that take lengths: bf16, every layer bidirectional and all_native with
+    cm_conv_xproj forming x_proj's rows (d_model 256, and 144 with its library GEMMs in the row-local places)."""
+    return (USE_FUSED_FFN and USE_LN_PW_GLU and dtype == torch.bfloat16 and bool(caches)
+            and all(c.all_native and _conv_forms_xdbl(c) and not c.uni and not c.causal and c.kernel_size == 31 for c in caches))
+
+
+def _encoder_forward_joined(encoder, src, dtype, ns, paired=False, lens=None):
     """The encoder with both feed-forward modules on cm_ffn_fused, every layer as _head, _scan, _tail, the batch as ``ns``
     parts.  One part: the three pieces on the whole batch.  Several: the parts run on ``ns`` HIP streams for everything
     EXCEPT the selective scan, which runs once per layer on the whole batch between a join and a fork: the kernels whose
@@ -468,10 +482,15 @@ def _encoder_forward_joined(encoder, src, dtype, ns, paired=False):
 
     ``paired`` (CM_STREAM_MODE=pair): the scan runs PER PART, and a part's scan waits for the end of the scan launched before
     it -- at most one scan is on the chip at any time, always beside the other parts' feed-forward / row kernels (VERDICT r2
-    item 4: the vector-issue-bound scan leaves 80 % of HBM and the matrix pipe idle)."""
+    item 4: the vector-issue-bound scan leaves 80 % of HBM and the matrix pipe idle).
+
+    ``lens`` (device int32 (batch,)): utterance b has lens[b] rows.  The three kernels of a layer that mix time take each
+    part's slice of it, the joined scan the whole tensor, unchunked; None is returned unless _ragged_native holds."""
     batch, seqlen, D = src.shape
     caches = [_cache(layer, dtype) for layer in encoder.layers]
     if not (USE_FUSED_FFN and caches and all(c.ffn_native for c in caches)):
+        return None
+    if lens is not None and not _ragged_native(caches, dtype):
         return None
     if ns > 1 and not (USE_CONV_XPROJ and USE_SCAN_ROWS and USE_LN_PW_GLU and all(c.all_native and not c.uni for c in caches)):
         return None
@@ -483,6 +502,10 @@ def _encoder_forward_joined(encoder, src, dtype, ns, paired=False):
     # CM_FFN_SMALL_ROWS is about the unsplit launch: parts share the chip with each other's kernels
     small = len(parts) == 1 and 0 < batch * seqlen <= ops.SMALL_FFN_ROWS
     fin = _final_norm(encoder)
+    # lens is checked once per tensor a launch takes: the whole one (the joined scan) and each part's slice
+    sl = None if lens is None else ops.slot_lens(lens, batch, dev, "encoder_forward")
+    psl = [None if lens is None else (sl if (b0, b1) == (0, batch) else ops.slot_lens(lens[b0:b1], b1 - b0, dev, "encoder_forward"))
+           for b0, b1 in parts]
     with torch.autocast("cuda", enabled=False):
         x = _residual_rows(src)
         nd = len(caches[0].dirs)
@@ -505,36 +528,70 @@ def _encoder_forward_joined(encoder, src, dtype, ns, paired=False):
         fork()
         gate = None                                                                 # pair mode: end of the scan launched last
         for li, c in enumerate(caches):
-            for st, (b0, b1) in zip(streams, parts):
+            for st, (b0, b1), pl in zip(streams, parts, psl):
                 with torch.cuda.stream(st):
-                    _head(c, rows(x3, b0, b1), xz[b0:b1], ucat[b0:b1], None if xdbl is None else xdbl[b0:b1], small)
+                    _head(c, rows(x3, b0, b1), xz[b0:b1], ucat[b0:b1], None if xdbl is None else xdbl[b0:b1], small, lens=pl)
             if paired:
-                for st, (b0, b1) in zip(streams, parts):
+                for st, (b0, b1), pl in zip(streams, parts, psl):
                     with torch.cuda.stream(st):
                         if gate is not None:
                             st.wait_event(gate)
-                        _scan(c, xz[b0:b1], ucat[b0:b1], ycat[b0:b1], xdbl[b0:b1], b1 - b0, seqlen)
+                        _scan(c, xz[b0:b1], ucat[b0:b1], ycat[b0:b1], xdbl[b0:b1], b1 - b0, seqlen, lens=pl)
                         gate = torch.cuda.Event()
                         gate.record(st)
             else:
                 join()
-                _scan(c, xz, ucat, ycat, xdbl, batch, seqlen)
+                _scan(c, xz, ucat, ycat, xdbl, batch, seqlen, lens=sl)
                 fork()
             for pi, (st, (b0, b1)) in enumerate(zip(streams, parts)):
                 with torch.cuda.stream(st):
                     outs[pi] = _tail(c, rows(x3, b0, b1), rows(ycat, b0, b1), b1 - b0, seqlen,
-                                     fin if li == len(caches) - 1 else None, small)
+                                     fin if li == len(caches) - 1 else None, small, lens=psl[pi])
         join()
         for o in outs[1:]:
             o.record_stream(cur)
         return (outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)).view(batch, seqlen, D)
 
 
+def _encoder_forward_ragged(encoder, src, dtype, streams, lens):
+    """encoder_forward with per-utterance row counts: the joined native route with ``lens`` in its three time-mixing kernels, or each
+    utterance alone on its own rows."""
+    batch, seqlen, D = src.shape
+    ops.slot_lens(lens, batch, src.device, "encoder_forward")
+    ns = min(N_STREAMS, max(1, batch // 16)) if streams is None else streams
+    if not (ns > 1 and batch >= 2 * 8):
+        ns = 1
+    caches = [_cache(layer, dtype) for layer in encoder.layers]
+    if _ragged_native(caches, dtype):
+        # several parts: the joined route, or the per-part scans of "pair"; "free" falls out of slicing -- independent parts are one part each
+        if ns > 1 and STREAM_MODE not in ("join", "pair"):
+            ns = 1
+        out = _encoder_forward_joined(encoder, src, dtype, ns, paired=ns > 1 and STREAM_MODE == "pair", lens=lens)
+        if out is not None:
+            return out
+    out = torch.zeros((batch, seqlen, D), dtype=torch.float32, device=src.device)
+    for b, n in enumerate(lens.clamp(0, seqlen).tolist()):       # the one host read of the fallback
+        if n > 0:
+            out[b, :n] = encoder_forward(encoder, src[b:b + 1, :n], dtype, streams=1)[0]
+    return out
+
+
 @torch.no_grad()
-def encoder_forward(encoder, src, dtype: Optional[torch.dtype] = None, streams: Optional[int] = None):
-    """ConmambaEncoder.forward (eval, no grad) through the fused path: src (B, T, D) -> (B, T, D) fp32."""
+def encoder_forward(encoder, src, dtype: Optional[torch.dtype] = None, streams: Optional[int] = None, lens=None):
+    """ConmambaEncoder.forward (eval, no grad) through the fused path: src (B, T, D) -> (B, T, D) fp32.
+
+    ``lens``: an int32 (B,) tensor on src's device, utterance b has lens[b] rows (clamped to [0, T] on the device).  Its
+    output rows [0, lens[b]) are those of this function on src[b:b+1, :lens[b]] alone; rows at and past lens[b] are unspecified, and
+    what src holds there (NaN included) reaches no valid row of any utterance.  On the native route (bf16, every layer bidirectional
+    and all_native with cm_conv_xproj: d_model 256, and 144) the lengths are read on the device only, so a fixed (B, T) call can be
+    captured in a hipGraph and replayed with other lengths; the selective scan is unchunked under ``lens``, as in the per-slot
+    streaming route (bit-equal to a solo run whose scan is unchunked too: CM_SCAN_CHUNKS=1).  Any other configuration (fp32,
+    CM_*=0 switches, other layers) reads ``lens`` on the host, encodes each utterance alone on its own rows and scatters the results:
+    the same semantics, slowly.  ``lens=None`` is the call without lengths, launch for launch."""
     if dtype is None:
         dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.float32
+    if lens is not None:
+        return _encoder_forward_ragged(encoder, src, dtype, streams, lens)
     # parts of at least 16 utterances (measured, join mode: 16 utterances 12.1 M frames/s as one part vs 10.6 M as four;
     # 32: 15.1 / 15.3 / 15.2 M with 1 / 2 / 4; 64: 16.6 / 17.0 / 17.7 M); an explicit ``streams`` argument is taken as is
     ns = min(N_STREAMS, max(1, src.shape[0] // 16)) if streams is None else streams
@@ -698,15 +755,91 @@ def _frontend_cache(model, dtype):
     return _FRONTEND.lookup(model, _params_key(dtype, model.CNN, model.Transformer.custom_src_module), dtype)
 
 
+def ragged_sample_counts(wav_lens, n_total: int, hop: int):
+    """Per-utterance sample counts of a padded (B, n_total) batch, on the host: relative lengths (a floating tensor, speechbrain's
+    wav_lens) become round(rel * n_total), absolute counts (an integer tensor or a sequence of ints) are taken as they are; one
+    .tolist().  An utterance outside [0, n_total] or under the front end's minimum of 5 frames (4 * hop samples) raises ValueError."""
+    if isinstance(wav_lens, torch.Tensor):
+        vals = wav_lens.detach().tolist()
+        counts = [int(round(v * n_total)) for v in vals] if wav_lens.is_floating_point() else [int(v) for v in vals]
+    else:
+        counts = [int(v) for v in wav_lens]
+    for b, n in enumerate(counts):
+        if not 0 <= n <= n_total:
+            raise ValueError(f"ragged batch: utterance {b} has {n} samples, outside [0, {n_total}]")
+        if 1 + n // hop < 5:
+            raise ValueError(f"ragged batch: utterance {b} has {n} samples = {1 + n // hop} frames; the front end needs at least 5 "
+                             f"frames ({4 * hop} samples)")
+    return counts
+
+
+def frontend_ragged_native(model, wavs, dtype) -> bool:
+    """The ragged front end runs on cm_fbank_wav_lens / cm_fbank_finish_lens / cm_cnn_front_lens: GPU, bf16, n_fft 512, the recipes' CNN."""
+    from . import sb_compat
+    fb, b0 = model.compute_features, model.CNN.blocks[0]
+    return (wavs.is_cuda and dtype == torch.bfloat16 and USE_CNN_FRONT and sb_compat.USE_FBANK_WAV and ops.fbank_wav_supported(fb.n_fft, fb.hop, fb.n_mels)
+            and fb.n_mels == 80 and tuple(b0.conv.weight.shape) == (64, 1, 3, 3) and b0.norm.norm.weight.numel() == 40 * 64
+            and tuple(model.CNN.blocks[1].conv.weight.shape) == (32, 64, 3, 3))
+
+
 @torch.no_grad()
-def asr_encode(model, wavs, wav_lens, dtype: Optional[torch.dtype] = None):
+def frontend_ragged(model, wavs, n_samples, dtype=torch.bfloat16):
+    """The whole-utterance front end on a padded batch whose utterance b has n_samples[b] samples (host ints, checked by
+    ragged_sample_counts): -> (rows (B, T2_max, 640) bf16, row_lens, frames) with row_lens a RowLens of frontend_rows_total(n_samples[b],
+    hop) and frames the device int32 (B,) frame counts.  Rows [0, row_lens[b]) are those of the front end on wavs[b:b+1, :n_samples[b]]
+    alone; rows past them are unspecified.  Three device arrays (samples, frames, rows) are built once; the kernels read them."""
+    fb, hop = model.compute_features, model.compute_features.hop
+    frames = [1 + n // hop for n in n_samples]
+    rows = [frontend_rows_total(n, hop) for n in n_samples]
+    counts = torch.tensor([list(n_samples), frames, rows], dtype=torch.int32).to(wavs.device)
+    with torch.autocast("cuda", enabled=False):
+        feats = ops.fbank_from_wav(wavs, fb.window, fb.n_fft, hop, fb.fbank, fb.amin, fb.top_db, model.normalize.glob_mean,
+                                   model.normalize.glob_std, lens=counts[0])
+        c = _frontend_cache(model, dtype)
+        b0 = model.CNN.blocks[0]
+        n0 = b0.norm.norm
+        src = ops.cnn_front(feats, b0.conv.weight, b0.conv.bias, n0.weight, n0.bias, n0.eps,
+                            c["w2_ohwi"], c["b2f"], c["ln2"][0], c["ln2"][1], c["ln2"][2], 0.01, lens=counts[1])
+    return src, RowLens(rows, counts[2]), counts[1]
+
+
+def _asr_encode_ragged(model, wavs, n_samples, dtype):
+    """asr_encode on a padded batch with per-utterance sample counts -> (enc (B, T2_max, d_model) fp32, row_lens)."""
+    batch = wavs.shape[0]
+    if frontend_ragged_native(model, wavs, dtype):
+        src, row_lens, _ = frontend_ragged(model, wavs, n_samples, dtype)
+        c = _frontend_cache(model, dtype)
+        t2 = src.shape[1]
+        with torch.autocast("cuda", enabled=False):
+            x = torch.addmm(c["lin_b"], src.view(batch * t2, -1), c["lin_w"].t())           # row-local: a row past an utterance's own stays there
+        return encoder_forward(model.Transformer.encoder, x.view(batch, t2, -1), dtype, lens=row_lens.dev), row_lens
+    # any other configuration: each utterance alone through the route without lengths, scattered
+    hop = model.compute_features.hop
+    rows = [frontend_rows_total(n, hop) for n in n_samples]
+    out = None
+    for b, n in enumerate(n_samples):
+        e = asr_encode(model, wavs[b:b + 1, :n], None, dtype)
+        if out is None:
+            out = torch.zeros((batch, max(rows), e.shape[-1]), dtype=e.dtype, device=e.device)
+        out[b, :rows[b]] = e[0]
+    return out, RowLens(rows, torch.tensor(rows, dtype=torch.int32).to(wavs.device))
+
+
+@torch.no_grad()
+def asr_encode(model, wavs, wav_lens, dtype: Optional[torch.dtype] = None, n_samples=None):
     """ConMambaASR.encode in eval mode through native kernels: Fbank (torch.stft/rocFFT + mel GEMM) -> global
     normalisation -> the two CNN blocks -> src Linear -> fused encoder.  The CNN blocks (conv + LayerNorm + LeakyReLU
     each) run as cm_cnn_front, both in one kernel (bf16, the recipes' shapes); else cm_cnn_block1 (the next block's
     reflect border included) + cm_cnn_block2 (bf16); else cm_cnn_block1 + library conv (64->32, 3x3, stride 2,
-    channels-last, unpadded) + cm_add_layernorm (LN + LeakyReLU).  Returns (batch, ceil(T/4), d_model) fp32."""
+    channels-last, unpadded) + cm_add_layernorm (LN + LeakyReLU).  Returns (batch, ceil(T/4), d_model) fp32.
+
+    ``n_samples``: per-utterance sample counts as host ints (ragged_sample_counts) -> (enc, row_lens): utterance b's rows
+    [0, row_lens[b]) are those of this function on wavs[b:b+1, :n_samples[b]] alone, row_lens a RowLens.  ``wav_lens`` itself is not
+    read on either path (the reference computes a padding mask from it and discards it)."""
     if dtype is None:
         dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.float32
+    if n_samples is not None:
+        return _asr_encode_ragged(model, wavs, list(n_samples), dtype)
     with torch.autocast("cuda", enabled=False):
         # Fbank back end + frozen global normalisation in the native kernels (cm_fbank_mel_db / cm_fbank_finish)
         feats = model.compute_features(wavs, norm=(model.normalize.glob_mean, model.normalize.glob_std))

@@ -509,11 +509,13 @@ def _scan_cl_dir_rows(x, dd, u0, z, keep):
 SCAN_CHUNKS = os.environ.get("CM_SCAN_CHUNKS", "auto")
 
 
-def scan_cl_fwd(directions, z=None, delta_softplus=True, time_chunks=None, split: int = 0, lens=None):
+def scan_cl_fwd(directions, z=None, delta_softplus=True, time_chunks=None, split: int = 0, lens=None, whole: bool = False):
     """Channels-last selective scan, 1 or 2 directions in one launch (cm_scan_cl_fwd).
     ``time_chunks`` (xdbl mode): None = the CM_SCAN_CHUNKS policy, else the chunk count.
     ``lens`` (cm_scan_cl_fwd_slots; xdbl mode, one direction, unchunked): int32 (batch,) device tensor, sequence b runs its first
-    lens[b] steps only (h_last = h0 for 0); ``out`` rows at and past lens[b] are not written.
+    lens[b] steps only (h_last = h0 for 0); ``out`` rows at and past lens[b] are not written.  With two directions, or
+    ``whole=True`` (cm_scan_cl_fwd_lens; xdbl mode, unchunked, no carried state): sequence b is a whole utterance of lens[b] steps --
+    the reverse direction starts from a zero state at step lens[b] - 1.
 
     ``directions``: list of dicts with u, delta (batch, seqlen, dim), A (dim, 16), B, C (16, batch, seqlen) fp32
     time-contiguous (see alloc_bc), D, delta_bias (dim) or None, out (batch, seqlen, dim) view or None, reverse.
@@ -584,6 +586,10 @@ def scan_cl_fwd(directions, z=None, delta_softplus=True, time_chunks=None, split
             a.workspace, a.workspace_bytes = _ptr(ws), nbytes
     elif time_chunks not in (None, 0, 1):
         raise RuntimeError("time_chunks needs the xdbl mode")
+    if lens is not None and (whole or len(directions) == 2):
+        lp, fn = _slot_lens(lens, b, u0.device, "scan_cl_fwd"), N.lib().cm_scan_cl_fwd_lens
+        _launch("cm_scan_cl_fwd_lens", lambda ref: fn(ref, lp), a, units=b * l * len(directions))
+        return outs
     if lens is not None:
         lp, fn = _slot_lens(lens, b, u0.device, "scan_cl_fwd"), N.lib().cm_scan_cl_fwd_slots
         _launch("cm_scan_cl_fwd_slots", lambda ref: fn(ref, lp), a, units=b * l)
@@ -1249,10 +1255,12 @@ def scan_cl_bwd(directions, z, time_chunks=0, da_log=False):
     return outs
 
 
-def conv_xproj(x, weight_f, bias_f, weight_b, bias_b, wx_f, wx_b, out_f, out_b, xdbl=None, variant: int = 0):
+def conv_xproj(x, weight_f, bias_f, weight_b, bias_b, wx_f, wx_b, out_f, out_b, xdbl=None, variant: int = 0, lens=None):
     """Both directions' depthwise conv + SiLU and x_proj GEMMs in one kernel (cm_conv_xproj, bf16).
     x (batch, seqlen, dim) view; conv weights (dim, 4) fp32; wx_f / wx_b PackedWeight of the (P + 32, dim) re-rowed x_proj
     weights [dt P | B | C], P = 16, or 32 for 16 < dt_rank <= 32; out_f / out_b (batch, seqlen, dim) views.
+    ``lens`` (cm_conv_xproj_lens): int32 (batch,) device tensor, utterance b has lens[b] rows -- the backward direction's taps past
+    them read the conv's zero padding; rows at and past lens[b] of the three outputs are not written.
     Returns xdbl (batch, seqlen, 2 * (P + 32)) bf16."""
     _dev_check(x, weight_f, bias_f, weight_b, bias_b, out_f, out_b)
     _rows_ok(x, "x"), _rows_ok(out_f, "out_f"), _rows_ok(out_b, "out_b")
@@ -1274,6 +1282,10 @@ def conv_xproj(x, weight_f, bias_f, weight_b, bias_b, wx_f, wx_b, out_f, out_b, 
     a.x_bs, a.x_ts, a.yf_bs, a.yf_ts = x.stride(0), x.stride(1), out_f.stride(0), out_f.stride(1)
     a.yb_bs, a.yb_ts, a.xdbl_bs, a.xdbl_ts = out_b.stride(0), out_b.stride(1), xdbl.stride(0), xdbl.stride(1)
     a.stream, a.dt_pad, a.variant = _stream(), rw - 32, int(variant)     # variant 1: always the 16-step tiles
+    if lens is not None:
+        lp, fn = _slot_lens(lens, b, x.device, "conv_xproj"), N.lib().cm_conv_xproj_lens
+        _launch("cm_conv_xproj_lens", lambda ref: fn(ref, lp), a, units=b * l)
+        return xdbl
     _launch("cm_conv_xproj", N.lib().cm_conv_xproj, a, units=b * l)
     return xdbl
 
@@ -1794,11 +1806,13 @@ def glu_dwconv_ln_gelu(inp, weight, bias, ln_weight, ln_bias, eps=1e-5, weight_t
     ``causal`` (cm_glu_dwconv_ln_gelu_causal): all k - 1 padding rows in front; hist (batch, k - 1, dim) in inp's dtype are
     the gated rows in front of inp (None = zeros), hist_out (another buffer than hist) receives the last k - 1 gated rows of
     [hist | inp].  ``lens`` (cm_glu_dwconv_ln_gelu_causal_slots): int32 (batch,) device tensor, slot b has lens[b] valid rows --
-    hist_out[b] is cut behind gated row lens[b] - 1, output rows at and past it are unspecified.
+    hist_out[b] is cut behind gated row lens[b] - 1, output rows at and past it are unspecified.  ``lens`` without ``causal``
+    (cm_glu_dwconv_ln_gelu_lens): utterance b has lens[b] rows, the 'same' padding starts behind its own last row, output rows at and
+    past lens[b] are not written.
     ``out``: optional contiguous (batch, seqlen, dim) tensor in inp's dtype to receive the result."""
     _dev_check(inp, weight, bias, ln_weight, ln_bias, hist, hist_out)
-    if (hist is not None or hist_out is not None or lens is not None) and not causal:
-        raise RuntimeError("glu_dwconv_ln_gelu: hist / hist_out / lens belong to the causal form")
+    if (hist is not None or hist_out is not None) and not causal:
+        raise RuntimeError("glu_dwconv_ln_gelu: hist / hist_out belong to the causal form")
     if not inp.is_contiguous():
         inp = inp.contiguous()
     b, l, d2 = inp.shape
@@ -1822,7 +1836,10 @@ def glu_dwconv_ln_gelu(inp, weight, bias, ln_weight, ln_bias, eps=1e-5, weight_t
         lb = _f32c(lin_b)
         a.lin_w, a.lin_b = _ptr(lin_w.data), _ptr(lb)
     a.stream, a.variant = _stream(), int(variant)        # variant 1: always the generic 16-step kernel
-    if lens is not None:
+    if lens is not None and not causal:
+        lp, fn = _slot_lens(lens, b, inp.device, "glu_dwconv_ln_gelu"), N.lib().cm_glu_dwconv_ln_gelu_lens
+        _launch("cm_glu_dwconv_ln_gelu_lens", lambda ref: fn(ref, lp), a, units=b * l)
+    elif lens is not None:
         lp, fn = _slot_lens(lens, b, inp.device, "glu_dwconv_ln_gelu"), N.lib().cm_glu_dwconv_ln_gelu_causal_slots
         _launch("cm_glu_dwconv_ln_gelu_causal_slots", lambda ref: fn(ref, lp), a, units=b * l)
     elif causal:
@@ -1856,8 +1873,11 @@ def cnn_front_supported(feats, w1, w2_ohwi) -> bool:
             and w2_ohwi.dtype == torch.bfloat16 and feats.shape[1] >= 5)
 
 
-def cnn_front(feats, w1, b1, ln1_w, ln1_b, eps1, w2_ohwi, b2, ln2_w, ln2_b, eps2, slope=0.01):
-    """feats (batch, T, 80) fp32 -> (batch, T2, 640) bf16: both ConvolutionFrontEnd blocks in one kernel (cm_cnn_front)."""
+def cnn_front(feats, w1, b1, ln1_w, ln1_b, eps1, w2_ohwi, b2, ln2_w, ln2_b, eps2, slope=0.01, lens=None, out=None):
+    """feats (batch, T, 80) fp32 -> (batch, T2, 640) bf16: both ConvolutionFrontEnd blocks in one kernel (cm_cnn_front).
+    ``lens`` (cm_cnn_front_lens): int32 (batch,) device tensor of FRAME counts, utterance b has lens[b] frames and
+    ceil(ceil(lens[b] / 2) / 2) rows -- both reflections at its own ends, rows past its own not written, frames past its own not read.
+    ``out``: optional contiguous (batch, T2, 640) bf16 tensor to receive the result."""
     _dev_check(feats, w1, b1, ln1_w, ln1_b, w2_ohwi, b2, ln2_w, ln2_b)
     feats = feats.float().contiguous()
     if not cnn_front_supported(feats, w1, w2_ohwi) or not w2_ohwi.is_contiguous():
@@ -1869,12 +1889,16 @@ def cnn_front(feats, w1, b1, ln1_w, ln1_b, eps1, w2_ohwi, b2, ln2_w, ln2_b, eps2
     b2f, g2, bt2 = _f32c(b2), _f32c(ln2_w).reshape(-1), _f32c(ln2_b).reshape(-1)
     if g1.numel() != 40 * 64 or g2.numel() != 20 * 32:
         raise RuntimeError("cnn_front: LayerNorm parameters must have 40*64 and 20*32 elements")
-    out = torch.empty((b, t2, 640), dtype=torch.bfloat16, device=feats.device)
+    out = _out_rows(out, (b, t2, 640), torch.bfloat16, feats.device, "cnn_front: out")
     a = N.CnnFrontArgs()
     a.batch, a.T, a.F, a.C1, a.C2 = b, t, f, 64, 32
     a.feats, a.w1, a.b1, a.ln1_g, a.ln1_b = _ptr(feats), _ptr(w1f), _ptr(b1f), _ptr(g1), _ptr(bt1)
     a.w2, a.b2, a.ln2_g, a.ln2_b = _ptr(w2_ohwi), _ptr(b2f), _ptr(g2), _ptr(bt2)
     a.eps1, a.eps2, a.slope, a.out, a.stream = float(eps1), float(eps2), float(slope), _ptr(out), _stream()
+    if lens is not None:
+        lp, fn = _slot_lens(lens, b, feats.device, "cnn_front"), N.lib().cm_cnn_front_lens
+        _launch("cm_cnn_front_lens", lambda ref: fn(ref, lp), a, units=b * t)
+        return out
     _launch("cm_cnn_front", N.lib().cm_cnn_front, a, units=b * t)
     return out
 
@@ -2175,9 +2199,13 @@ def fbank_wav_supported(n_fft: int, hop: int, n_mels: int) -> bool:
     return n_fft == 512 and hop % 2 == 0 and n_mels <= 128
 
 
-def fbank_from_wav(wav, window, n_fft, hop, fbank, amin=1e-10, top_db=80.0, mean=None, std=None):
+def fbank_from_wav(wav, window, n_fft, hop, fbank, amin=1e-10, top_db=80.0, mean=None, std=None, lens=None, bufs=None):
     """(batch, samples) fp32 waveform -> (batch, 1 + samples // hop, n_mels) fp32 log-mel features, STFT included
-    (cm_fbank_wav + cm_fbank_finish): torch.stft(center=True, pad_mode='constant', window centred in n_fft) semantics."""
+    (cm_fbank_wav + cm_fbank_finish): torch.stft(center=True, pad_mode='constant', window centred in n_fft) semantics.
+    ``lens`` (cm_fbank_wav_lens + cm_fbank_finish_lens): int32 (batch,) device tensor of SAMPLE counts, utterance b has lens[b]
+    samples and 1 + lens[b] // hop frames -- samples behind them read as zero, the top_db maximum runs over its own frames, frames
+    at and past its own are not written.  ``bufs``: optional dict of contiguous fp32 outputs db (batch, frames, n_mels), umax (batch,),
+    umax_part (batch, ceil(frames / 16))."""
     _dev_check(wav, window, fbank, mean, std)
     if wav.dtype != torch.float32 or wav.dim() != 2 or wav.stride(1) != 1:
         wav = wav.float().contiguous()
@@ -2191,9 +2219,10 @@ def fbank_from_wav(wav, window, n_fft, hop, fbank, amin=1e-10, top_db=80.0, mean
     lo, hi, off, packed = _mel_bands(fb)
     if packed is None:
         raise RuntimeError("fbank_from_wav: filterbank is not banded (no packed band weights)")
-    db = torch.empty((b, t, m), dtype=torch.float32, device=wav.device)
-    umax = torch.empty((b,), dtype=torch.float32, device=wav.device)
-    part = torch.empty((b, (t + 15) // 16), dtype=torch.float32, device=wav.device)
+    bufs = bufs or {}
+    db = _out_rows(bufs.get("db"), (b, t, m), torch.float32, wav.device, "fbank_from_wav: db")
+    umax = _out_rows(bufs.get("umax"), (b,), torch.float32, wav.device, "fbank_from_wav: umax")
+    part = _out_rows(bufs.get("umax_part"), (b, (t + 15) // 16), torch.float32, wav.device, "fbank_from_wav: umax_part")
     a = N.FbankArgs()
     a.batch, a.n_freq, a.frames, a.n_mels = b, nf, t, m
     a.fbank, a.db, a.umax, a.amin, a.top_db = _ptr(fb), _ptr(db), _ptr(umax), float(amin), float(top_db)
@@ -2204,6 +2233,11 @@ def fbank_from_wav(wav, window, n_fft, hop, fbank, amin=1e-10, top_db=80.0, mean
     a.wav, a.window, a.twiddle, a.wav_bs = _ptr(wav), _ptr(win), _ptr(tw), wav.stride(0)
     a.samples, a.hop, a.n_fft = ns, hop, n_fft
     a.stream = _stream()
+    if lens is not None:
+        lp, lib = _slot_lens(lens, b, wav.device, "fbank_from_wav"), N.lib()
+        _launch("cm_fbank_wav_lens", lambda ref: lib.cm_fbank_wav_lens(ref, lp), a, units=b * t)
+        _launch("cm_fbank_finish_lens", lambda ref: lib.cm_fbank_finish_lens(ref, lp), a, units=b * t)
+        return db
     _launch("cm_fbank_wav", N.lib().cm_fbank_wav, a, units=b * t)
     _launch("cm_fbank_finish", N.lib().cm_fbank_finish, a, units=b * t)
     return db
