@@ -295,6 +295,26 @@ int cm_scan_cl_fwd_lens(const cm_scan_cl_args *args, const int32_t *lens);
 int64_t cm_scan_cl_fwd_workspace_bytes(const cm_scan_cl_args *args);
 /* the chunk count that fills 256 CUs for this problem size (1 = do not chunk); a pure function of the sizes */
 int32_t cm_scan_cl_fwd_auto_chunks(int32_t batch, int32_t seqlen, int32_t dim, int32_t ndir);
+/* Both BiMamba directions folded into ONE output tensor (reference bimamba.py:251-253 adds the directions in front
+ * of out_proj, and both are gated by the same SiLU(z)): dir[0].out (batch, seqlen, dim) receives
+ *     out[t] = io((hi + float(io(p_first[t] - hi)) + p_second[t]) * SiLU(z[t])),  hi = float(io(p_first[t])),
+ * p = sum_n C h + D u the pre-gate value of one direction (p_first is carried as two I/O-dtype pieces: one rounding, the result's),
+ * where "first" is the direction that reaches row t first: with L the sequence's step count and mid = 16 * (ceil(L / 16) / 2), forward
+ * time for t < mid and reverse time for t >= mid -- a function of t and L alone.  Two launches of one grid in args->stream: the first
+ * runs forward time over [0, mid) and reverse time over [mid, L) from zero states, stores p in the I/O dtype into `out`, and what
+ * that rounding dropped and each direction's state into the workspace; the second carries both recurrences on from there (the same values in the same order as an
+ * uncut run), adds, gates once and stores in place.  args->workspace: cm_scan_cl_fwd_fold_workspace_bytes(args) bytes ((2, batch, dim,
+ * 16) fp32 states, then (batch, seqlen, dim) in the I/O dtype), 16-byte aligned, caller owned.  Requires: xdbl mode, two directions of opposite time, z and softplus, bf16 I/O,
+ * dt_rank <= 16, time_chunks <= 1, lanes_per_channel 0 or 4, no ckpt / ypre / h0 / h_last / decay, dir[1].out NULL or equal to
+ * dir[0].out (dir[1]'s out strides are ignored); anything else is refused before anything is launched (CM_EUNSUPPORTED / CM_EINVAL /
+ * CM_EALIGN).  cm_scan_cl_fwd_fold: L = seqlen.  cm_scan_cl_fwd_fold_lens: L = min(max(lens[b], 0), seqlen) with the semantics of
+ * cm_scan_cl_fwd_lens -- rows at and past L are neither read nor written, L == 0 reads and writes nothing, rows [0, L) carry the bits
+ * of cm_scan_cl_fwd_fold on that sequence alone with seqlen = L; lens: `batch` int32 in DEVICE memory, NULL is refused. */
+int cm_scan_cl_fwd_fold(const cm_scan_cl_args *args);
+int cm_scan_cl_fwd_fold_lens(const cm_scan_cl_args *args, const int32_t *lens);
+/* bytes of workspace the fold needs: 2 * batch * dim * 16 * sizeof(float) for the states plus batch * seqlen * dim * 2 for the
+ * remainders of the first launch's bf16 roundings; a pure function of the sizes */
+int64_t cm_scan_cl_fwd_fold_workspace_bytes(const cm_scan_cl_args *args);
 
 /* ---------------------------------------------------------------------------------------
  * Channels-last selective scan BACKWARD, both BiMamba directions in one launch (csrc/scan_rows_bwd.hip): the gradient

@@ -406,6 +406,8 @@ int by_split(const cm_scan_cl_args &a, int ns) {
 int cm_scan_rows_fwd(const cm_scan_cl_args &a, const int32_t *lens, bool whole);   // scan_rows_fwd.hip; lens: per-slot lengths
                                                                                     // (whole: per-utterance, every direction) or NULL
 
+int cm_scan_rows_fold(const cm_scan_cl_args &a, const int32_t *lens, const char *who);   // scan_rows_fwd.hip
+
 #ifdef CM_ABLATE
 extern "C" int cm_debug_set(int v) { return g_debug.exchange(v); }
 extern "C" int cm_debug_get() { return g_debug.load(); }
@@ -474,4 +476,26 @@ extern "C" int cm_scan_cl_fwd_lens(const cm_scan_cl_args *args, const int32_t *l
     for (int i = 0; i < a.ndir; ++i)
         CM_REQUIRE(a.dir[i].xdbl != nullptr, CM_EUNSUPPORTED, "scan_cl_fwd_lens: built for the xdbl mode (the row-group kernel) only");
     return cm_scan_rows_fwd(a, lens, true);
+}
+
+extern "C" int cm_scan_cl_fwd_fold(const cm_scan_cl_args *args) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "scan_cl_fwd_fold: args is NULL");
+    const cm_scan_cl_args &a = *args;
+    CM_REQUIRE(a.batch > 0 && a.dim > 0 && a.seqlen > 0, CM_EINVAL, "scan_cl_fwd_fold: bad sizes batch=%d dim=%d seqlen=%d",
+               a.batch, a.dim, a.seqlen);
+    CM_REQUIRE(a.dstate == 16, CM_EUNSUPPORTED, "scan_cl_fwd_fold: dstate %d unsupported (16 only)", a.dstate);
+    CM_REQUIRE(a.ndir == 1 || a.ndir == 2, CM_EINVAL, "scan_cl_fwd_fold: ndir must be 1 or 2");
+    return cm_scan_rows_fold(a, nullptr, "scan_cl_fwd_fold");
+}
+
+extern "C" int cm_scan_cl_fwd_fold_lens(const cm_scan_cl_args *args, const int32_t *lens) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "scan_cl_fwd_fold_lens: args is NULL");
+    CM_REQUIRE(lens != nullptr, CM_EINVAL, "scan_cl_fwd_fold_lens: lens is NULL (cm_scan_cl_fwd_fold is the form without lengths)");
+    CM_REQUIRE(cm_aligned(lens, 4), CM_EALIGN, "scan_cl_fwd_fold_lens: lens must be 4-byte aligned");
+    const cm_scan_cl_args &a = *args;
+    CM_REQUIRE(a.batch > 0 && a.dim > 0 && a.seqlen > 0, CM_EINVAL, "scan_cl_fwd_fold_lens: bad sizes batch=%d dim=%d seqlen=%d",
+               a.batch, a.dim, a.seqlen);
+    CM_REQUIRE(a.dstate == 16, CM_EUNSUPPORTED, "scan_cl_fwd_fold_lens: dstate %d unsupported (16 only)", a.dstate);
+    CM_REQUIRE(a.ndir == 1 || a.ndir == 2, CM_EINVAL, "scan_cl_fwd_fold_lens: ndir must be 1 or 2");
+    return cm_scan_rows_fold(a, lens, "scan_cl_fwd_fold_lens");
 }

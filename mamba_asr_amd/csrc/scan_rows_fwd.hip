@@ -59,11 +59,18 @@ struct rows_slot_plan : rows_plan {
 // 3 = no per-(channel,step) owner work (softplus / gate), 4 = plain add instead of the output MFMA, 5 = no staging
 // DTR: zero-padded dt_rank of the x_dbl rows, 16 or 32 (32: bf16 only; rows are then [dt32 | B16 | C16] and the K = 32 bf16
 // MFMA that forms delta contracts real columns in all four lane groups -- the S2S-large encoder, d_model 512)
+// FOLD (cm_scan_cl_fwd_fold: both directions into ONE output tensor): 1 = no z is staged and no gate applied, the pre-gate value
+// p = sum_n C h + D u is stored in the I/O dtype, and what that rounding dropped, p - float(io(p)), in the I/O dtype at the same
+// (step, channel) of the contiguous plane fold_res; 2 = the partner direction's p and its remainder are read from the rows this
+// run is about to write (each lane loads exactly the elements it stores, a block's worth before the block's recurrence) and
+// out = io((float(p) + float(rem) + q) * SiLU(z)) goes back in place, q being this run's own fp32 pre-gate value: the stored
+// intermediate carries 16 significant bits, so the result has ONE bf16 rounding.
+// fold_res: this sequence's (seqlen, dim) remainder plane (FOLD != 0), else NULL.
 // Runs steps [t_lo, t_lo + T) of sequence b; h0 / h_last / decay point at this run's (dim, 16) carry slabs or are NULL.
-template <typename IO, bool REV, bool FULL, int ABL = 0, int DTR = 16, bool SUM = false>
+template <typename IO, bool REV, bool FULL, int ABL = 0, int DTR = 16, bool SUM = false, int FOLD = 0>
 __device__ __forceinline__ void scan_rows(const cm_scan_cl_args &p, const cm_scan_cl_dir &d, unsigned char *lds,
                                           const int cx, const int b, const int t_lo, const int T,
-                                          const float *h0, float *h_last, float *decay) {
+                                          const float *h0, float *h_last, float *decay, IO *fold_res = nullptr) {
     using L = rows_lds<IO>;
     constexpr int S = (int)sizeof(IO);
     constexpr int VEC = cm_elem<IO>::kVec;       // elements per 16-byte vector
@@ -74,6 +81,7 @@ __device__ __forceinline__ void scan_rows(const cm_scan_cl_args &p, const cm_sca
     constexpr int XCPR = RW / VEC;               // chunks per x_dbl row
     constexpr int DTC = DTR / 8;                 // bf16 I/O: 16-byte chunks of raw dt columns per row
     static_assert(DTR == 16 || (DTR == 32 && sizeof(IO) == 2), "dt_rank 32 needs bf16 I/O");
+    static_assert(FOLD == 0 || (sizeof(IO) == 2 && FULL && !SUM && ABL == 0), "the fold is built for the bf16 BiMamba call");
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c16 = lane & 15, g = lane >> 4;
@@ -81,7 +89,7 @@ __device__ __forceinline__ void scan_rows(const cm_scan_cl_args &p, const cm_sca
     const int c = c0 + 16 * w + c16;
     const bool c_ok = c < E;
     const int cc = c_ok ? c : E - 1;
-    const bool has_z = !SUM && (FULL || p.z != nullptr);
+    const bool has_z = !SUM && FOLD != 1 && (FULL || p.z != nullptr);
     const bool softplus = FULL || p.delta_softplus != 0;
     const int nblk = (T + TB - 1) / TB;
     const int u_ts = (int)d.u_ts, z_ts = (int)p.z_ts, x_ts = (int)d.xdbl_ts, o_ts = (int)d.out_ts;
@@ -93,6 +101,7 @@ __device__ __forceinline__ void scan_rows(const cm_scan_cl_args &p, const cm_sca
                                                 ((int64_t)(T - 1) * x_ts + RW) * S);
     const __amdgpu_buffer_rsrc_t orr = make_rsrc(SUM ? nullptr : reinterpret_cast<IO *>(d.out) + (int64_t)b * d.out_bs + (int64_t)t_lo * o_ts,
                                                  SUM ? 0 : ((int64_t)(T - 1) * o_ts + E) * S);
+    const __amdgpu_buffer_rsrc_t rrr = make_rsrc(FOLD ? fold_res + (int64_t)t_lo * E : nullptr, FOLD ? (int64_t)T * E * S : 0);
     const bool has_pre = !SUM && d.ypre != nullptr;          // training forward: pre-gate output for cm_scan_cl_bwd
     const int p_ts = (int)d.ypre_ts;
     const __amdgpu_buffer_rsrc_t prr = make_rsrc(has_pre ? reinterpret_cast<IO *>(d.ypre) + (int64_t)b * d.ypre_bs + (int64_t)t_lo * p_ts : nullptr,
@@ -303,16 +312,25 @@ __device__ __forceinline__ void scan_rows(const cm_scan_cl_args &p, const cm_sca
         return y;
     };
 
+    unsigned short pin[4] = {0, 0, 0, 0}, rin[4] = {0, 0, 0, 0};  // FOLD == 2: the partner's p and remainder of the lane's 4 owned steps, raw bf16
+    int r_off = (FOLD && c_ok) ? ((tb0 + 4 * g) * E + c) * S : 0x7fffffff;
+    const int r_step = (FOLD && c_ok) ? DIR * TB * E * S : 0;
     auto gate = [&](const f32x4 &y) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float ov = fmaf(Dv, uq[i], y[i]);
+            if constexpr (FOLD == 2) ov += __uint_as_float((unsigned)pin[i] << 16) + __uint_as_float((unsigned)rin[i] << 16);
+            if constexpr (FOLD == 1) {                                // p in two bf16 pieces: the rounded value, and what the rounding dropped
+                const float hi = __uint_as_float((unsigned)cm_elem<cm_bf16>::to_bits(ov) << 16);
+                st_io(rrr, r_off, i * E * S, ov - hi, IO{});
+            }
             if (has_pre) st_io(prr, p_off, i * p_ts * S, ov, IO{});
             if (has_z && ABL != 3) ov *= zq[i] * cm_sigmoid(zq[i]);
             st_io(orr, o_off, i * o_ts * S, ov, IO{});
         }
         o_off += o_step;
         p_off += p_step;
+        r_off += r_step;
     };
 
     // tile ring: byte offsets of the (u/z, x_dbl) tiles holding block k, k+1 and the one block k+2 is committed to
@@ -331,6 +349,13 @@ __device__ __forceinline__ void scan_rows(const cm_scan_cl_args &p, const cm_sca
     for (int k = 0; k < nblk; ++k) {
         const bool more = ABL != 5 && k + 2 < nblk;
         if (more) issue();
+        if constexpr (FOLD == 2) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                pin[i] = __builtin_amdgcn_raw_buffer_load_b16(orr, o_off, i * o_ts * S, 0);
+                rin[i] = __builtin_amdgcn_raw_buffer_load_b16(rrr, r_off, i * E * S, 0);
+            }
+        }
         if constexpr (!SUM) {
             if (ck) *reinterpret_cast<float4 *>(ck + (REV ? ck_half : 0)) = make_float4(h01.x, h01.y, h23.x, h23.y);
         }
@@ -448,6 +473,43 @@ __global__ __launch_bounds__(256, sizeof(IO) == 2 ? 4 : 3) void scan_rows_lens_k
         if (d.reverse_time) scan_rows<IO, true, false, 0, DTR, false>(p, d, lds, cx, b, 0, T, nullptr, nullptr, nullptr);
         else scan_rows<IO, false, false, 0, DTR, false>(p, d, lds, cx, b, 0, T, nullptr, nullptr, nullptr);
     }
+}
+
+// The fold (cm_scan_cl_fwd_fold / _fold_lens): both directions of a BiMamba layer into ONE (batch, seqlen, dim) tensor of gated sums,
+// as two launches of the same grid (sequence, 64-channel group, direction) in one stream.  With T the sequence's own step count,
+// nblk = ceil(T / 16) and mid = 16 (nblk / 2) -- a block boundary, so both directions keep the 16-step blocks of an uncut run --
+//   PHASE 1: forward time runs [0, mid), reverse time [mid, T), each from a zero state; pre-gate values into `out`, what their bf16
+//            rounding dropped into the workspace's (batch, seqlen, dim) bf16 plane, end states into its (2, batch, dim, 16) fp32 slabs;
+//   PHASE 2: forward time goes on over [mid, T), reverse time over [0, mid), from those states; every row is read (the partner's p,
+//            finished by launch 1), summed, gated once and stored in place.
+// A workgroup of launch 2 reads only rows launch 1 finished and writes only its own (row range x channel segment): the kernel
+// boundary is the whole synchronisation.  Which direction reaches a row first depends on the row index and T alone.
+struct rows_fold_plan {
+    int nx;
+    const int32_t *lens;     // device, or NULL: every sequence has seqlen steps
+    float *ws;               // (2, batch, dim, 16) fp32 states
+    cm_bf16 *res;            // (batch, seqlen, dim): the remainders of launch 1's bf16 roundings
+};
+template <int PHASE>
+__global__ __launch_bounds__(256, 4) void scan_rows_fold_kernel(const cm_scan_cl_args p, const rows_fold_plan pl) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[rows_lds<cm_bf16>::kBytes];
+    const int total = gridDim.x, nx = pl.nx;
+    int id = blockIdx.x;
+    if ((total & 7) == 0) id = (id & 7) * (total >> 3) + (id >> 3);
+    const int cx = id % nx, b = (id / nx) % p.batch, z = id / (nx * p.batch);
+    const cm_scan_cl_dir &d = p.dir[z];
+    const int T = pl.lens ? min(max(pl.lens[b], 0), p.seqlen) : p.seqlen;
+    const int mid = TB * (((T + TB - 1) / TB) / 2);
+    const bool rev = d.reverse_time != 0;
+    const bool low = rev == (PHASE == 2);                         // this run covers [0, mid), else [mid, T)
+    const int t_lo = low ? 0 : mid, n = low ? mid : T - mid;
+    if (n <= 0) return;                                           // T == 0, or mid == 0 and this is the half without rows
+    float *slab = pl.ws + ((int64_t)z * p.batch + b) * p.dim * 16;
+    const float *h0 = (PHASE == 2 && T - n > 0) ? slab : nullptr; // nothing ran before: the zero state
+    float *h_last = PHASE == 1 ? slab : nullptr;
+    cm_bf16 *res = pl.res + (int64_t)b * p.seqlen * p.dim;
+    if (rev) scan_rows<cm_bf16, true, true, 0, 16, false, PHASE>(p, d, lds, cx, b, t_lo, n, h0, h_last, nullptr, res);
+    else scan_rows<cm_bf16, false, true, 0, 16, false, PHASE>(p, d, lds, cx, b, t_lo, n, h0, h_last, nullptr, res);
 }
 
 // Entry state of every chunk from the chunk summaries, in scan order; the caller's h0 enters the first chunk, the caller's
@@ -597,6 +659,58 @@ extern "C" int32_t cm_scan_cl_fwd_auto_chunks(int32_t batch, int32_t seqlen, int
     long c = 1024 / wgs;
     if (c > seqlen / 128) c = seqlen / 128;
     return c < 2 ? 1 : (int32_t)c;
+}
+
+extern "C" int64_t cm_scan_cl_fwd_fold_workspace_bytes(const cm_scan_cl_args *a) {
+    if (!a || a->batch <= 0 || a->dim <= 0 || a->seqlen <= 0) return 0;
+    // the states (2, batch, dim, 16) fp32, then the remainder plane (batch, seqlen, dim) bf16
+    return 2 * (int64_t)a->batch * a->dim * 16 * (int64_t)sizeof(float) + (int64_t)a->batch * a->seqlen * a->dim * 2;
+}
+
+// cm_scan_cl_fwd_fold (lens == NULL) and cm_scan_cl_fwd_fold_lens; the entries (scan_cl_fwd.hip) have checked args, lens and the sizes
+int cm_scan_rows_fold(const cm_scan_cl_args &a0, const int32_t *lens, const char *who) {
+    CM_REQUIRE(a0.ndir == 2 && a0.dir[0].xdbl && a0.dir[1].xdbl, CM_EUNSUPPORTED, "%s: built for the xdbl mode (the row-group kernel) with two directions", who);
+    CM_REQUIRE((a0.dir[0].reverse_time != 0) != (a0.dir[1].reverse_time != 0), CM_EUNSUPPORTED, "%s: the two directions must walk time in opposite ways", who);
+    CM_REQUIRE(a0.z && a0.delta_softplus, CM_EUNSUPPORTED, "%s: needs z and softplus (the BiMamba layer's call)", who);
+    CM_REQUIRE(a0.io_dtype == CM_BF16, CM_EUNSUPPORTED, "%s: io dtype %d: bf16 I/O only", who, a0.io_dtype);
+    CM_REQUIRE(a0.time_chunks <= 1, CM_EUNSUPPORTED, "%s: time_chunks %d: the unchunked launch only", who, a0.time_chunks);
+    CM_REQUIRE(a0.lanes_per_channel == 0 || a0.lanes_per_channel == 4, CM_EUNSUPPORTED, "%s: lanes_per_channel %d (0 or 4)", who, a0.lanes_per_channel);
+    CM_REQUIRE(a0.dim % 8 == 0, CM_EUNSUPPORTED, "%s: dim %d must be a multiple of 8", who, a0.dim);
+    for (int i = 0; i < 2; ++i) {
+        const cm_scan_cl_dir &d = a0.dir[i];
+        CM_REQUIRE(d.dt_rank >= 0 && d.dt_rank <= 16, CM_EUNSUPPORTED, "%s: dir %d: dt_rank %d: at most 16", who, i, d.dt_rank);
+        CM_REQUIRE(!d.ckpt && !d.ypre && !d.h0 && !d.h_last && !d.decay, CM_EUNSUPPORTED,
+                   "%s: dir %d: no training checkpoints, no carried state (ckpt / ypre / h0 / h_last / decay)", who, i);
+    }
+    CM_REQUIRE(a0.dir[1].out == nullptr || a0.dir[1].out == a0.dir[0].out, CM_EUNSUPPORTED,
+               "%s: one output tensor: dir[1].out must be NULL or dir[0].out", who);
+    CM_REQUIRE(a0.dir[0].out != nullptr, CM_EINVAL, "%s: dir 0 has a NULL tensor", who);
+    CM_REQUIRE(cm_aligned(a0.z, 16) && a0.z_bs % 8 == 0 && a0.z_ts % 8 == 0, CM_EALIGN,
+               "%s: z must be 16-byte aligned with strides that are multiples of 8", who);
+    for (int i = 0; i < 2; ++i) {
+        const cm_scan_cl_dir &d = a0.dir[i];
+        CM_REQUIRE(d.u && d.A && d.dt_weight, CM_EINVAL, "%s: dir %d has a NULL tensor", who, i);
+        CM_REQUIRE(cm_aligned(d.u, 16) && d.u_bs % 8 == 0 && d.u_ts % 8 == 0 && cm_aligned(d.xdbl, 16) && d.xdbl_bs % 8 == 0 &&
+                       d.xdbl_ts % 8 == 0 && cm_aligned(d.A, 16) && cm_aligned(d.dt_weight, 16),
+                   CM_EALIGN, "%s: dir %d: u / xdbl / A / dt_weight must be 16-byte aligned, strides multiples of 8", who, i);
+    }
+    CM_REQUIRE(cm_aligned(a0.dir[0].out, 2), CM_EALIGN, "%s: out must be 2-byte aligned", who);
+    const long total = (long)((a0.dim + 63) / 64) * a0.batch * 2;
+    CM_REQUIRE(total < (1L << 31), CM_EINVAL, "%s: grid too large", who);
+    const int64_t need = cm_scan_cl_fwd_fold_workspace_bytes(&a0);
+    CM_REQUIRE(a0.workspace && cm_aligned(a0.workspace, 16) && a0.workspace_bytes >= need, CM_EINVAL,
+               "%s: needs a 16-byte aligned workspace of %lld bytes (cm_scan_cl_fwd_fold_workspace_bytes), got %lld", who,
+               (long long)need, (long long)a0.workspace_bytes);
+    cm_scan_cl_args a = a0;
+    a.dir[1].out = a.dir[0].out, a.dir[1].out_bs = a.dir[0].out_bs, a.dir[1].out_ts = a.dir[0].out_ts;
+    float *states = reinterpret_cast<float *>(a.workspace);
+    rows_fold_plan pl{(a.dim + 63) / 64, lens, states, reinterpret_cast<cm_bf16 *>(states + 2 * (int64_t)a.batch * a.dim * 16)};
+    const dim3 grid((unsigned)total), block(256);
+    hipStream_t st = reinterpret_cast<hipStream_t>(a.stream);
+    hipLaunchKernelGGL(scan_rows_fold_kernel<1>, grid, block, 0, st, a, pl);
+    if (int rc = cm_launch_status(lens ? "cm_scan_cl_fwd_fold_lens(first halves)" : "cm_scan_cl_fwd_fold(first halves)")) return rc;
+    hipLaunchKernelGGL(scan_rows_fold_kernel<2>, grid, block, 0, st, a, pl);
+    return cm_launch_status(lens ? "cm_scan_cl_fwd_fold_lens(second halves)" : "cm_scan_cl_fwd_fold(second halves)");
 }
 
 // called by cm_scan_cl_fwd (scan_cl_fwd.hip) when every direction carries xdbl, by cm_scan_cl_fwd_slots with lens, and by

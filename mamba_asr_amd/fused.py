@@ -119,6 +119,11 @@ class _LayerCache:
         if (self.pw_packed is not None and self.out_cat.is_cuda and self.out_cat.shape[0] == 256 and self.out_cat.shape[1] % 128 == 0
                 and self.out_cat.shape[1] <= 8192 and self.out_bias is None and self.gamma is None):
             self.out_packed = ops.PackedWeight(self.out_cat)
+        # the same projection for the folded scan output (ycat = the gated sum of both directions, E wide): half * out_proj.weight,
+        # (256, E); if_devide_out's 0.5 is a power of two, so the scaling is exact
+        self.out_fold_packed = None
+        if self.out_packed is not None and not self.uni and self.rows_mode and R <= 16 and dtype == torch.bfloat16:
+            self.out_fold_packed = ops.PackedWeight(c(m.out_proj.weight * half))
         self.in_bias_f = None if m.in_proj.bias is None else f(m.in_proj.bias)
         self.out_bias_f = None if m.out_proj.bias is None else f(m.out_proj.bias)
         self.dw_w, self.dw_b = f(cm.conv.weight), f(cm.conv.bias)
@@ -197,7 +202,19 @@ USE_SCAN_ROWS = os.environ.get("CM_SCAN_ROWS", "1") == "1"
 USE_CONV_XPROJ = os.environ.get("CM_CONV_XPROJ", "1") == "1"
 
 
-def _scan_dirs(c: _LayerCache, ucat, ycat, batch, seqlen, xdbl=None):
+# both directions' gated outputs summed by the scan into one E-wide tensor (cm_scan_cl_fwd_fold), out_proj at K = E in the mixer's
+# tail; CM_SCAN_FOLD=0 = [y_fwd | y_bwd] and K = 2E
+USE_SCAN_FOLD = os.environ.get("CM_SCAN_FOLD", "1") == "1"
+
+
+def _layer_folds(c: _LayerCache) -> bool:
+    """The layer's scan folds its directions: a function of the layer cache and the switches (the caller adds the chunk policy --
+    time-chunked launches stay on the two-tensor route)."""
+    return (USE_SCAN_FOLD and USE_SCAN_ROWS and USE_MIXER_TAIL and USE_LN_PW_GLU and c.out_fold_packed is not None
+            and _conv_forms_xdbl(c))
+
+
+def _scan_dirs(c: _LayerCache, ucat, ycat, batch, seqlen, xdbl=None, fold=False):
     """x_proj for both directions (one library GEMM, time-contiguous output rows), fp32 feature buffer, and the two
     direction descriptors of cm_scan_cl_fwd (one of each for the unidirectional mixer: ucat / ycat are E wide then).
     ``xdbl``: x_proj's rows when cm_conv_xproj has formed them already (only the row-group kernel reads them)."""
@@ -208,8 +225,9 @@ def _scan_dirs(c: _LayerCache, ucat, ycat, batch, seqlen, xdbl=None):
             xdbl = (ucat.view(rows, nd * E) @ c.x_proj_rows.t()).view(batch, seqlen, nd * c.row_width)  # one library GEMM, rows as the scan reads them
         RW = c.row_width
         return [dict(u=ucat[:, :, i * E:(i + 1) * E], A=d["A"], D=d["D"], delta_bias=d["dt_bias"], dt_weight=d["dt_w16"],
-                     xdbl=xdbl[:, :, RW * i:RW * (i + 1)], out=ycat[:, :, i * E:(i + 1) * E], reverse=bool(i))
+                     xdbl=xdbl[:, :, RW * i:RW * (i + 1)], out=ycat if fold else ycat[:, :, i * E:(i + 1) * E], reverse=bool(i))
                 for i, d in enumerate(c.dirs)]
+    assert not fold
     xdblT = c.x_proj_bd @ ucat.view(rows, nd * E).t()                     # (2P, rows): [dt | B | C] fwd, then bwd
     feat = ops.alloc_bc(nd * P, batch, seqlen, ucat.device)
     feat.view(nd * P, rows).copy_(xdblT)                                  # one bf16 -> fp32 conversion
@@ -242,8 +260,10 @@ def _out_proj(c: _LayerCache, ycat):
 
 def mixer_tail(c: _LayerCache, x, ycat):
     """The mixer's tail on the residual stream: x += out_proj(ycat); conv-module LN; pointwise conv; GLU.  x (rows, D) fp32, updated in
-    place; ycat (rows, 2E) bf16 contiguous.  One kernel (cm_ln_pw_glu with the projection in front) when out_proj has neither bias nor
+    place; ycat (rows, 2E) bf16 contiguous, or (rows, E): the folded scan output.  One kernel (cm_ln_pw_glu with the projection in front) when out_proj has neither bias nor
     layer scale, else the library GEMM and cm_ln_pw_glu.  Returns the gated (rows, D) bf16 tensor."""
+    if ycat.shape[1] == c.d_inner and not c.uni:
+        return ops.ln_pw_glu(x, None, 1.0, c.cm_ln, c.pw_packed, c.pw_bf, ycat=ycat, out_w=c.out_fold_packed)
     if USE_MIXER_TAIL and c.out_packed is not None:
         return ops.ln_pw_glu(x, None, 1.0, c.cm_ln, c.pw_packed, c.pw_bf, ycat=ycat, out_w=c.out_packed)
     return ops.ln_pw_glu(x, _out_proj(c, ycat), 1.0, c.cm_ln, c.pw_packed, c.pw_bf)
@@ -282,19 +302,21 @@ def _conv(c: _LayerCache, xz, ucat, xdbl=None, xproj=True, hist=None, lens=None)
     return None
 
 
-def _scan(c: _LayerCache, xz, ucat, ycat, xdbl, batch, seqlen, state=None, lens=None):
+def _scan(c: _LayerCache, xz, ucat, ycat, xdbl, batch, seqlen, state=None, lens=None, fold=False):
     """Both directions' selective scan of ucat, gated by xz's z half, into ycat (all (batch, seqlen, 2E)): one launch.
+    ``fold``: ycat is (batch, seqlen, E) and receives the gated sum of both directions (cm_scan_cl_fwd_fold).
     ``state`` (batch, E, 16) fp32, streaming: the unidirectional scan starts from it and leaves its last state there (each workgroup
     reads its channels' entry state before it writes them), unchunked -- the recurrence then visits the same values in the same
     order as over the whole sequence.  ``lens`` (with ``state``): per-slot step counts (cm_scan_cl_fwd_slots).  ``lens`` without
     ``state``: the utterances' own step counts, every direction, unchunked (cm_scan_cl_fwd_lens; the ragged whole-utterance route)."""
-    dirs = _scan_dirs(c, ucat, ycat, batch, seqlen, xdbl)
+    dirs = _scan_dirs(c, ucat, ycat, batch, seqlen, xdbl, fold)
     if state is None and lens is not None:
-        ops.scan_cl_fwd(dirs, z=xz[:, :, c.d_inner:], delta_softplus=True, time_chunks=1, lens=lens, whole=True)
+        ops.scan_cl_fwd(dirs, z=xz[:, :, c.d_inner:], delta_softplus=True, time_chunks=1, lens=lens, whole=True, fold=fold)
         return
     if state is None:
-        ops.scan_cl_fwd(dirs, z=xz[:, :, c.d_inner:], delta_softplus=True)
+        ops.scan_cl_fwd(dirs, z=xz[:, :, c.d_inner:], delta_softplus=True, fold=fold)
         return
+    assert not fold
     if len(dirs) != 1 or "xdbl" not in dirs[0]:
         raise NotImplementedError("streaming needs the row-group scan (dt_rank <= 16, or <= 32 in bf16) of a unidirectional mixer")
     ops.scan_cl_fwd([dict(dirs[0], h0=state, h_last=state)], z=xz[:, :, c.d_inner:], delta_softplus=True, time_chunks=1, lens=lens)
@@ -353,7 +375,7 @@ def _ffn2(c: _LayerCache, x, addend, final_ln=None, f2=None):
 
 
 def _tail(c: _LayerCache, x, ycat, batch, seqlen, final_ln=None, small=False, hist=None, lens=None):
-    """A layer behind the scan, on the rows of whole utterances: x (rows, D) fp32 += out_proj(ycat (rows, 2E)); the
+    """A layer behind the scan, on the rows of whole utterances: x (rows, D) fp32 += out_proj(ycat (rows, 2E, or E folded)); the
     convolution module; FFN2 + norm2 (-> _ffn2).  ``hist`` = (hist, hist_out) of cm_glu_dwconv_ln_gelu_causal, the native
     streaming route's carry, ``lens`` its per-slot row counts (cm_glu_dwconv_ln_gelu_causal_slots).  ``lens`` without ``hist``: the
     utterances' own row counts under the 'same' padding (cm_glu_dwconv_ln_gelu_lens; the ragged whole-utterance route)."""
@@ -511,7 +533,13 @@ def _encoder_forward_joined(encoder, src, dtype, ns, paired=False, lens=None):
         nd = len(caches[0].dirs)
         xz = torch.empty((batch, seqlen, 2 * caches[0].d_inner), dtype=dtype, device=dev)
         ucat = torch.empty((batch, seqlen, nd * caches[0].d_inner), dtype=dtype, device=dev)
-        ycat = torch.empty_like(ucat)
+        # a layer folds both directions into an E-wide ycat unless its scan launches are time-chunked (small batches without lens)
+        E = caches[0].d_inner
+        unchunked = all(ops.scan_chunks_policy(nb, seqlen, E, nd, lens) == 1
+                        for nb in ([b1 - b0 for b0, b1 in parts] if paired else [batch]))
+        folds = [unchunked and _layer_folds(c) for c in caches]
+        ycat = None if all(folds) else torch.empty_like(ucat)
+        yfold = torch.empty((batch, seqlen, E), dtype=dtype, device=dev) if any(folds) else None
         xdbl = torch.empty((batch, seqlen, nd * caches[0].row_width), dtype=dtype, device=dev) if _conv_forms_xdbl(caches[0]) else None
         x3 = x.view(batch, seqlen, D)
         rows = lambda t, b0, b1: t[b0:b1].view((b1 - b0) * seqlen, -1)      # a part's utterances of a (batch, seqlen, .) buffer as rows
@@ -528,6 +556,8 @@ def _encoder_forward_joined(encoder, src, dtype, ns, paired=False, lens=None):
         fork()
         gate = None                                                                 # pair mode: end of the scan launched last
         for li, c in enumerate(caches):
+            fold = folds[li]
+            yc = yfold if fold else ycat
             for st, (b0, b1), pl in zip(streams, parts, psl):
                 with torch.cuda.stream(st):
                     _head(c, rows(x3, b0, b1), xz[b0:b1], ucat[b0:b1], None if xdbl is None else xdbl[b0:b1], small, lens=pl)
@@ -536,16 +566,16 @@ def _encoder_forward_joined(encoder, src, dtype, ns, paired=False, lens=None):
                     with torch.cuda.stream(st):
                         if gate is not None:
                             st.wait_event(gate)
-                        _scan(c, xz[b0:b1], ucat[b0:b1], ycat[b0:b1], xdbl[b0:b1], b1 - b0, seqlen, lens=pl)
+                        _scan(c, xz[b0:b1], ucat[b0:b1], yc[b0:b1], xdbl[b0:b1], b1 - b0, seqlen, lens=pl, fold=fold)
                         gate = torch.cuda.Event()
                         gate.record(st)
             else:
                 join()
-                _scan(c, xz, ucat, ycat, xdbl, batch, seqlen, lens=sl)
+                _scan(c, xz, ucat, yc, xdbl, batch, seqlen, lens=sl, fold=fold)
                 fork()
             for pi, (st, (b0, b1)) in enumerate(zip(streams, parts)):
                 with torch.cuda.stream(st):
-                    outs[pi] = _tail(c, rows(x3, b0, b1), rows(ycat, b0, b1), b1 - b0, seqlen,
+                    outs[pi] = _tail(c, rows(x3, b0, b1), rows(yc, b0, b1), b1 - b0, seqlen,
                                      fin if li == len(caches) - 1 else None, small, lens=psl[pi])
         join()
         for o in outs[1:]:

@@ -509,13 +509,25 @@ def _scan_cl_dir_rows(x, dd, u0, z, keep):
 SCAN_CHUNKS = os.environ.get("CM_SCAN_CHUNKS", "auto")
 
 
-def scan_cl_fwd(directions, z=None, delta_softplus=True, time_chunks=None, split: int = 0, lens=None, whole: bool = False):
+def scan_chunks_policy(batch: int, seqlen: int, dim: int, ndir: int, lens=None) -> int:
+    """The chunk count scan_cl_fwd picks for an xdbl-mode launch that names none: 1 under ``lens``, else CM_SCAN_CHUNKS."""
+    if lens is not None:
+        return 1
+    return N.lib().cm_scan_cl_fwd_auto_chunks(batch, seqlen, dim, ndir) if SCAN_CHUNKS == "auto" else int(SCAN_CHUNKS)
+
+
+def scan_cl_fwd(directions, z=None, delta_softplus=True, time_chunks=None, split: int = 0, lens=None, whole: bool = False, fold: bool = False,
+                workspace=None):
     """Channels-last selective scan, 1 or 2 directions in one launch (cm_scan_cl_fwd).
     ``time_chunks`` (xdbl mode): None = the CM_SCAN_CHUNKS policy, else the chunk count.
     ``lens`` (cm_scan_cl_fwd_slots; xdbl mode, one direction, unchunked): int32 (batch,) device tensor, sequence b runs its first
     lens[b] steps only (h_last = h0 for 0); ``out`` rows at and past lens[b] are not written.  With two directions, or
     ``whole=True`` (cm_scan_cl_fwd_lens; xdbl mode, unchunked, no carried state): sequence b is a whole utterance of lens[b] steps --
     the reverse direction starts from a zero state at step lens[b] - 1.
+    ``fold`` (cm_scan_cl_fwd_fold / _fold_lens; xdbl mode, two directions of opposite time, z, softplus, bf16, dt_rank <= 16, unchunked):
+    the gated SUM of both directions goes into directions[0]["out"] (batch, seqlen, dim) -- directions[1]["out"] must be absent or that
+    tensor -- and [out] is returned; ``workspace``: a caller-owned contiguous tensor of at least cm_scan_cl_fwd_fold_workspace_bytes
+    bytes, 16-byte aligned (allocated here otherwise).  Logged as the unfolded launch is (cm_scan_cl_fwd, or cm_scan_cl_fwd_lens with lengths).
 
     ``directions``: list of dicts with u, delta (batch, seqlen, dim), A (dim, 16), B, C (16, batch, seqlen) fp32
     time-contiguous (see alloc_bc), D, delta_bias (dim) or None, out (batch, seqlen, dim) view or None, reverse.
@@ -534,7 +546,14 @@ def scan_cl_fwd(directions, z=None, delta_softplus=True, time_chunks=None, split
         _rows_ok(z, "z")
         a.z, a.z_bs, a.z_ts = _ptr(z), z.stride(0), z.stride(1)
     outs = []
+    if fold:
+        if len(directions) != 2 or any(dd.get("xdbl") is None for dd in directions):
+            raise RuntimeError("fold needs two directions in xdbl mode")
+        if directions[1].get("out") is not None and directions[1]["out"] is not directions[0].get("out"):
+            raise RuntimeError("fold writes one tensor: directions[1]['out'] must be absent or directions[0]['out']")
     for i, dd in enumerate(directions):
+        if fold and i == 1:
+            dd = dict(dd, out=outs[0])
         if dd.get("xdbl") is not None:
             outs.append(_scan_cl_dir_rows(a.dir[i], dd, u0, z, keep))
             continue
@@ -576,8 +595,7 @@ def scan_cl_fwd(directions, z=None, delta_softplus=True, time_chunks=None, split
     a.lanes_per_channel = int(split)                     # tuning of the state-split kernel: 4, 8, 16 lanes per channel; 0 = automatic
     if "xdbl" in directions[0]:
         if time_chunks is None:
-            time_chunks = 1 if lens is not None else (N.lib().cm_scan_cl_fwd_auto_chunks(b, l, d, len(directions)) if SCAN_CHUNKS == "auto"
-                                                      else int(SCAN_CHUNKS))
+            time_chunks = scan_chunks_policy(b, l, d, len(directions), lens)
         a.time_chunks = int(time_chunks)
         nbytes = N.lib().cm_scan_cl_fwd_workspace_bytes(ct.byref(a))
         if nbytes:
@@ -586,6 +604,22 @@ def scan_cl_fwd(directions, z=None, delta_softplus=True, time_chunks=None, split
             a.workspace, a.workspace_bytes = _ptr(ws), nbytes
     elif time_chunks not in (None, 0, 1):
         raise RuntimeError("time_chunks needs the xdbl mode")
+    if fold:
+        if a.time_chunks > 1:
+            raise RuntimeError(f"fold: the unchunked launch only (time_chunks {a.time_chunks}); the caller asks the chunk policy first")
+        nbytes = N.lib().cm_scan_cl_fwd_fold_workspace_bytes(ct.byref(a))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=u0.device) if workspace is None else workspace
+        _dev_check(ws)
+        if not ws.is_contiguous() or ws.numel() * ws.element_size() < nbytes:
+            raise RuntimeError(f"fold: workspace must be a contiguous tensor of at least {nbytes} bytes")
+        keep.append(ws)
+        a.workspace, a.workspace_bytes = _ptr(ws), ws.numel() * ws.element_size()
+        if lens is not None:
+            lp, fn = _slot_lens(lens, b, u0.device, "scan_cl_fwd"), N.lib().cm_scan_cl_fwd_fold_lens
+            _launch("cm_scan_cl_fwd_lens", lambda ref: fn(ref, lp), a, units=b * l * 2)
+        else:
+            _launch("cm_scan_cl_fwd", N.lib().cm_scan_cl_fwd_fold, a, units=b * l * 2)
+        return outs[:1]
     if lens is not None and (whole or len(directions) == 2):
         lp, fn = _slot_lens(lens, b, u0.device, "scan_cl_fwd"), N.lib().cm_scan_cl_fwd_lens
         _launch("cm_scan_cl_fwd_lens", lambda ref: fn(ref, lp), a, units=b * l * len(directions))
