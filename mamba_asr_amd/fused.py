@@ -105,7 +105,7 @@ class _LayerCache:
             self.x_proj_rows = torch.block_diag(*rows)            # (2 RW, 2 E)
             # per-direction (RW, E) images for cm_conv_xproj (conv + x_proj in one kernel, bf16)
             self.wx_packed = None
-            if dtype == torch.bfloat16 and m.d_inner % 32 == 0 and m.d_inner <= 2048 and rows[0].is_cuda and m.d_conv == 4:
+            if dtype == torch.bfloat16 and ops.conv_xproj_supported(m.d_inner, pad, m.d_conv, len(sfxs)) and rows[0].is_cuda:
                 self.wx_packed = [ops.PackedWeight(r) for r in rows]
             for d_, dtp in zip(self.dirs, [getattr(m, "dt_proj" + sfx) for sfx in sfxs]):
                 d_["dt_w16"] = ops.pad_dt_weight(dtp.weight.detach().to(dtype))      # dtype-rounded like the reference's GEMM operand
@@ -167,8 +167,10 @@ def supports(layer) -> bool:
     cm = layer.convolution_module
     act_ok = isinstance(cm.after_conv[1], torch.nn.GELU) and isinstance(layer.ffn_module1[1].ffn[1], torch.nn.GELU)
     mixer_ok = isinstance(layer.mamba, UniMamba) if cm.causal else isinstance(layer.mamba, BiMamba)
+    # every route off cm_ffn_fused (d_model 256 / 144) joins its stages with cm_add_layernorm: rows of whole float4s, 1024 columns at most
+    d = layer.mamba.d_model
     return (mixer_ok and cm.kernel_size == 31 and cm.dilation == 1 and act_ok
-            and layer.mamba.d_state == 16 and layer.mamba.d_conv == 4)
+            and layer.mamba.d_state == 16 and layer.mamba.d_conv == 4 and d % 4 == 0 and d <= 1024)
 
 
 def _ffn(x, y_in, p, dtype):

@@ -61,7 +61,7 @@ class _Derived:
             self.xr.append(ops.xproj_rows(xp.weight, R, P, cdt))
             self.dtw.append(ops.pad_dt_weight(dtp.weight.detach().to(cdt)))
             self.A.append((-torch.exp(getattr(m, "A_b_log" if s else "A_log").detach().float())).contiguous())
-        if cdt == torch.bfloat16 and len(sfx) == 2 and E % 32 == 0 and E <= 2048:
+        if cdt == torch.bfloat16 and len(sfx) == 2 and ops.conv_xproj_supported(E, P, m.d_conv):
             self.xr_packed = [ops.PackedWeight(x) for x in self.xr]
         # both directions' x_proj as ONE block-diagonal (2 RW, 2 E) matrix: the backward's input gradient (du += dx_dbl W_x) and weight
         # gradient are one GEMM / one batched GEMM for the pair instead of one per direction (the step is host-bound: launches count)

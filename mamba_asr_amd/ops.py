@@ -1289,6 +1289,13 @@ def scan_cl_bwd(directions, z, time_chunks=0, da_log=False):
     return outs
 
 
+def conv_xproj_supported(dim: int, dt_pad: int, d_conv: int = 4, ndir: int = 2) -> bool:
+    """cm_conv_xproj (``ndir`` 2) / cm_conv_xproj_uni (1) take the mixer: conv width 4, channels in whole 32-column groups up to 2048,
+    and for both directions with 64-wide x_dbl rows (dt_pad 32: 16 < dt_rank <= 32) a 16-step tile pair within 80 KiB of LDS -- 1248
+    channels at the most (the entry points' own checks, csrc/conv_xproj.hip)."""
+    return d_conv == 4 and dim % 32 == 0 and dim <= 2048 and (dt_pad != 32 or ndir == 1 or 2 * 16 * (dim + 16) * 2 <= 80 * 1024)
+
+
 def conv_xproj(x, weight_f, bias_f, weight_b, bias_b, wx_f, wx_b, out_f, out_b, xdbl=None, variant: int = 0, lens=None):
     """Both directions' depthwise conv + SiLU and x_proj GEMMs in one kernel (cm_conv_xproj, bf16).
     x (batch, seqlen, dim) view; conv weights (dim, 4) fp32; wx_f / wx_b PackedWeight of the (P + 32, dim) re-rowed x_proj
@@ -2000,8 +2007,10 @@ def gemm_bf16(a, w, bias=None, epilogue=0, x=None, alpha=1.0, norm1=None, norm2=
 
 
 def ffn_supported(d_model: int, hidden: int, dtype) -> bool:
-    """cm_ffn_fused's inference forward covers the module: d_model 256, or 144 on the 16x16x32 kernel (csrc/fused_d144.hip)."""
-    return dtype == torch.bfloat16 and (d_model == 256 or (d_model == 144 and FFN_LAYOUT == 16)) and hidden >= 256 and hidden % 256 == 0
+    """cm_ffn_fused's inference forward covers the module: d_model 256, or 144 on the 16x16x32 kernel (csrc/fused_d144.hip); the hidden
+    width in whole 256-column slabs, 2048 at the most (the entry point's own limit, csrc/ffn_fused.hip)."""
+    return (dtype == torch.bfloat16 and (d_model == 256 or (d_model == 144 and FFN_LAYOUT == 16)) and hidden >= 256 and hidden % 256 == 0
+            and hidden <= 2048)
 
 
 # cm_ffn_fused's inference forward on v_mfma_f32_32x32x16_bf16 (csrc/ffn_fused32.hip, weights in the 32 x 16 tile image) instead of

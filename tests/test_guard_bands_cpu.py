@@ -185,7 +185,7 @@ def _colsum_case(rows=9, d=8, ws_rows=None, **fault):
     inp = torch.randn(rows, d)
     nwg = (rows + TILE - 1) // TILE
     nws = (ws_rows or nwg) * d
-    stale = torch.empty(nws + d)
+    stale = torch.zeros(nws + d)                                              # rows the first run does not write are zero, not whatever the host allocator recycled
     k_colsum(inp, stale[:nws], torch.empty(d))                               # the "first run" of a run-twice determinism check
     stale[nws:] = 0.0
 
