@@ -213,6 +213,23 @@ def _bufs(bufs, names, what):
     return take
 
 
+def _time_view(t, shape, dtype, device, what):
+    """A caller-supplied (batch, dim, seqlen) output of the operator-route kernels: any view with the time axis contiguous (a half of
+    xz, (dim, batch, seqlen) storage), or a fresh one."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.stride(-1) != 1 or t.device != device:
+        raise RuntimeError(f"{what} must be a {dtype} tensor of shape {tuple(shape)} on {device} with the time axis contiguous")
+    return t
+
+
+def _accum(bufs, name, shape, device, what):
+    """A caller-placed fp32 reduction output is ACCUMULATED into (the C contract); a fresh one starts at zero."""
+    if bufs is None or bufs.get(name) is None:
+        return torch.zeros(shape, dtype=torch.float32, device=device)
+    return _out_rows(bufs[name], shape, torch.float32, device, f"{what}: bufs[{name!r}]")
+
+
 def _time_contig(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     # same rule as the reference wrappers (selective_scan_interface.py:24-35): last dim must have stride 1
     if t is None:
@@ -267,12 +284,14 @@ def _fill_scan_args(a, u, delta, A, B, C_, D, z, delta_bias, delta_softplus, rev
 
 def selective_scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False,
                        reverse=False, need_out=True, need_x=True, out_z_buf: Optional[torch.Tensor] = None,
-                       h0: Optional[torch.Tensor] = None, split: int = 0):
+                       h0: Optional[torch.Tensor] = None, split: int = 0, bufs=None):
     """-> (out, x, out_z): what selective_scan_cuda.fwd returns (selective_scan_interface.py:42).
     ``out`` is the pre-gate output (None when z is given and need_out is False), ``x`` the
     checkpoint tensor (batch, dim, nchunks, 2*dstate) or None, ``out_z`` the gated output or None.
     ``h0`` (batch, dim, dstate) fp32: state the recurrence starts from (time-split scans, seqpar.py).
-    ``split``: tuning, lanes per channel (cm_scan_fwd_args.lanes_per_channel; 0 = the library's choice)."""
+    ``split``: tuning, lanes per channel (cm_scan_fwd_args.lanes_per_channel; 0 = the library's choice).
+    ``bufs``: caller-supplied ``out`` / ``out_z`` (time-contiguous (batch, dim, seqlen) views of u's dtype; the C contract gives both
+    one pair of strides) and ``x`` (contiguous fp32); an output this call does not produce may not be placed."""
     _dev_check(u, delta, A, B, C, D, z, delta_bias)
     u, delta, z = _time_contig(u), _time_contig(delta), _time_contig(z)
     if delta.dtype != u.dtype or (z is not None and z.dtype != u.dtype):
@@ -284,14 +303,25 @@ def selective_scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta
     b, d, l = u.shape
     a = N.ScanFwdArgs()
     _fill_scan_args(a, u, delta, A, B, C, D, z, delta_bias, delta_softplus, reverse)
-    out = torch.empty((b, d, l), dtype=u.dtype, device=u.device) if (z is None or need_out) else None
+    want_out = z is None or need_out
+    if bufs is not None:
+        what = "selective_scan_fwd"
+        _bufs(bufs, ("out", "out_z", "x"), what)
+        if out_z_buf is not None and bufs.get("out_z") is not None:
+            raise RuntimeError(f"{what}: out_z_buf and bufs['out_z'] name the same output")
+        for name, made in (("out", want_out), ("out_z", z is not None), ("x", need_x)):
+            if bufs.get(name) is not None and not made:
+                raise RuntimeError(f"{what}: bufs[{name!r}] places an output this call does not produce")
+        out_z_buf = bufs.get("out_z") if out_z_buf is None else out_z_buf
+    out = _time_view(None if bufs is None else bufs.get("out"), (b, d, l), u.dtype, u.device, "selective_scan_fwd: bufs['out']") if want_out else None
     out_z = None
     if z is not None:
         # out_z_buf: a pre-allocated time-contiguous (batch, dim, seqlen) view, e.g. of (dim, batch, seqlen) storage
         out_z = out_z_buf if out_z_buf is not None else torch.empty((b, d, l), dtype=u.dtype, device=u.device)
         if out_z.shape != (b, d, l) or out_z.stride(-1) != 1 or out_z.dtype != u.dtype:
             raise RuntimeError("out_z_buf must be a time-contiguous (batch, dim, seqlen) tensor of u's dtype")
-    x = torch.empty((b, d, num_chunks(l), 2 * A.shape[1]), dtype=torch.float32, device=u.device) if need_x else None
+    xshape = (b, d, num_chunks(l), 2 * A.shape[1])
+    x = _out_rows(None if bufs is None else bufs.get("x"), xshape, torch.float32, u.device, "selective_scan_fwd: bufs['x']") if need_x else None
     a.out, a.out_z, a.x = _ptr(out), _ptr(out_z), _ptr(x)
     if h0 is not None:
         _dev_check(h0)
@@ -299,10 +329,11 @@ def selective_scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta
             raise RuntimeError(f"h0 must be (batch, dim, dstate) = {(b, d, A.shape[1])}, got {tuple(h0.shape)}")
         h0 = _f32c(h0)
         a.h0 = _ptr(h0)
-    a.out_bs, a.out_ds = d * l, l
+    if out is not None:
+        a.out_bs, a.out_ds = out.stride(0), out.stride(1)
     a.lanes_per_channel = int(split)
     if out_z is not None:
-        if out is not None and (out_z.stride(0), out_z.stride(1)) != (d * l, l):
+        if out is not None and (out_z.stride(0), out_z.stride(1)) != (out.stride(0), out.stride(1)):
             raise RuntimeError("out and a strided out_z_buf cannot be requested together (they share strides)")
         a.out_bs, a.out_ds = out_z.stride(0), out_z.stride(1)
     _launch("cm_selective_scan_fwd", N.lib().cm_selective_scan_fwd, a, units=b * l)
@@ -311,10 +342,27 @@ def selective_scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta
 
 def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, x, delta_softplus=False, reverse=False,
                        dz: Optional[torch.Tensor] = None, recompute_out_z=False, du_buf: Optional[torch.Tensor] = None,
-                       ddelta_buf: Optional[torch.Tensor] = None, out_z_buf: Optional[torch.Tensor] = None, split: int = 0):
+                       ddelta_buf: Optional[torch.Tensor] = None, out_z_buf: Optional[torch.Tensor] = None, split: int = 0, bufs=None):
     """-> (du, ddelta, dA, dB, dC, dD, ddelta_bias, dz, out_z): the tuple selective_scan_cuda.bwd
     returns (selective_scan_interface.py:67, 252).  ``dz`` may be a pre-allocated view (e.g. half of
-    dxz, :249-256).  dB/dC are fp32 (batch, 1, dstate, seqlen)."""
+    dxz, :249-256).  dB/dC are fp32 (batch, 1, dstate, seqlen).
+    ``bufs``: caller-supplied ``du`` / ``ddelta`` / ``dz`` / ``out_z`` (time-contiguous views, as the *_buf keywords they stand for),
+    ``dA`` / ``dB`` / ``dC`` / ``dD`` / ``ddelta_bias`` (contiguous fp32, ACCUMULATED into, not zeroed) and ``workspace``
+    (cm_selective_scan_bwd_workspace_bytes / 4 floats; the deterministic path only)."""
+    if bufs is not None:
+        what = "selective_scan_bwd"
+        _bufs(bufs, ("du", "ddelta", "dz", "out_z", "dA", "dB", "dC", "dD", "ddelta_bias", "workspace"), what)
+        for name, kw in (("du", du_buf), ("ddelta", ddelta_buf), ("dz", dz), ("out_z", out_z_buf)):
+            if kw is not None and bufs.get(name) is not None:
+                raise RuntimeError(f"{what}: bufs[{name!r}] and the keyword name the same output")
+        for name, made in (("dz", z is not None), ("out_z", z is not None and recompute_out_z), ("dD", D is not None),
+                           ("ddelta_bias", delta_bias is not None), ("workspace", DETERMINISTIC)):
+            if bufs.get(name) is not None and not made:
+                raise RuntimeError(f"{what}: bufs[{name!r}] places a buffer this call does not use")
+        placed = lambda name, kw: kw if bufs.get(name) is None else bufs[name]
+        du_buf, ddelta_buf, dz, out_z_buf = placed("du", du_buf), placed("ddelta", ddelta_buf), placed("dz", dz), placed("out_z", out_z_buf)
+        if dz is not None and (tuple(dz.shape) != tuple(u.shape) or dz.dtype != u.dtype):
+            raise RuntimeError(f"{what}: bufs['dz'] must be a time-contiguous (batch, dim, seqlen) tensor of u's dtype")
     _dev_check(u, delta, A, B, C, D, z, delta_bias, dout, x)
     u, delta, z, dout = _time_contig(u), _time_contig(delta), _time_contig(z), _time_contig(dout)
     B, C = _bc4(B), _bc4(C)
@@ -344,11 +392,11 @@ def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, x, delta_softp
         dz = torch.empty((b, d, l), dtype=u.dtype, device=dev)
     if z is not None and dz.stride(-1) != 1:
         raise RuntimeError("dz must be time-contiguous")
-    dA = torch.zeros((d, n), dtype=torch.float32, device=dev)
-    dB = torch.zeros((b, 1, n, l), dtype=torch.float32, device=dev)
-    dC = torch.zeros((b, 1, n, l), dtype=torch.float32, device=dev)
-    dD = torch.zeros((d,), dtype=torch.float32, device=dev) if D is not None else None
-    dbias = torch.zeros((d,), dtype=torch.float32, device=dev) if delta_bias is not None else None
+    dA = _accum(bufs, "dA", (d, n), dev, "selective_scan_bwd")
+    dB = _accum(bufs, "dB", (b, 1, n, l), dev, "selective_scan_bwd")
+    dC = _accum(bufs, "dC", (b, 1, n, l), dev, "selective_scan_bwd")
+    dD = _accum(bufs, "dD", (d,), dev, "selective_scan_bwd") if D is not None else None
+    dbias = _accum(bufs, "ddelta_bias", (d,), dev, "selective_scan_bwd") if delta_bias is not None else None
     a.dout, a.dout_bs, a.dout_ds = _ptr(dout), dout.stride(0), dout.stride(1)
     a.du, a.ddelta, a.dz = _ptr(du), _ptr(ddelta), _ptr(dz if z is not None else None)
     a.du_bs, a.du_ds, a.ddelta_bs, a.ddelta_ds = du.stride(0), du.stride(1), ddelta.stride(0), ddelta.stride(1)
@@ -357,19 +405,28 @@ def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, x, delta_softp
     a.dA, a.dB, a.dC, a.dD, a.ddelta_bias = _ptr(dA), _ptr(dB), _ptr(dC), _ptr(dD), _ptr(dbias)
     if DETERMINISTIC:
         nbytes = int(N.lib().cm_selective_scan_bwd_workspace_bytes(ct.byref(a)))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)          # caching allocator: 16-byte aligned
+        if bufs is not None and bufs.get("workspace") is not None:
+            ws = _out_rows(bufs["workspace"], (nbytes // 4,), torch.float32, dev, "selective_scan_bwd: bufs['workspace']")
+        else:
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)      # caching allocator: 16-byte aligned
         a.workspace, a.workspace_bytes = _ptr(ws), nbytes
     _launch("cm_selective_scan_bwd", N.lib().cm_selective_scan_bwd, a, units=b * l)
     return du, ddelta, dA, dB, dC, dD, dbias, (dz if z is not None else None), out_z
 
 
-def causal_conv1d_fwd(x, weight, bias=None, silu=True, reverse=False, out: Optional[torch.Tensor] = None):
+def causal_conv1d_fwd(x, weight, bias=None, silu=True, reverse=False, out: Optional[torch.Tensor] = None, bufs=None):
     """x (batch, dim, seqlen), weight (dim, width) -> y.  causal_conv1d_cuda.causal_conv1d_fwd
-    (selective_scan_interface.py:182) with seq_idx=None."""
+    (selective_scan_interface.py:182) with seq_idx=None.
+    ``bufs``: caller-supplied ``y`` (a time-contiguous (batch, dim, seqlen) view of x's dtype; what ``out`` stands for)."""
     _dev_check(x, weight, bias)
     x = _time_contig(x)
     w, bs = _f32c(weight), _f32c(bias)
     b, d, l = x.shape
+    if bufs is not None:
+        _bufs(bufs, ("y",), "causal_conv1d_fwd")
+        if out is not None and bufs.get("y") is not None:
+            raise RuntimeError("causal_conv1d_fwd: bufs['y'] and out name the same output")
+        out = _time_view(out if bufs.get("y") is None else bufs["y"], (b, d, l), x.dtype, x.device, "causal_conv1d_fwd: bufs['y']")
     y = out if out is not None else torch.empty((b, d, l), dtype=x.dtype, device=x.device)
     a = N.ConvArgs()
     a.batch, a.dim, a.seqlen, a.width = b, d, l, w.shape[1]
@@ -381,19 +438,30 @@ def causal_conv1d_fwd(x, weight, bias=None, silu=True, reverse=False, out: Optio
     return y
 
 
-def causal_conv1d_bwd(x, weight, bias, dy, silu=True, reverse=False, dx: Optional[torch.Tensor] = None):
+def causal_conv1d_bwd(x, weight, bias, dy, silu=True, reverse=False, dx: Optional[torch.Tensor] = None, bufs=None):
     """-> (dx, dweight (dim, width) fp32, dbias (dim) fp32 or None); dx may be a pre-allocated view
-    (selective_scan_interface.py:286-288)."""
+    (selective_scan_interface.py:286-288).
+    ``bufs``: caller-supplied ``dx`` (a time-contiguous view, what the keyword stands for), ``dweight`` / ``dbias`` (contiguous fp32,
+    ACCUMULATED into, not zeroed) and ``workspace`` (batch * dim * (width + 1) floats; the deterministic path only)."""
     _dev_check(x, weight, bias, dy, dx)
     x, dy = _time_contig(x), _time_contig(dy)
     w, bs = _f32c(weight), _f32c(bias)
     b, d, l = x.shape
+    if bufs is not None:
+        what = "causal_conv1d_bwd"
+        _bufs(bufs, ("dx", "dweight", "dbias", "workspace"), what)
+        if dx is not None and bufs.get("dx") is not None:
+            raise RuntimeError(f"{what}: bufs['dx'] and dx name the same output")
+        for name, made in (("dbias", bias is not None), ("workspace", DETERMINISTIC)):
+            if bufs.get(name) is not None and not made:
+                raise RuntimeError(f"{what}: bufs[{name!r}] places a buffer this call does not use")
+        dx = _time_view(dx if bufs.get("dx") is None else bufs["dx"], (b, d, l), x.dtype, x.device, f"{what}: bufs['dx']")
     if dx is None:
         dx = torch.empty((b, d, l), dtype=x.dtype, device=x.device)
     if dx.stride(-1) != 1:
         raise RuntimeError("dx must be time-contiguous")
-    dw = torch.zeros_like(w)
-    db = torch.zeros((d,), dtype=torch.float32, device=x.device) if bias is not None else None
+    dw = _accum(bufs, "dweight", tuple(w.shape), x.device, "causal_conv1d_bwd")
+    db = _accum(bufs, "dbias", (d,), x.device, "causal_conv1d_bwd") if bias is not None else None
     a = N.ConvArgs()
     a.batch, a.dim, a.seqlen, a.width = b, d, l, w.shape[1]
     a.io_dtype, a.silu, a.reverse_time = _DT[x.dtype], int(bool(silu)), int(bool(reverse))
@@ -403,7 +471,8 @@ def causal_conv1d_bwd(x, weight, bias, dy, silu=True, reverse=False, dx: Optiona
     a.dy_bs, a.dy_ds, a.dx_bs, a.dx_ds = dy.stride(0), dy.stride(1), dx.stride(0), dx.stride(1)
     a.stream = _stream()
     if DETERMINISTIC:
-        ws = torch.empty((b * d * (w.shape[1] + 1),), dtype=torch.float32, device=x.device)
+        ws = _out_rows(None if bufs is None else bufs.get("workspace"), (b * d * (w.shape[1] + 1),), torch.float32, x.device,
+                       "causal_conv1d_bwd: bufs['workspace']")
         a.workspace = _ptr(ws)
     _launch("cm_causal_conv1d_bwd", N.lib().cm_causal_conv1d_bwd, a, units=b * l)
     return dx, dw, db

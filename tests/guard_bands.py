@@ -8,6 +8,10 @@ Geometry.  A 3-D (batch, seqlen, width) view of a (batch + 2, seqlen + rows, lef
 columns beside every row, ``rows`` guard rows behind every utterance, one whole guard utterance in front of the batch and one behind.
 A 2-D (rows, width) tensor given guard columns (left or right > 0) is a column slice of a wider matrix: the same geometry with batch 1,
 indexed [0] -- ``rows`` guard rows behind, a whole guard block in front and behind, guard columns beside every row.
+transposed=True: the operator route's production layout -- a 3-D (batch, dim, time) view of (dim, batch, time) storage, buffer
+(rows + dim + rows, batch + 2, left + time + right): the view's batch stride is one padded row and its channel stride a whole padded
+batch, ``left`` / ``right`` guard columns lie in time beside every row, a whole guard utterance stands in front of and behind every
+channel's batch, and ``rows`` whole guard channels stand in front of and behind the tensor.
 Everything else (2-D (rows, D) tensors the kernels want contiguous; 3-D with contiguous=True; any other rank) stays contiguous: a flat
 buffer with ``rows`` x shape[-1] guard elements in front and behind.
 
@@ -25,16 +29,21 @@ import math
 import torch
 
 SENTINEL = -65536.0            # exact in bf16 (-2^16); the cases' results stay far from it (assert_far_from_sentinel on the reference)
+F16_SENTINEL = -32768.0        # fp16 ends at 65504: its outputs (the causal conv's) take -2^15
 INT_SENTINEL = 0xA5            # integer outputs (a stored keep mask holds 0 / 1 only)
 ROW_TILE = 64                  # rows per workgroup of the row kernels (cm_ffn_fused, cm_ln_pw_glu, cm_gemm_bf16, cm_add_layernorm)
 TIME_TILE = 32                 # time steps per workgroup of the time-tiled kernels (conv_xproj, scan, dwconv rows)
 LEFT, RIGHT = 8, 16            # guard columns: 16 / 32 bytes in bf16, 32 / 64 in fp32 -- views stay 16-byte aligned
 
 
-def _geometry(shape, rows, left, right, contiguous):
+def _geometry(shape, rows, left, right, contiguous, transposed=False):
     """-> (buffer shape, function buffer -> view)."""
     shape = tuple(int(s) for s in shape)
     assert len(shape) >= 1 and all(s > 0 for s in shape) and rows >= 0 and left >= 0 and right >= 0, (shape, rows, left, right)
+    if transposed:
+        assert len(shape) == 3 and not contiguous, "transposed: a (batch, dim, time) view of (dim, batch, time) storage"
+        b, d, l = shape
+        return (rows + d + rows, b + 2, left + l + right), lambda buf: buf[rows:rows + d, 1:b + 1, left:left + l].transpose(0, 1)
     if len(shape) == 3 and not contiguous:
         b, l, w = shape
         return (b + 2, l + rows, left + w + right), lambda buf: buf[1:b + 1, :l, left:left + w]
@@ -47,13 +56,15 @@ def _geometry(shape, rows, left, right, contiguous):
 
 
 def sentinel_of(dtype):
+    if dtype == torch.float16:
+        return F16_SENTINEL
     return SENTINEL if dtype.is_floating_point else INT_SENTINEL
 
 
-def guarded(shape, dtype, device, rows=ROW_TILE, left=0, right=0, contiguous=False, align=16):
+def guarded(shape, dtype, device, rows=ROW_TILE, left=0, right=0, contiguous=False, align=16, transposed=False):
     """-> (sentinel-filled buffer, its view of ``shape``, bool mask of the buffer's elements outside the view).  ``align``: the byte
     alignment the view's start must keep (16: what the vector loads of most kernels need; odd widths keep less)."""
-    bshape, view_of = _geometry(shape, rows, left, right, contiguous)
+    bshape, view_of = _geometry(shape, rows, left, right, contiguous, transposed)
     buf = torch.full(bshape, sentinel_of(dtype), dtype=dtype, device=device)
     assert float(buf.reshape(-1)[0]) == sentinel_of(dtype), f"{sentinel_of(dtype)} is not exact in {dtype}"
     outside = torch.ones(bshape, dtype=torch.bool, device=device)
@@ -63,10 +74,10 @@ def guarded(shape, dtype, device, rows=ROW_TILE, left=0, right=0, contiguous=Fal
     return buf, view, outside
 
 
-def poisoned(t, rows=ROW_TILE, left=0, right=0, contiguous=False, align=16):
+def poisoned(t, rows=ROW_TILE, left=0, right=0, contiguous=False, align=16, transposed=False):
     """t's values in a view of guarded()'s geometry inside a NaN-filled buffer."""
     assert t.is_floating_point()
-    bshape, view_of = _geometry(t.shape, rows, left, right, contiguous)
+    bshape, view_of = _geometry(t.shape, rows, left, right, contiguous, transposed)
     buf = torch.full(bshape, float("nan"), dtype=t.dtype, device=t.device)
     view = view_of(buf)
     view.copy_(t)
@@ -120,7 +131,8 @@ def assert_far_from_sentinel(ref, name):
         return
     r = ref.detach().double()
     assert bool(torch.isfinite(r).all()), f"{name}: reference not finite"
-    assert float(r.abs().max()) < 0.5 * abs(SENTINEL), f"{name}: reference reaches {float(r.abs().max()):.3e}, too near the sentinel {SENTINEL}"
+    s = sentinel_of(ref.dtype)
+    assert float(r.abs().max()) < 0.5 * abs(s), f"{name}: reference reaches {float(r.abs().max()):.3e}, too near the sentinel {s}"
 
 
 class Guards:
@@ -185,10 +197,39 @@ class Launch:
             v[..., dead[0]:dead[1]] = float("nan")
         return v
 
+    @staticmethod
+    def _chan_align(l, itemsize, shift):
+        """Rows of l + LEFT + RIGHT elements start 16-byte aligned only when that is whole 16-byte vectors and nothing shifts them."""
+        return 16 if shift == 0 and ((l + LEFT + RIGHT) * itemsize) % 16 == 0 else itemsize
+
+    def _plain_chan(self, shape, dtype, shift):
+        b, d, l = shape
+        flat = torch.zeros((d * b * l + shift,), dtype=dtype, device=self.device)
+        return flat[shift:].view(d, b, l).transpose(0, 1)
+
+    def chan(self, t, rows=1, shift=0):
+        """A (batch, dim, time) input as a view of (dim, batch, time) storage inside NaN time columns / utterances / ``rows`` channels;
+        plain: the same layout without the guards.  ``shift`` elements move the view off its 16-byte alignment in both."""
+        if t is None:
+            return None
+        if self.guard:
+            return poisoned(t, rows=rows, left=LEFT + shift, right=RIGHT - shift, align=self._chan_align(t.shape[-1], t.element_size(), shift), transposed=True)
+        v = self._plain_chan(t.shape, t.dtype, shift)
+        v.copy_(t)
+        return v
+
     def out(self, name, shape, dtype, fill=None, **kw):
         """An output: zeros (plain) or a sentinel-guarded view; ``fill``: initial content of both (an aliased input, or 0 where the
         kernel need not write every element)."""
-        t = self.g.out(name, shape, dtype, **kw) if self.guard else torch.zeros(shape, dtype=dtype, device=self.device)
+        shift = kw.pop("shift", 0)                    # transposed outputs only: as chan()
+        if kw.get("transposed"):
+            kw.update(left=LEFT + shift, right=RIGHT - shift, align=self._chan_align(shape[-1], torch.empty((), dtype=dtype).element_size(), shift))
+        if self.guard:
+            t = self.g.out(name, shape, dtype, **kw)
+        elif kw.get("transposed"):
+            t = self._plain_chan(shape, dtype, shift)
+        else:
+            t = torch.zeros(shape, dtype=dtype, device=self.device)
         if fill is not None:
             t.copy_(fill) if torch.is_tensor(fill) else t.fill_(fill)
         self.outs[name] = t

@@ -302,3 +302,72 @@ def test_two_dim_column_slices(dtype):
         make(**fault)(faulty)
         with pytest.raises(AssertionError, match=rf"dw: {count} of 384 element\(s\) not finite"):
             faulty.g.check(outs)
+
+
+# the operator route's (dim, batch, time) storage ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("shift", [0, 1])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_transposed_geometry(dtype, shift):
+    """(batch, dim, time) view of (dim, batch, time) storage: batch stride = one padded row, channel stride = a padded batch; guard
+    columns in time, a guard utterance around every channel's batch, whole guard channels around the tensor.  ``shift`` moves the
+    view off its 16-byte alignment, in the plain launch's tensor too."""
+    b, d, l, rows = 2, 3, 8, 2
+    lp = l + G.LEFT + G.RIGHT
+    L = G.Launch(True, CPU)
+    view = L.out("du", (b, d, l), dtype, transposed=True, rows=rows, shift=shift)
+    buf, _, outside = L.g.items["du"]
+    assert buf.shape == (rows + d + rows, b + 2, lp) and view.shape == (b, d, l) and view.stride() == (lp, (b + 2) * lp, 1)
+    assert (view.data_ptr() % 16 == 0) == (shift == 0)
+    inside = torch.zeros_like(outside)
+    inside[rows:rows + d, 1:b + 1, G.LEFT + shift:G.LEFT + shift + l] = True
+    assert torch.equal(outside, ~inside)
+    t = torch.randn(b, d, l).to(dtype)
+    p = L.chan(t, rows=rows, shift=shift)
+    assert torch.equal(p, t) and p.stride() == view.stride() and p.storage_offset() == view.storage_offset()
+    around = _reach(p, (b + 2, d + 2, l + 2), -p.stride(1) - p.stride(0) - 1).clone()   # one utterance, channel and step on every side
+    around[1:b + 1, 1:d + 1, 1:l + 1] = float("nan")
+    assert bool(torch.isnan(around).all())
+    P = G.Launch(False, CPU)
+    q, o = P.chan(t, rows=rows, shift=shift), P.out("du", (b, d, l), dtype, transposed=True, rows=rows, shift=shift)
+    assert torch.equal(q, t) and q.stride() == (l, b * l, 1) == o.stride() and (q.data_ptr() % 16 == 0) == (shift == 0) == (o.data_ptr() % 16 == 0)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_transposed_kernels(dtype):
+    """In (dim, batch, time) storage the element behind a row's end is the NEXT UTTERANCE's first step of the same channel: a kernel
+    that reads or writes one step too many is flagged; the correct one passes."""
+    t = torch.randn(2, 3, 8).to(dtype)
+    want = 2 * t
+
+    def correct(inp, out):
+        out.copy_(2 * inp)
+
+    def one_step_past(inp, out):                       # every row one step longer, input and output
+        b, d, l = inp.shape
+        _reach(out, (b, d, l + 1)).copy_(2 * _reach(inp, (b, d, l + 1)))
+
+    def reads_past(inp, out):                          # the last step takes the value behind the row's end
+        b, d, l = inp.shape
+        out.copy_(2 * inp)
+        out[:, :, -1] += 0 * _reach(inp, (b, d, l + 1))[:, :, -1]
+
+    L = G.Launch(True, CPU)
+    correct(L.chan(t), L.out("ddelta", t.shape, dtype, transposed=True, rows=1))
+    L.g.check({"ddelta": want})
+    L = G.Launch(True, CPU)
+    one_step_past(L.chan(t), L.out("ddelta", t.shape, dtype, transposed=True, rows=1))
+    with pytest.raises(AssertionError, match=r"ddelta: 6 element\(s\) written outside the view"):
+        L.g.check({"ddelta": want})
+    L = G.Launch(True, CPU)
+    reads_past(L.chan(t), L.out("ddelta", t.shape, dtype, transposed=True, rows=1))
+    with pytest.raises(AssertionError, match=r"ddelta: 6 of 48 element\(s\) not finite"):
+        L.g.check({"ddelta": want})
+
+
+def test_fp16_outputs_take_a_sentinel_fp16_holds():
+    buf, view, outside = G.guarded((2, 3, 8), torch.float16, CPU, rows=1, left=G.LEFT, right=G.RIGHT, transposed=True)
+    assert G.sentinel_of(torch.float16) == G.F16_SENTINEL and bool((buf == G.F16_SENTINEL).all())
+    G.assert_untouched(buf, outside, "fresh")
+    G.assert_far_from_sentinel(torch.full((2,), 16000.0, dtype=torch.float16), "y")
+    with pytest.raises(AssertionError, match="too near the sentinel"):
+        G.assert_far_from_sentinel(torch.full((2,), 17000.0, dtype=torch.float16), "y")
