@@ -470,6 +470,58 @@ typedef struct cm_ctc_beam_args {
 int64_t cm_ctc_beam_workspace_bytes(const cm_ctc_beam_args *args);
 int cm_ctc_beam_search(const cm_ctc_beam_args *args);
 
+/* CTC beam search with a backoff n-gram LM fused into the frame loop (csrc/ctc_beam_lm.hip; speechbrain's CTCBeamSearcher with
+ * kenlm_model_path; contract: mamba_asr_amd/ctc_decode.py).  Everything cm_ctc_beam_search takes, with the same
+ * meaning, plus the packed LM (mamba_asr_amd/ngram_lm.py builds it from an ARPA file) and tok_len[v], the code points of token v's
+ * clean piece.  Steps 1 - 3 of the frame (select, extend, merge) act on the acoustic score; prune, rank and the beam_size cut act
+ * on total = acoustic + LM(text) + partial_score(partial word).
+ * Tables, all open addressing with linear probing from lm slot(key) & (cap - 1), caps powers of two, empty key = all ones:
+ *   word table    word_keys (word_cap, 2) = the two 61-bit hashes H_k(word) (as tok_hash), word_ids (word_cap) -> word id < n_words;
+ *   prefix set    prefix_keys (prefix_cap, 2): the hashes of every non-empty prefix of every unigram-list word;
+ *   n-gram table  ngram_keys (ngram_cap) = (entry of the context as an n-gram << 32) | word id, ngram_vals -> entry < n_entries.
+ * lm_prob / lm_backoff (n_entries) hold log10 p and the backoff weight (0 when the file has none) of every entry; the unigram of
+ * word id w is entry w.  slot(key) = mix(key) for the n-gram table and mix(h0 * 0x9E3779B97F4A7C15 + h1) for the hash pairs, mix
+ * being the splitmix64 finaliser.  A beam's LM state is the entries of its last 1 .. order-1 words (-1: not stored).
+ * lm_bos: word id that starts every context (<s> when the boundary is scored and listed), lm_eos: word id scored at the finish
+ * without beta (</s>, likewise), lm_unk: word id of <unk>; each -1 when absent.  word_score = alpha ln(10) lw + beta.
+ * Outputs as cm_ctc_beam_search: scores = the acoustic score of each hypothesis, lm_scores = its total, by which they are ranked.
+ * Every probe loop is bounded by its table's capacity and every id read from a table is range-checked, so a damaged table gives
+ * wrong scores but neither spins nor reads out of bounds.  Arguments are validated on the host before any launch. */
+typedef struct cm_ctc_beam_lm_args {
+    int32_t batch, T, V, dtype;               /* dtype: CM_F32 or CM_BF16; V <= 4096                           */
+    int64_t lp_bs, lp_ts;                     /* log_probs element strides of batch and time                    */
+    const void *log_probs;
+    const int32_t *lengths;                   /* (batch) frames to decode                                       */
+    const int32_t *tok_class;                 /* (V)                                                            */
+    const uint64_t *tok_hash, *tok_pow;       /* (V, 2)                                                         */
+    const int32_t *tok_len;                   /* (V) code points of the clean piece                             */
+    uint64_t hash_base[2], hash_sep;
+    int32_t blank, beam_size, topk, prune_history;   /* beam_size <= 256                                        */
+    double beam_prune_logp, token_prune_min_logp, blank_skip_threshold;
+    double blank_skip_log;                    /* set by the library                                             */
+    int32_t order, n_words;                   /* order in [1, 5]                                                */
+    int32_t lm_bos, lm_eos, lm_unk, reserved0;
+    int64_t n_entries, word_cap, prefix_cap, ngram_cap;
+    const uint64_t *word_keys;                /* (word_cap, 2)                                                  */
+    const int32_t *word_ids;                  /* (word_cap)                                                     */
+    const uint64_t *prefix_keys;              /* (prefix_cap, 2)                                                */
+    const uint64_t *ngram_keys;               /* (ngram_cap)                                                    */
+    const int32_t *ngram_vals;                /* (ngram_cap)                                                    */
+    const float *lm_prob, *lm_backoff;        /* (n_entries)                                                    */
+    double alpha, beta, unk_score_offset;     /* finite                                                         */
+    double alpha_ln10;                        /* set by the library                                             */
+    int32_t *tokens;                          /* (batch, topk, T)                                               */
+    int32_t *token_len;                       /* (batch, topk)                                                  */
+    double *scores, *lm_scores;               /* (batch, topk)                                                  */
+    int32_t *num_hyps, *bad_frame;            /* (batch)                                                        */
+    void *workspace;                          /* cm_ctc_beam_lm_workspace_bytes() bytes                         */
+    int64_t workspace_bytes;
+    void *stream;
+} cm_ctc_beam_lm_args;
+
+int64_t cm_ctc_beam_lm_workspace_bytes(const cm_ctc_beam_lm_args *args);
+int cm_ctc_beam_lm_search(const cm_ctc_beam_lm_args *args);
+
 /* The same search carried across streaming chunks (csrc/ctc_beam_stream.hip): one call consumes the next chunk of
  * every stream of a batch from a caller-owned state and runs the frame body of cm_ctc_beam_search on it (csrc/ctc_beam_impl.h,
  * shared), so after n frames in any chunking the hypotheses carry the bits cm_ctc_beam_search returns for lengths = n.

@@ -1,0 +1,193 @@
+// ctc_beam_lm_impl.h — what the LM-fused CTC beam search (ctc_beam_lm.hip, cm_ctc_beam_lm_search) adds to ctc_beam_impl.h: the
+// per-beam LM state in LDS, the table probes, ARPA backoff, the word and partial-word scores, and merge_rank_lm, the merge_rank
+// that folds acoustic scores but prunes and ranks by a total the caller derives from each run head.  Contract: DESIGN.md §4p.
+// Probes read global memory from a few divergent lanes; each loop runs at most `capacity` steps and every id a table returns is
+// range-checked before it indexes anything.
+#pragma once
+#include "ctc_beam_impl.h"
+
+namespace {
+
+constexpr int LM_ORDER_MAX = 5, LM_CTX = LM_ORDER_MAX - 1;
+constexpr uint64_t LM_EMPTY = ~0ull;
+
+// one beam's LM state (struct-of-arrays in LDS, double-buffered like Beams, whose score holds the acoustic score here): 18 KB
+struct LmBeams {
+    double lm[2][KMAX];                // LM(text): the sum of word_score over the completed words, in word order
+    double ps[2][KMAX];                // partial_score(partial word)
+    int32_t ctx[2][LM_CTX][KMAX];      // ctx[k - 1]: entry of the last k words as a k-gram, -1 when not stored
+    int32_t plen[2][KMAX];             // code points of the partial word
+};
+
+struct LmState {
+    double lm, ps;
+    int32_t ctx[LM_CTX];
+    int32_t plen;
+};
+
+__device__ __forceinline__ LmState lm_load(const LmBeams &lb, int buf, int r) {
+    LmState s;
+    s.lm = lb.lm[buf][r]; s.ps = lb.ps[buf][r]; s.plen = lb.plen[buf][r];
+#pragma unroll
+    for (int k = 0; k < LM_CTX; ++k) s.ctx[k] = lb.ctx[buf][k][r];
+    return s;
+}
+
+__device__ __forceinline__ void lm_store(LmBeams &lb, int buf, int r, const LmState &s) {
+    lb.lm[buf][r] = s.lm; lb.ps[buf][r] = s.ps; lb.plen[buf][r] = s.plen;
+#pragma unroll
+    for (int k = 0; k < LM_CTX; ++k) lb.ctx[buf][k][r] = s.ctx[k];
+}
+
+// splitmix64 finaliser; the host packs with the same function (mamba_asr_amd/ngram_lm.py)
+__device__ __forceinline__ uint64_t lm_mix(uint64_t x) {
+    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27; x *= 0x94d049bb133111ebull;
+    x ^= x >> 31;
+    return x;
+}
+
+// position of the hash pair (h0, h1) in an open-addressing table of cap slots (keys (cap, 2)), -1 when absent
+__device__ __forceinline__ int64_t lm_find_pair(const uint64_t *keys, int64_t cap, uint64_t h0, uint64_t h1) {
+    const uint64_t mask = (uint64_t)cap - 1;
+    uint64_t s = lm_mix(h0 * 0x9E3779B97F4A7C15ull + h1) & mask;
+    for (int64_t n = 0; n < cap; ++n, s = (s + 1) & mask) {
+        const uint64_t k0 = keys[2 * s];
+        if (k0 == LM_EMPTY) return -1;
+        if (k0 == h0 && keys[2 * s + 1] == h1) return (int64_t)s;
+    }
+    return -1;
+}
+
+template <class P> __device__ __forceinline__ int lm_word(const P &p, uint64_t h0, uint64_t h1) {
+    const int64_t s = lm_find_pair(p.word_keys, p.word_cap, h0, h1);
+    if (s < 0) return -1;
+    const int id = p.word_ids[s];
+    return id >= 0 && id < p.n_words ? id : -1;
+}
+
+// entry of the n-gram (context entry ctx, word w), -1 when not stored
+template <class P> __device__ __forceinline__ int lm_ngram(const P &p, int ctx, int w) {
+    const uint64_t key = ((uint64_t)(uint32_t)ctx << 32) | (uint32_t)w, mask = (uint64_t)p.ngram_cap - 1;
+    uint64_t s = lm_mix(key) & mask;
+    for (int64_t n = 0; n < p.ngram_cap; ++n, s = (s + 1) & mask) {
+        const uint64_t k = p.ngram_keys[s];
+        if (k == LM_EMPTY) return -1;
+        if (k == key) {
+            const int e = p.ngram_vals[s];
+            return e >= 0 && e < p.n_entries ? e : -1;
+        }
+    }
+    return -1;
+}
+
+// log10 p(w | ctx) by ARPA backoff for the word id w, and the context after w.  e[k] is the entry of (last k words, w): the
+// longest stored one gives the probability, every longer context adds its backoff when it is stored.  The probes are independent.
+template <class P> __device__ __forceinline__ double lm_cond(const P &p, const int32_t ctx[LM_CTX], int w, int32_t next[LM_CTX]) {
+    int32_t e[LM_ORDER_MAX];
+    e[0] = w;
+#pragma unroll
+    for (int k = 1; k < LM_ORDER_MAX; ++k) e[k] = (k < p.order && ctx[k - 1] >= 0) ? lm_ngram(p, ctx[k - 1], w) : -1;
+    int hit = 0;
+#pragma unroll
+    for (int k = 1; k < LM_ORDER_MAX; ++k) hit = e[k] >= 0 ? k : hit;
+    int32_t eh = e[0];
+#pragma unroll
+    for (int k = 1; k < LM_ORDER_MAX; ++k) eh = hit == k ? e[k] : eh;
+    double lw = (double)p.lm_prob[eh];
+#pragma unroll
+    for (int j = 1; j < LM_ORDER_MAX; ++j)
+        if (j > hit && j < p.order && ctx[j - 1] >= 0) lw += (double)p.lm_backoff[ctx[j - 1]];
+#pragma unroll
+    for (int k = 0; k < LM_CTX; ++k) next[k] = k + 1 < p.order ? e[k] : -1;
+    return lw;
+}
+
+// the word with hashes (h0, h1) is completed: LM(text) grows by its word_score, the context moves on
+template <class P> __device__ __forceinline__ void lm_commit(const P &p, LmState &s, uint64_t h0, uint64_t h1) {
+    const int w = lm_word(p, h0, h1);
+    int32_t next[LM_CTX];
+    double lw;
+    if (w >= 0) {
+        lw = lm_cond(p, s.ctx, w, next);
+    } else if (p.lm_unk >= 0) {
+        lw = lm_cond(p, s.ctx, p.lm_unk, next) + p.unk_score_offset;
+    } else {
+        lw = p.unk_score_offset;
+#pragma unroll
+        for (int k = 0; k < LM_CTX; ++k) next[k] = -1;
+    }
+    s.lm += p.alpha_ln10 * lw + p.beta;
+#pragma unroll
+    for (int k = 0; k < LM_CTX; ++k) s.ctx[k] = next[k];
+}
+
+// the LM state of beam state `par` (LM state l) after the text-changing token v of class cls gave the beam state `now`
+template <class P> __device__ __forceinline__ LmState lm_extend(const P &p, LmState l, const State &par, const State &now, int v, int cls) {
+    if (cls == 1) {
+        if (!(par.flags & F_PART_EMPTY)) lm_commit(p, l, par.hp[0], par.hp[1]);
+        l.plen = p.tok_len[v];
+    } else {
+        l.plen += p.tok_len[v];
+    }
+    if ((now.flags & F_PART_EMPTY) || lm_find_pair(p.prefix_keys, p.prefix_cap, now.hp[0], now.hp[1]) >= 0) l.ps = 0.0;
+    else l.ps = p.alpha_ln10 * p.unk_score_offset * fmax(1.0, (double)l.plen / 6.0);
+    return l;
+}
+
+// the single initial beam's LM state into slot 0 of buffer buf (one thread calls it)
+template <class P> __device__ __forceinline__ void lm_store_initial(const P &p, LmBeams &lb, int buf) {
+    LmState s;
+    s.lm = s.ps = 0.0;
+    s.plen = 0;
+#pragma unroll
+    for (int k = 0; k < LM_CTX; ++k) s.ctx[k] = -1;
+    if (p.order >= 2) s.ctx[0] = p.lm_bos;
+    lm_store(lb, buf, 0, s);
+}
+
+// merge_rank with a total: runs of equal keys fold their acoustic scores (score(idx), as merge_rank does) into b.sc at the head's
+// position, which stays there; each head then gets total(idx, folded acoustic), and prune, rank and limit act on the totals.  On
+// return positions 0 .. kept-1 hold the survivors in rank order: k1 = score_key(total), k2 = candidate index, k3 = the position
+// in b.sc of the folded acoustic score.
+template <bool G, class ScoreFn, class TotalFn>
+__device__ int merge_rank_lm(Shared &sh, const Buf b, int n, int n2, int limit, double prune, ScoreFn score, TotalFn total) {
+    const int tid = threadIdx.x;
+    bitonic<G>(b, n2);
+    for (int i = tid; i < n2; i += NT) {
+        double s = 0.0;
+        bool head = false;
+        if (i < n) {
+            const uint64_t a1 = b.k1[i], a2 = b.k2[i], a3 = b.k3[i];
+            head = i == 0 || b.k1[i - 1] != a1 || b.k2[i - 1] != a2 || (b.k3[i - 1] >> 32) != (a3 >> 32);
+            if (head) {
+                s = score((int)(uint32_t)a3);
+                for (int j = i + 1; j < n && b.k1[j] == a1 && b.k2[j] == a2 && (b.k3[j] >> 32) == (a3 >> 32); ++j)
+                    s = lae(s, score((int)(uint32_t)b.k3[j]));
+            }
+        }
+        b.sc[i] = head ? s : __builtin_nan("");
+    }
+    barrier<G>();
+    for (int i = tid; i < n2; i += NT) {
+        const double s = b.sc[i];
+        const bool alive = s == s;
+        const uint64_t idx = (uint32_t)b.k3[i];
+        b.k1[i] = alive ? score_key(total((int)idx, s)) : KEY_MAX;
+        b.k2[i] = alive ? idx : KEY_MAX;
+        b.k3[i] = (uint64_t)i;
+    }
+    barrier<G>();
+    bitonic<G>(b, n2);
+    const double thr = key_score(b.k1[0]) + prune;
+    if (tid == 0) sh.nkeep = 0;
+    barrier<G>();
+    for (int i = tid; i < n2; i += NT) {
+        auto ok = [&](int x) { return x < n2 && b.k1[x] != KEY_MAX && key_score(b.k1[x]) >= thr; };
+        if (ok(i) && !ok(i + 1)) sh.nkeep = i + 1;        // the single boundary of a monotone predicate: one writer
+    }
+    barrier<G>();
+    return min(sh.nkeep, limit);
+}
+
+}  // namespace

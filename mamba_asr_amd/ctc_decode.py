@@ -1,4 +1,4 @@
-"""LM-free CTC beam search on the GPU: the drop-in for speechbrain.decoders.ctc.CTCBeamSearcher in the CTC recipe's TEST stage
+"""CTC beam search on the GPU, LM-free or with a fused n-gram LM: the drop-in for speechbrain.decoders.ctc.CTCBeamSearcher in the CTC recipe's TEST stage
 (reference train_CTC.py:1155-1161 builds it from hparams/CTC/conmamba_large.yaml:232-237; compute_forward calls it at :309-310;
 compute_objectives reads hyp[0].text at :411-414).  The search itself is the HIP kernel behind ops.ctc_beam_search
 (csrc/ctc_beam.hip); this module classifies the vocabulary once, maps relative lengths to frame counts and composes texts.
@@ -34,9 +34,41 @@ Streaming.  StreamingCTCBeamSearcher carries the same search across chunks (ops.
 beams and the backtracking history live in a device slab per stream, a step is one launch that reads nothing back, and
 hypotheses() after n frames is by definition what the search above returns for n_b = n -- the kernels share the frame body, so the
 score bits agree as well.
+
+N-gram LM fusion (kenlm_model_path; ops.ctc_beam_search_lm, csrc/ctc_beam_lm.hip, tables by ngram_lm.NgramLM).
+kenlm, pyctcdecode and speechbrain cannot be installed here, so parity with them is not pinned: these rules are the contract.
+
+Model.  A backoff n-gram LM in ARPA text format, plain or .gz, of order 1 to 5; log10 probabilities and backoffs are stored as
+fp32, a missing backoff column means 0; <s>, </s> and <unk> are optional.  A kenlm binary file or a malformed ARPA file raises
+ValueError naming the path and the line.  (Choices: an n-gram whose context is not listed as an (n-1)-gram, a duplicate n-gram,
+a count that differs from the header and a non-finite number are malformed.)
+
+Conditional probability.  log10 p(w | c) is plain ARPA backoff over the last order-1 words of c: the longest stored n-gram gives
+the probability, every context that had to be dropped contributes its backoff if it is stored.  (Choice: the fp32 values are
+summed in float64, probability first, then the backoffs from the shortest dropped context to the longest.)
+
+Word score.  A completed word w after the beam's completed words c (preceded by <s> when score_boundary is set and the LM lists
+<s>): lw = log10 p(w|c) when w is in the LM vocabulary (the 1-grams); otherwise lw = log10 p(<unk>|c) + unk_score_offset, the
+p(<unk>|c) term being 0 when the LM lists no <unk>, and the context continues with <unk> (no <unk>: the context is emptied, <s>
+included).  word_score = alpha * ln(10) * lw + beta.  LM(text) is the float64 sum of word_score over the words of text, in order.
+
+Partial-word score.  partial_score(p) = 0 if p is empty or a prefix of, or equal to, some word of the unigram list (unigrams=
+when given, else the ARPA 1-grams minus the three specials); otherwise alpha * ln(10) * unk_score_offset * max(1, len(p) / 6),
+len in code points.
+
+Per frame.  Steps 1 to 3 above are unchanged and act on the acoustic score alone (equal keys have equal LM state by
+construction, so the merge folds acoustic scores).  Then every merged candidate gets total = acoustic + LM(text) +
+partial_score(partial); steps 4 and 5 act on total, ties to the earliest candidate; step 6 is unchanged.
+
+Finish.  Commit the partial as a word, scored as above; merge by text, folding the acoustic score; total = acoustic + LM(text),
+plus alpha * ln(10) * log10 p(</s> | text) when score_boundary is set and the LM lists </s> (no beta for it); prune and rank by
+total; return CTCHypothesis(text, None, score=acoustic, lm_score=total, None).  n_b = 0 or T = 0 gives one hypothesis with
+text "", score 0.0 and lm_score = LM("") by the same rules (the </s> term alone).  Without kenlm_model_path the LM keywords are
+inert.  The streamed searcher does not carry LM state: it refuses a path.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -89,8 +121,6 @@ class CTCBeamSearcher:
                  beta: float = 1.5, unk_score_offset: float = -10.0, score_boundary: bool = True, beam_size: int = 100,
                  beam_prune_logp: float = -10.0, token_prune_min_logp: float = -5.0, prune_history: bool = True,
                  blank_skip_threshold: float = 1.0, topk: int = 1):
-        if kenlm_model_path is not None:
-            raise NotImplementedError("CTCBeamSearcher: language-model fusion (kenlm_model_path) is not supported")
         vocab = list(vocab_list)
         if len(set(vocab)) != len(vocab):
             dup = sorted({p for p in vocab if vocab.count(p) > 1})
@@ -125,7 +155,21 @@ class CTCBeamSearcher:
         self.tok_class = torch.tensor([1 if c == WORD_START else 0 for c in self.classes], dtype=torch.int32)
         self.tok_hash = torch.tensor([h for h, _ in hashes], dtype=torch.int64)
         self.tok_pow = torch.tensor([p for _, p in hashes], dtype=torch.int64)
+        self.tok_len = torch.tensor([len(c) for c in self.clean], dtype=torch.int32)
         self._dev_tables = {}
+        self.lm = None
+        if kenlm_model_path is not None:
+            from .ngram_lm import NgramLM
+            if WORD_START not in self.classes:
+                raise NotImplementedError("CTCBeamSearcher: language-model fusion (kenlm_model_path) needs a vocabulary with a "
+                                          "word-start piece (a piece starting with spm_token, or space_token): without one no word "
+                                          "ever completes and a word-level n-gram LM has nothing to score")
+            for name, x in (("alpha", alpha), ("beta", beta), ("unk_score_offset", unk_score_offset)):
+                if not math.isfinite(float(x)):
+                    raise ValueError(f"CTCBeamSearcher: {name} must be finite, got {x}")
+            self.lm = NgramLM.from_arpa(kenlm_model_path, unigrams=unigrams)
+            self.alpha, self.beta, self.unk_score_offset = float(alpha), float(beta), float(unk_score_offset)
+            self.score_boundary = bool(score_boundary)
 
     def compose(self, tokens: Sequence[int]) -> str:
         """Text of a sequence of text-changing tokens, by the class rules."""
@@ -141,6 +185,12 @@ class CTCBeamSearcher:
         key = str(device)
         if key not in self._dev_tables:
             self._dev_tables[key] = tuple(t.to(device) for t in (self.tok_class, self.tok_hash, self.tok_pow))
+        return self._dev_tables[key]
+
+    def _tok_len(self, device):
+        key = (str(device), "tok_len")
+        if key not in self._dev_tables:
+            self._dev_tables[key] = self.tok_len.to(device)
         return self._dev_tables[key]
 
     def frame_counts(self, steps: int, wav_lens: Optional[torch.Tensor], batch: int) -> List[int]:
@@ -164,22 +214,34 @@ class CTCBeamSearcher:
             if len(counts) != b or any(not 0 <= x <= steps for x in counts):
                 raise ValueError(f"CTCBeamSearcher: lengths must be {b} frame counts in [0, {steps}], got {counts}")
         if steps == 0:
-            return [[CTCHypothesis("", None, 0.0, 0.0, None)] for _ in range(b)]
+            empty = 0.0 if self.lm is None else self.lm.lm_of_text("", self.alpha, self.beta, self.unk_score_offset,
+                                                                   self.score_boundary, finish=True)
+            return [[CTCHypothesis("", None, 0.0, empty, None)] for _ in range(b)]
         lengths = torch.tensor(counts, dtype=torch.int32).to(log_probs.device)
         tc, th, tp = self._tables(log_probs.device)
+        if self.lm is not None:
+            lm, tl = self.lm, self._tok_len(log_probs.device)
+            tokens, token_len, scores, lm_scores, num_hyps, bad = ops.ctc_beam_search_lm(
+                log_probs, lengths, tc, th, tp, tl, HASH_BASE, HASH_SEP, lm.tables(log_probs.device), order=lm.order,
+                n_words=len(lm.words), lm_bos=lm.bos if self.score_boundary else -1, lm_eos=lm.eos if self.score_boundary else -1,
+                lm_unk=lm.unk, alpha=self.alpha, beta=self.beta, unk_score_offset=self.unk_score_offset, blank=self.blank_index,
+                beam_size=self.beam_size, topk=self.topk, prune_history=self.prune_history, beam_prune_logp=self.beam_prune_logp,
+                token_prune_min_logp=self.token_prune_min_logp, blank_skip_threshold=self.blank_skip_threshold)
+            return self._hypotheses(tokens, token_len, scores, num_hyps, bad, range(b), "utterance", lm_scores=lm_scores)
         tokens, token_len, scores, num_hyps, bad = ops.ctc_beam_search(
             log_probs, lengths, tc, th, tp, HASH_BASE, HASH_SEP, blank=self.blank_index, beam_size=self.beam_size,
             topk=self.topk, prune_history=self.prune_history, beam_prune_logp=self.beam_prune_logp,
             token_prune_min_logp=self.token_prune_min_logp, blank_skip_threshold=self.blank_skip_threshold)
         return self._hypotheses(tokens, token_len, scores, num_hyps, bad, range(b), "utterance")
 
-    def _hypotheses(self, tokens, token_len, scores, num_hyps, bad, rows, what) -> List[List[CTCHypothesis]]:
+    def _hypotheses(self, tokens, token_len, scores, num_hyps, bad, rows, what, lm_scores=None) -> List[List[CTCHypothesis]]:
         """The kernel's outputs of the named rows, read to the host: NaN check, then one list of hypotheses per row."""
         bad, num_hyps = bad.cpu().tolist(), num_hyps.cpu().tolist()
         for u in rows:
             if bad[u] >= 0:
                 raise ValueError(f"{type(self).__name__}: log_probs of {what} {u} hold NaN at frame {bad[u]}")
         token_len, scores = token_len.cpu().tolist(), scores.cpu().tolist()
+        lm_scores = scores if lm_scores is None else lm_scores.cpu().tolist()
         lmax = max((token_len[u][h] for u in rows for h in range(num_hyps[u])), default=0)
         tok = tokens[:, :, :lmax].cpu().tolist()
         out = []
@@ -187,7 +249,7 @@ class CTCBeamSearcher:
             hyps = []
             for h in range(num_hyps[u]):
                 s = scores[u][h]
-                hyps.append(CTCHypothesis(self.compose(tok[u][h][:token_len[u][h]]), None, s, s, None))
+                hyps.append(CTCHypothesis(self.compose(tok[u][h][:token_len[u][h]]), None, s, lm_scores[u][h], None))
             out.append(hyps)
         return out
 
@@ -227,6 +289,9 @@ class StreamingCTCBeamSearcher(CTCBeamSearcher):
     """
 
     def __init__(self, *args, max_frames: int = 1500, **kw):
+        if kw.get("kenlm_model_path") is not None or (len(args) > 4 and args[4] is not None):
+            raise NotImplementedError("StreamingCTCBeamSearcher: streamed language-model fusion (kenlm_model_path) is not provided; "
+                                      "CTCBeamSearcher fuses an n-gram LM over whole utterances")
         super().__init__(*args, **kw)
         if not 1 <= max_frames <= 0x7fff0000 // 256:
             raise ValueError(f"StreamingCTCBeamSearcher: max_frames {max_frames} not in [1, {0x7fff0000 // 256}]")

@@ -900,6 +900,69 @@ def ctc_beam_search(log_probs, lengths, tok_class, tok_hash, tok_pow, hash_base,
     return tokens, token_len, scores, num_hyps, bad_frame
 
 
+def ctc_beam_search_lm(log_probs, lengths, tok_class, tok_hash, tok_pow, tok_len, hash_base, hash_sep, lm, *, order, n_words,
+                       lm_bos=-1, lm_eos=-1, lm_unk=-1, alpha=0.5, beta=1.5, unk_score_offset=-10.0, blank=0, beam_size=100, topk=1,
+                       prune_history=False, beam_prune_logp=-10.0, token_prune_min_logp=-5.0, blank_skip_threshold=1.0):
+    """CTC beam search with a fused backoff n-gram LM (cm_ctc_beam_lm_search).  The arguments of ctc_beam_search, plus tok_len
+    (V) int32 (code points of each clean piece) and ``lm``, the dict of device tensors of ngram_lm.NgramLM.tables(): word_keys
+    (cap, 2) / prefix_keys (cap, 2) / ngram_keys (cap) int64 bit patterns, word_ids / ngram_vals int32, prob / backoff fp32; order,
+    n_words and the word ids lm_bos / lm_eos / lm_unk (-1: not used) describe it.
+    -> (tokens, token_len, scores (acoustic), lm_scores (total, the ranking score), num_hyps, bad_frame) as ctc_beam_search."""
+    names = ("word_keys", "word_ids", "prefix_keys", "ngram_keys", "ngram_vals", "prob", "backoff")
+    _dev_check(log_probs, lengths, tok_class, tok_hash, tok_pow, tok_len, *[lm[n] for n in names])
+    want = dict(word_keys=torch.int64, word_ids=torch.int32, prefix_keys=torch.int64, ngram_keys=torch.int64, ngram_vals=torch.int32,
+                prob=torch.float32, backoff=torch.float32)
+    for n in names:
+        if lm[n].dtype != want[n] or not lm[n].is_contiguous():
+            raise RuntimeError(f"ctc_beam_search_lm: lm[{n!r}] must be a contiguous {want[n]} tensor")
+    if lm["word_keys"].dim() != 2 or lm["word_keys"].shape[1] != 2 or lm["prefix_keys"].dim() != 2 or lm["prefix_keys"].shape[1] != 2:
+        raise RuntimeError("ctc_beam_search_lm: word_keys and prefix_keys must be (capacity, 2)")
+    if lm["word_ids"].numel() != lm["word_keys"].shape[0] or lm["ngram_vals"].numel() != lm["ngram_keys"].numel() \
+            or lm["backoff"].numel() != lm["prob"].numel():
+        raise RuntimeError("ctc_beam_search_lm: keys / values of a table, or prob / backoff, differ in length")
+    if log_probs.dtype not in (torch.float32, torch.bfloat16):
+        log_probs = log_probs.float()
+    lp = log_probs.detach()
+    if lp.stride(2) != 1:
+        lp = lp.contiguous()
+    b, t, v = lp.shape
+    dev = lp.device
+    ln = lengths.detach().to(device=dev, dtype=torch.int32).contiguous()
+    tc = tok_class.detach().to(device=dev, dtype=torch.int32).contiguous()
+    th = tok_hash.detach().to(device=dev, dtype=torch.int64).contiguous()
+    tp = tok_pow.detach().to(device=dev, dtype=torch.int64).contiguous()
+    tl = tok_len.detach().to(device=dev, dtype=torch.int32).contiguous()
+    if tc.numel() != v or th.numel() != 2 * v or tp.numel() != 2 * v or tl.numel() != v:
+        raise RuntimeError(f"ctc_beam_search_lm: token tables must cover the {v} tokens of log_probs")
+    tokens = torch.empty((b, topk, t), dtype=torch.int32, device=dev)
+    token_len = torch.zeros((b, topk), dtype=torch.int32, device=dev)
+    scores = torch.zeros((b, topk), dtype=torch.float64, device=dev)
+    lm_scores = torch.zeros((b, topk), dtype=torch.float64, device=dev)
+    num_hyps = torch.empty((b,), dtype=torch.int32, device=dev)
+    bad_frame = torch.empty((b,), dtype=torch.int32, device=dev)
+    a = N.CtcBeamLmArgs()
+    a.batch, a.T, a.V, a.dtype = b, t, v, _DT[lp.dtype]
+    a.lp_bs, a.lp_ts = lp.stride(0), lp.stride(1)
+    a.log_probs, a.lengths, a.tok_class, a.tok_hash, a.tok_pow, a.tok_len = _ptr(lp), _ptr(ln), _ptr(tc), _ptr(th), _ptr(tp), _ptr(tl)
+    a.hash_base[0], a.hash_base[1], a.hash_sep = int(hash_base[0]), int(hash_base[1]), int(hash_sep)
+    a.blank, a.beam_size, a.topk, a.prune_history = int(blank), int(beam_size), int(topk), int(bool(prune_history))
+    a.beam_prune_logp, a.token_prune_min_logp = float(beam_prune_logp), float(token_prune_min_logp)
+    a.blank_skip_threshold = float(blank_skip_threshold)
+    a.order, a.n_words, a.lm_bos, a.lm_eos, a.lm_unk = int(order), int(n_words), int(lm_bos), int(lm_eos), int(lm_unk)
+    a.n_entries, a.word_cap, a.prefix_cap, a.ngram_cap = (lm["prob"].numel(), lm["word_ids"].numel(), lm["prefix_keys"].shape[0],
+                                                          lm["ngram_keys"].numel())
+    a.word_keys, a.word_ids, a.prefix_keys = _ptr(lm["word_keys"]), _ptr(lm["word_ids"]), _ptr(lm["prefix_keys"])
+    a.ngram_keys, a.ngram_vals, a.lm_prob, a.lm_backoff = _ptr(lm["ngram_keys"]), _ptr(lm["ngram_vals"]), _ptr(lm["prob"]), _ptr(lm["backoff"])
+    a.alpha, a.beta, a.unk_score_offset = float(alpha), float(beta), float(unk_score_offset)
+    nws = int(N.lib().cm_ctc_beam_lm_workspace_bytes(ct.byref(a)))
+    ws = torch.empty((max(nws, 1),), dtype=torch.uint8, device=dev)
+    a.tokens, a.token_len, a.scores, a.lm_scores = _ptr(tokens), _ptr(token_len), _ptr(scores), _ptr(lm_scores)
+    a.num_hyps, a.bad_frame = _ptr(num_hyps), _ptr(bad_frame)
+    a.workspace, a.workspace_bytes, a.stream = _ptr(ws), nws, _stream()
+    _launch("cm_ctc_beam_lm_search", N.lib().cm_ctc_beam_lm_search, a, units=b * t)
+    return tokens, token_len, scores, lm_scores, num_hyps, bad_frame
+
+
 def ctc_beam_stream_state(slots, beam_size, max_frames, device):
     """The zeroed state of ``slots`` streamed CTC beam searches: (slots, cm_ctc_beam_stream_state_bytes(beam_size, max_frames)) uint8.
     An all-zero slab is a slot that was never reset; a row is plain memory, so copying it copies the stream."""
