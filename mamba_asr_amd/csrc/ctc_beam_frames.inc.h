@@ -1,12 +1,17 @@
-// ctc_beam_frames.inc.h — the frame loop of the CTC beam search as TEXT: both kernels (ctc_beam.hip, ctc_beam_stream.hip) include
-// this file in the middle of their bodies, so they run the same statements and the whole-utterance kernel compiles to the ISA it
-// had when the loop stood in it (every function boundary tried around this register-starved loop moved its time by 1 - 2 %).
+// ctc_beam_frames.inc.h — the frame loop of the CTC beam search as TEXT: the three kernels (ctc_beam.hip, ctc_beam_stream.hip,
+// ctc_beam_lm.hip) include this file in the middle of their bodies, so they run the same statements and the whole-utterance kernel
+// compiles to the ISA it had when the loop stood in it (every function boundary tried around this register-starved loop moved its
+// time by 1 - 2 %).
 // In scope at the include: p (the argument struct), sh (Shared), b, tid, lane, wave, V, K, n (frames of log_probs[b] to consume;
 // row t + 1 is fetched only while t + 1 < n, nothing past row n - 1 is read), hist (one row of K entries per processed frame is
 // written at hist[steps * K]), lbuf / gbuf (sort arrays in LDS / global memory), nb0 and steps0 (live beams in sh.bm[0] -- the
 // first barrier below publishes them -- and processed frames so far).  Declared here and left to the includer: nb, cur, steps (the
 // search after the n frames) and bad (-1, or the first of the n frames holding a NaN: the search then stands as before it).
 // Ends on a __syncthreads.
+// The LM switch: Lm, the includer's policy type (ctc_beam_impl.h), and lb (Lm::Lds).  With NoLm lb is an empty constant and nothing
+// below reads it.  Under `if constexpr (Lm::on)` lb holds the LM states of the beams in sh.bm, double-buffered by the same cur /
+// nxt (those of the nb0 initial beams in lb[0]), and the text calls lm_load, lm_extend (which reads p's LM tables and p.tok_len)
+// and lm_store of ctc_beam_lm_impl.h: the rank sort then runs on cand_total, and a surviving beam's score is the folded acoustic one.
     for (int c = 0; c < VCH; ++c)
         if (c * NT + tid < V && n > 0) sh.row[0][c * NT + tid] = load_lp(p, b, 0, c * NT + tid);
     int nb = nb0, cur = 0, steps = steps0, bad = -1;
@@ -75,19 +80,37 @@
                 const int j = idx / nb, r = idx - j * nb;
                 return sh.bm.score[cur][r] + (double)row[sh.sel[j]];
             };
+            // under an LM the rank sort runs on acoustic + LM(text) + partial_score(partial) of the candidate's state, as below
+            const auto cand_total = [&] {
+                if constexpr (Lm::on) {
+                    return [&](int idx, double acoustic) {
+                        const int j = idx / nb, r = idx - j * nb, v = sh.sel[j];
+                        typename Lm::State nl = lm_load(lb, cur, r);
+                        if (!(v == p.blank || v == sh.bm.last[cur][r])) {
+                            const State s = load_state(sh.bm, cur, r);
+                            const int cls = p.tok_class[v];
+                            nl = lm_extend(p, nl, s, extend(p, s, v, cls), v, cls);
+                        }
+                        return acoustic + nl.lm + nl.ps;
+                    };
+                } else {
+                    return NoTotal{};
+                }
+            }();
             int kept;
             if (n2 <= LDS_CAP) {
                 gen(lbuf);
                 cm_lds_barrier();
-                kept = merge_rank<false>(sh, lbuf, ncand, n2, K, p.beam_prune_logp, cand_score);
+                kept = merge_rank<false>(sh, lbuf, ncand, n2, K, p.beam_prune_logp, cand_score, cand_total);
             } else {
                 gen(gbuf);
                 __syncthreads();
-                kept = merge_rank<true>(sh, gbuf, ncand, n2, K, p.beam_prune_logp, cand_score);
+                kept = merge_rank<true>(sh, gbuf, ncand, n2, K, p.beam_prune_logp, cand_score, cand_total);
             }
             const Buf rb = n2 <= LDS_CAP ? lbuf : gbuf;
-            // the new beams, in rank order
+            // the new beams, in rank order; under an LM k1 ranks by the total and the folded acoustic score waits at the head's position
             State ns;
+            typename Lm::State nl;
             double nscore = 0.0;
             int nlast = -1, entry = 0;
             if (tid < kept) {
@@ -95,10 +118,17 @@
                 const State s = load_state(sh.bm, cur, r);
                 const bool same = v == p.blank || v == sh.bm.last[cur][r];
                 ns = same ? s : extend(p, s, v, p.tok_class[v]);
-                nscore = key_score(rb.k1[tid]);
+                if constexpr (Lm::on) {
+                    nl = lm_load(lb, cur, r);
+                    if (!same) nl = lm_extend(p, nl, s, ns, v, p.tok_class[v]);
+                    nscore = rb.sc[min(max((int)rb.k3[tid], 0), n2 - 1)] + 0.0;
+                } else {
+                    nscore = key_score(rb.k1[tid]);
+                }
                 nlast = v;
                 entry = (r << 16) | (same ? 0 : v + 1);
                 store_state(sh.bm, nxt, tid, ns, nscore, nlast);
+                if constexpr (Lm::on) lm_store(lb, nxt, tid, nl);
             }
             __syncthreads();
             int slot = tid;
@@ -120,7 +150,10 @@
                 int total = 0;
                 for (int q = 0; q < kept; ++q) total += sh.keep[q];
                 __syncthreads();
-                if (keep) store_state(sh.bm, nxt, slot, ns, nscore, nlast);
+                if (keep) {
+                    store_state(sh.bm, nxt, slot, ns, nscore, nlast);
+                    if constexpr (Lm::on) lm_store(lb, nxt, slot, nl);
+                }
                 if (!keep) slot = -1;
                 kept = total;
             }

@@ -1,7 +1,9 @@
-// ctc_beam_impl.h — what the whole-utterance CTC beam search (ctc_beam.hip, cm_ctc_beam_search) and the streamed one
-// (ctc_beam_stream.hip, cm_ctc_beam_stream) share: constants, the LDS layout, hashing, merge_rank and, as text both kernels include
-// in their bodies, the frame loop (ctc_beam_frames.inc.h) and the finish with its backtrack (ctc_beam_finish.inc.h).  Both kernels
-// run exactly these statements per frame, so a search fed chunk by chunk returns the bits of the search fed at once.  The
+// ctc_beam_impl.h — what the whole-utterance CTC beam search (ctc_beam.hip, cm_ctc_beam_search), the streamed one
+// (ctc_beam_stream.hip, cm_ctc_beam_stream) and the LM-fused one (ctc_beam_lm.hip, cm_ctc_beam_lm_search) share: constants, the LDS
+// layout, hashing, merge_rank, the host-side argument check and slab layout and, as text all three kernels include in their
+// bodies, the frame loop (ctc_beam_frames.inc.h) and the finish with its backtrack (ctc_beam_finish.inc.h).  The kernels run
+// exactly these statements per frame, so a search fed chunk by chunk returns the bits of the search fed at once, and the LM search
+// differs from the LM-free one only in what the fragments say under their LM switch (NoLm below).  The
 // algorithm is stated in mamba_asr_amd/ctc_decode.py and DESIGN.md §4b; in short, per processed frame:
 //   select tokens {v : lp[v] > token_prune_min_logp} U {first argmax}, ascending;  candidates (token outer, beam rank inner) with
 //   score + lp[v];  merge equal (canonical text hash, last token): survivor = earliest candidate, score = left logaddexp fold in
@@ -35,9 +37,10 @@ constexpr uint64_t KEY_MAX = ~0ull;
 constexpr int F_TEXT_EMPTY = 1, F_PART_EMPTY = 2;
 
 // The helpers that read search parameters (joined, extend, canonical, load_lp) are templates over the argument struct P,
-// cm_ctc_beam_args or cm_ctc_beam_stream_args, and the two text fragments name it p: the fields they read carry the same names in
-// both structs (log_probs, lp_bs, lp_ts, dtype, V, the token tables, the hash constants, blank, beam_size, topk, prune_history,
-// beam_prune_logp, token_prune_min_logp, blank_skip_log; the finish also num_hyps, tokens, token_len, scores).
+// cm_ctc_beam_args, cm_ctc_beam_stream_args or cm_ctc_beam_lm_args, and the two text fragments name it p: the fields they read
+// carry the same names in all three structs (log_probs, lp_bs, lp_ts, dtype, V, the token tables, the hash constants, blank, beam_size, topk, prune_history,
+// beam_prune_logp, token_prune_min_logp, blank_skip_log; the finish also num_hyps, tokens, token_len, scores; under the LM switch
+// also tok_len, the LM tables and constants, lm_scores).
 
 __device__ __forceinline__ uint64_t mod_add(uint64_t a, uint64_t b) {
     uint64_t r = a + b;
@@ -98,6 +101,17 @@ struct Shared {
 struct Buf {
     uint64_t *k1, *k2, *k3;
     double *sc;
+};
+
+// The LM switch of the two text fragments.  Every kernel that includes them is a template over a policy type Lm (and over its
+// argument struct), so that what the fragments say under `if constexpr (Lm::on)` is dependent and is never instantiated for the
+// LM-free kernels.  Lm::Lds is the type of the includer's `lb` (the per-beam LM state beside sh.bm), Lm::State one beam's LM
+// state in registers, Lm::CTX its context length.  NoLm holds nothing: its `lb` is an empty constant, no LDS.  The n-gram policy,
+// NgramLm, is in ctc_beam_lm_impl.h with the lm_* functions the fragments call under the switch.
+struct NoLm {
+    static constexpr bool on = false;
+    struct Lds {};
+    struct State {};
 };
 
 __device__ __forceinline__ State load_state(const Beams &bm, int buf, int r) {
@@ -197,11 +211,17 @@ template <bool G> __device__ void bitonic(const Buf b, int n2) {
         }
 }
 
+// merge_rank without a total: prune and rank by the folded score itself
+struct NoTotal {};
+
 // Merge + prune + rank over n candidates whose keys (k1, k2 = hashes, k3 = group tag << 32 | candidate index) are in b, padded to
-// n2 with KEY_MAX.  score(idx) gives a candidate's score.  On return positions 0 .. *kept-1 hold the survivors in rank order:
-// k1 = score_key(score), k2 = candidate index.
-template <bool G, class ScoreFn>
-__device__ int merge_rank(Shared &sh, const Buf b, int n, int n2, int limit, double prune, ScoreFn score) {
+// n2 with KEY_MAX.  score(idx) gives a candidate's score; the scores of a run of equal keys fold into b.sc at the position of the
+// run's head.  On return positions 0 .. kept-1 hold the survivors in rank order: k1 = score_key(score), k2 = candidate index.
+// With a total functor (the LM search) each head gets total(idx, folded score) and prune, rank and limit act on the totals:
+// k1 = score_key(total), and k3 = the position in b.sc where the folded score stays.
+template <bool G, class ScoreFn, class TotalFn = NoTotal>
+__device__ int merge_rank(Shared &sh, const Buf b, int n, int n2, int limit, double prune, ScoreFn score, TotalFn total = {}) {
+    constexpr bool totals = !std::is_same_v<TotalFn, NoTotal>;
     const int tid = threadIdx.x;
     bitonic<G>(b, n2);
     // fold each run of equal (k1, k2, tag) in candidate order into its first entry
@@ -224,9 +244,15 @@ __device__ int merge_rank(Shared &sh, const Buf b, int n, int n2, int limit, dou
         const double s = b.sc[i];
         const bool alive = s == s;
         const uint64_t idx = (uint32_t)b.k3[i];
-        b.k1[i] = alive ? score_key(s) : KEY_MAX;
-        b.k2[i] = alive ? idx : KEY_MAX;
-        b.k3[i] = 0;
+        if constexpr (totals) {
+            b.k1[i] = alive ? score_key(total((int)idx, s)) : KEY_MAX;
+            b.k2[i] = alive ? idx : KEY_MAX;
+            b.k3[i] = (uint64_t)i;
+        } else {
+            b.k1[i] = alive ? score_key(s) : KEY_MAX;
+            b.k2[i] = alive ? idx : KEY_MAX;
+            b.k3[i] = 0;
+        }
     }
     barrier<G>();
     bitonic<G>(b, n2);
@@ -285,6 +311,48 @@ inline int sort_entries(int beam_size, int V) {
 __device__ __forceinline__ Buf global_buf(char *base, int n2max) {
     uint64_t *k = reinterpret_cast<uint64_t *>(base);
     return Buf{k, k + n2max, k + 2 * (int64_t)n2max, reinterpret_cast<double *>(base) + 3 * (int64_t)n2max};
+}
+
+// per-utterance workspace slab of the whole-utterance searches: history (T x K int32, rounded to 16 B), then the sort arrays when
+// the candidates can outgrow LDS
+template <class A> void slab_layout(const A &a, int64_t *slab, int64_t *hist, int *n2max) {
+    *hist = ((int64_t)a.T * a.beam_size * 4 + 15) / 16 * 16;
+    *n2max = sort_entries(a.beam_size, a.V);
+    *slab = *hist + 4 * 8 * (int64_t)*n2max;
+}
+
+// the body of cm_ctc_beam_workspace_bytes and cm_ctc_beam_lm_workspace_bytes: 0 for sizes outside the limits
+template <class A> int64_t whole_workspace_bytes(const A *args) {
+    if (!args || args->batch <= 0 || args->T <= 0 || args->V <= 1 || args->V > VMAX || args->beam_size <= 0 || args->beam_size > KMAX)
+        return 0;
+    int64_t slab, hist;
+    int n2max;
+    slab_layout(*args, &slab, &hist, &n2max);
+    return slab * args->batch;
+}
+
+// The argument checks the three entry points share, in the order each of them always made them; `who` prefixes the messages.
+// max_frames is NULL for a whole-utterance entry (T in [1, TMAX]), else the streamed entry's, whose chunk of T rows may be empty
+// (then no log_probs and no strides) and must fit *max_frames.  pointers: the entry's own "none of my pointers is NULL".
+template <class A> int check_beam_args(const A &a, const char *who, const int32_t *max_frames, bool pointers) {
+    const bool whole = max_frames == nullptr;
+    CM_REQUIRE(a.batch > 0 && a.T >= (whole ? 1 : 0) && a.V > 1, CM_EINVAL, "%s: bad sizes batch=%d T=%d V=%d", who, a.batch, a.T, a.V);
+    CM_REQUIRE(a.V <= VMAX, CM_EUNSUPPORTED, "%s: at most %d tokens (got %d)", who, VMAX, a.V);
+    CM_REQUIRE(!whole || a.T <= TMAX, CM_EUNSUPPORTED, "%s: T=%d too long", who, a.T);
+    CM_REQUIRE(a.beam_size >= 1 && a.beam_size <= KMAX, CM_EINVAL, "%s: beam_size %d not in [1, %d]", who, a.beam_size, KMAX);
+    CM_REQUIRE(whole || (*max_frames >= 1 && *max_frames <= TMAX), CM_EINVAL, "%s: max_frames %d not in [1, %d]", who, *max_frames, TMAX);
+    CM_REQUIRE(whole || a.T <= *max_frames, CM_EINVAL, "%s: a chunk of T=%d rows exceeds max_frames=%d", who, a.T, *max_frames);
+    CM_REQUIRE(a.topk >= 1, CM_EINVAL, "%s: topk %d < 1", who, a.topk);
+    CM_REQUIRE(a.blank >= 0 && a.blank < a.V, CM_EINVAL, "%s: blank %d out of range", who, a.blank);
+    CM_REQUIRE(a.dtype == CM_F32 || a.dtype == CM_BF16, CM_EUNSUPPORTED, "%s: log_probs must be fp32 or bf16", who);
+    CM_REQUIRE(a.T == 0 || (a.lp_bs >= 0 && a.lp_ts >= a.V), CM_EINVAL, "%s: bad log_probs strides bs=%lld ts=%lld", who,
+               (long long)a.lp_bs, (long long)a.lp_ts);
+    CM_REQUIRE(pointers, CM_EINVAL, "%s: NULL pointer", who);
+    CM_REQUIRE(a.hash_base[0] > 1 && a.hash_base[0] < P61 && a.hash_base[1] > 1 && a.hash_base[1] < P61 && a.hash_sep < P61,
+               CM_EINVAL, "%s: hash bases / separator must lie in (1, 2^61 - 1)", who);
+    CM_REQUIRE(!std::isnan(a.beam_prune_logp) && !std::isnan(a.token_prune_min_logp) && a.blank_skip_threshold > 0.0,
+               CM_EINVAL, "%s: thresholds must not be NaN and blank_skip_threshold must be > 0", who);
+    return CM_OK;
 }
 
 }  // namespace

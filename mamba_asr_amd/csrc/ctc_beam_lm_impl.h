@@ -1,6 +1,6 @@
 // ctc_beam_lm_impl.h — what the LM-fused CTC beam search (ctc_beam_lm.hip, cm_ctc_beam_lm_search) adds to ctc_beam_impl.h: the
-// per-beam LM state in LDS, the table probes, ARPA backoff, the word and partial-word scores, and merge_rank_lm, the merge_rank
-// that folds acoustic scores but prunes and ranks by a total the caller derives from each run head.  Contract: DESIGN.md §4p.
+// per-beam LM state in LDS, the table probes, ARPA backoff, the word and partial-word scores, and NgramLm, the policy that turns on
+// the LM switch of the shared frame loop and finish, which call these functions.  Contract: DESIGN.md §4p.
 // Probes read global memory from a few divergent lanes; each loop runs at most `capacity` steps and every id a table returns is
 // range-checked before it indexes anything.
 #pragma once
@@ -146,48 +146,12 @@ template <class P> __device__ __forceinline__ void lm_store_initial(const P &p, 
     lm_store(lb, buf, 0, s);
 }
 
-// merge_rank with a total: runs of equal keys fold their acoustic scores (score(idx), as merge_rank does) into b.sc at the head's
-// position, which stays there; each head then gets total(idx, folded acoustic), and prune, rank and limit act on the totals.  On
-// return positions 0 .. kept-1 hold the survivors in rank order: k1 = score_key(total), k2 = candidate index, k3 = the position
-// in b.sc of the folded acoustic score.
-template <bool G, class ScoreFn, class TotalFn>
-__device__ int merge_rank_lm(Shared &sh, const Buf b, int n, int n2, int limit, double prune, ScoreFn score, TotalFn total) {
-    const int tid = threadIdx.x;
-    bitonic<G>(b, n2);
-    for (int i = tid; i < n2; i += NT) {
-        double s = 0.0;
-        bool head = false;
-        if (i < n) {
-            const uint64_t a1 = b.k1[i], a2 = b.k2[i], a3 = b.k3[i];
-            head = i == 0 || b.k1[i - 1] != a1 || b.k2[i - 1] != a2 || (b.k3[i - 1] >> 32) != (a3 >> 32);
-            if (head) {
-                s = score((int)(uint32_t)a3);
-                for (int j = i + 1; j < n && b.k1[j] == a1 && b.k2[j] == a2 && (b.k3[j] >> 32) == (a3 >> 32); ++j)
-                    s = lae(s, score((int)(uint32_t)b.k3[j]));
-            }
-        }
-        b.sc[i] = head ? s : __builtin_nan("");
-    }
-    barrier<G>();
-    for (int i = tid; i < n2; i += NT) {
-        const double s = b.sc[i];
-        const bool alive = s == s;
-        const uint64_t idx = (uint32_t)b.k3[i];
-        b.k1[i] = alive ? score_key(total((int)idx, s)) : KEY_MAX;
-        b.k2[i] = alive ? idx : KEY_MAX;
-        b.k3[i] = (uint64_t)i;
-    }
-    barrier<G>();
-    bitonic<G>(b, n2);
-    const double thr = key_score(b.k1[0]) + prune;
-    if (tid == 0) sh.nkeep = 0;
-    barrier<G>();
-    for (int i = tid; i < n2; i += NT) {
-        auto ok = [&](int x) { return x < n2 && b.k1[x] != KEY_MAX && key_score(b.k1[x]) >= thr; };
-        if (ok(i) && !ok(i + 1)) sh.nkeep = i + 1;        // the single boundary of a monotone predicate: one writer
-    }
-    barrier<G>();
-    return min(sh.nkeep, limit);
-}
+// the LM switch of the text fragments (ctc_beam_impl.h, NoLm) for this LM
+struct NgramLm {
+    static constexpr bool on = true;
+    using Lds = LmBeams;
+    using State = LmState;
+    static constexpr int CTX = LM_CTX;
+};
 
 }  // namespace

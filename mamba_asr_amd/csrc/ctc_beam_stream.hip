@@ -1,6 +1,6 @@
 // ctc_beam_stream.hip — the CTC beam search carried across streaming chunks (contract: cm_ctc_beam_stream).  One
 // workgroup per slot loads the slot's beams from its state slab into LDS, runs the frame loop of ctc_beam_impl.h -- the text
-// cm_ctc_beam_search runs -- over the chunk's rows, appending to the history inside the slab, stores the beams back and, when asked,
+// cm_ctc_beam_search and cm_ctc_beam_lm_search run, here with the LM switch off (NoLm) -- over the chunk's rows, appending to the history inside the slab, stores the beams back and, when asked,
 // finishes on the sort buffers and backtracks: an emit changes neither beams nor history.  Loading and storing the state moves the
 // live beams only (plain vector loads and stores); nothing is shared between workgroups.
 //
@@ -37,8 +37,10 @@ __device__ __forceinline__ Slab slab_of(char *base, int K) {
     return s;
 }
 
-__global__ __launch_bounds__(NT) void ctc_beam_stream_kernel(const cm_ctc_beam_stream_args p, int64_t ws_bytes, int n2max) {
+template <class Lm, class P>
+__global__ __launch_bounds__(NT) void ctc_beam_stream_kernel(const P p, int64_t ws_bytes, int n2max) {
     __shared__ Shared sh;
+    [[maybe_unused]] constexpr typename Lm::Lds lb{};      // NoLm: no per-beam LM state (the slab holds none yet)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int V = p.V, K = p.beam_size, F = p.max_frames;
     const int asked = min(max(p.chunk_len[b], 0), p.T);
@@ -122,22 +124,9 @@ extern "C" int64_t cm_ctc_beam_stream_workspace_bytes(const cm_ctc_beam_stream_a
 extern "C" int cm_ctc_beam_stream(const cm_ctc_beam_stream_args *args) {
     CM_REQUIRE(args != nullptr, CM_EINVAL, "ctc_beam_stream: args is NULL");
     cm_ctc_beam_stream_args a = *args;
-    CM_REQUIRE(a.batch > 0 && a.T >= 0 && a.V > 1, CM_EINVAL, "ctc_beam_stream: bad sizes batch=%d T=%d V=%d", a.batch, a.T, a.V);
-    CM_REQUIRE(a.V <= VMAX, CM_EUNSUPPORTED, "ctc_beam_stream: at most %d tokens (got %d)", VMAX, a.V);
-    CM_REQUIRE(a.beam_size >= 1 && a.beam_size <= KMAX, CM_EINVAL, "ctc_beam_stream: beam_size %d not in [1, %d]", a.beam_size, KMAX);
-    CM_REQUIRE(a.max_frames >= 1 && a.max_frames <= TMAX, CM_EINVAL, "ctc_beam_stream: max_frames %d not in [1, %d]", a.max_frames, TMAX);
-    CM_REQUIRE(a.T <= a.max_frames, CM_EINVAL, "ctc_beam_stream: a chunk of T=%d rows exceeds max_frames=%d", a.T, a.max_frames);
-    CM_REQUIRE(a.topk >= 1, CM_EINVAL, "ctc_beam_stream: topk %d < 1", a.topk);
-    CM_REQUIRE(a.blank >= 0 && a.blank < a.V, CM_EINVAL, "ctc_beam_stream: blank %d out of range", a.blank);
-    CM_REQUIRE(a.dtype == CM_F32 || a.dtype == CM_BF16, CM_EUNSUPPORTED, "ctc_beam_stream: log_probs must be fp32 or bf16");
-    CM_REQUIRE(a.T == 0 || (a.lp_bs >= 0 && a.lp_ts >= a.V), CM_EINVAL, "ctc_beam_stream: bad log_probs strides bs=%lld ts=%lld",
-               (long long)a.lp_bs, (long long)a.lp_ts);
-    CM_REQUIRE((a.log_probs || a.T == 0) && a.chunk_len && a.tok_class && a.tok_hash && a.tok_pow && a.state && a.tokens && a.token_len &&
-                   a.scores && a.num_hyps && a.status, CM_EINVAL, "ctc_beam_stream: NULL pointer");
-    CM_REQUIRE(a.hash_base[0] > 1 && a.hash_base[0] < P61 && a.hash_base[1] > 1 && a.hash_base[1] < P61 && a.hash_sep < P61,
-               CM_EINVAL, "ctc_beam_stream: hash bases / separator must lie in (1, 2^61 - 1)");
-    CM_REQUIRE(!std::isnan(a.beam_prune_logp) && !std::isnan(a.token_prune_min_logp) && a.blank_skip_threshold > 0.0,
-               CM_EINVAL, "ctc_beam_stream: thresholds must not be NaN and blank_skip_threshold must be > 0");
+    const bool pointers = (a.log_probs || a.T == 0) && a.chunk_len && a.tok_class && a.tok_hash && a.tok_pow && a.state && a.tokens &&
+                          a.token_len && a.scores && a.num_hyps && a.status;
+    if (const int rc = check_beam_args(a, "ctc_beam_stream", &a.max_frames, pointers)) return rc;
     CM_REQUIRE(a.state_stride_bytes >= state_bytes(a.beam_size, a.max_frames) && a.state_stride_bytes % 16 == 0 &&
                    reinterpret_cast<uintptr_t>(a.state) % 16 == 0, CM_EINVAL,
                "ctc_beam_stream: state_stride_bytes %lld must be a multiple of 16 and at least cm_ctc_beam_stream_state_bytes() = %lld, "
@@ -146,7 +135,7 @@ extern "C" int cm_ctc_beam_stream(const cm_ctc_beam_stream_args *args) {
     CM_REQUIRE(a.workspace_bytes >= ws && (a.workspace || ws == 0) && reinterpret_cast<uintptr_t>(a.workspace) % 8 == 0, CM_EINVAL,
                "ctc_beam_stream: workspace smaller than cm_ctc_beam_stream_workspace_bytes() or not 8-byte aligned");
     a.blank_skip_log = std::log(a.blank_skip_threshold);
-    hipLaunchKernelGGL(ctc_beam_stream_kernel, dim3(a.batch), dim3(NT), 0, reinterpret_cast<hipStream_t>(a.stream), a, ws / a.batch,
-                       sort_entries(a.beam_size, a.V));
+    hipLaunchKernelGGL((ctc_beam_stream_kernel<NoLm, cm_ctc_beam_stream_args>), dim3(a.batch), dim3(NT), 0,
+                       reinterpret_cast<hipStream_t>(a.stream), a, ws / a.batch, sort_entries(a.beam_size, a.V));
     return cm_launch_status("cm_ctc_beam_stream");
 }

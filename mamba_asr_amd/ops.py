@@ -861,6 +861,65 @@ def ctc_loss_grad(log_probs, targets, input_lengths, target_lengths, blank=0):
     return nll, grad
 
 
+def _ctc_beam_args(what, a, log_probs, dev, tok_class, tok_hash, tok_pow, tok_len, hash_base, hash_sep, blank, beam_size, topk,
+                   prune_history, beam_prune_logp, token_prune_min_logp, blank_skip_threshold):
+    """What the three CTC beam searches prepare alike, filled into their argument struct ``a``: log_probs as fp32 / bf16 with unit
+    vocabulary stride (None: no rows, V from tok_class), the token tables on the device (dev, or None for log_probs'), checked to
+    cover the V tokens (tok_len: the LM search's, else None), the hash constants, beam and thresholds.
+    -> (lp, T, V, keep): keep holds the converted tensors ``a`` points at."""
+    if log_probs is None:
+        lp, t, v = None, 0, int(tok_class.shape[0])
+        a.dtype = N.CM_F32
+    else:
+        if log_probs.dtype not in (torch.float32, torch.bfloat16):
+            log_probs = log_probs.float()
+        lp = log_probs.detach()
+        if lp.stride(2) != 1:
+            lp = lp.contiguous()
+        _, t, v = lp.shape
+        a.dtype, a.lp_bs, a.lp_ts = _DT[lp.dtype], lp.stride(0), lp.stride(1)
+        dev = lp.device if dev is None else dev
+    tc = tok_class.detach().to(device=dev, dtype=torch.int32).contiguous()
+    th = tok_hash.detach().to(device=dev, dtype=torch.int64).contiguous()
+    tp = tok_pow.detach().to(device=dev, dtype=torch.int64).contiguous()
+    tl = None if tok_len is None else tok_len.detach().to(device=dev, dtype=torch.int32).contiguous()
+    if tc.numel() != v or th.numel() != 2 * v or tp.numel() != 2 * v or (tl is not None and tl.numel() != v):
+        raise RuntimeError(f"{what}: token tables must cover the {v} tokens of log_probs")
+    a.T, a.V = t, v
+    a.log_probs, a.tok_class, a.tok_hash, a.tok_pow = _ptr(lp), _ptr(tc), _ptr(th), _ptr(tp)
+    if tl is not None:
+        a.tok_len = _ptr(tl)
+    a.hash_base[0], a.hash_base[1], a.hash_sep = int(hash_base[0]), int(hash_base[1]), int(hash_sep)
+    a.blank, a.beam_size, a.topk, a.prune_history = int(blank), int(beam_size), int(topk), int(bool(prune_history))
+    a.beam_prune_logp, a.token_prune_min_logp = float(beam_prune_logp), float(token_prune_min_logp)
+    a.blank_skip_threshold = float(blank_skip_threshold)
+    return lp, t, v, (lp, tc, th, tp, tl)
+
+
+def _ctc_beam_whole(a, workspace_bytes, lp, lengths, topk):
+    """Lengths, outputs and workspace of a whole-utterance CTC beam search into its argument struct ``a`` (filled by
+    _ctc_beam_args; lm_scores where the struct has it) -> (the outputs in the struct's order, the tensors to keep until launch)."""
+    b, t, _ = lp.shape
+    dev = lp.device
+    ln = lengths.detach().to(device=dev, dtype=torch.int32).contiguous()
+    tokens = torch.empty((b, topk, t), dtype=torch.int32, device=dev)
+    token_len = torch.zeros((b, topk), dtype=torch.int32, device=dev)
+    scores = torch.zeros((b, topk), dtype=torch.float64, device=dev)
+    num_hyps = torch.empty((b,), dtype=torch.int32, device=dev)
+    bad_frame = torch.empty((b,), dtype=torch.int32, device=dev)
+    a.tokens, a.token_len, a.scores, a.num_hyps, a.bad_frame = _ptr(tokens), _ptr(token_len), _ptr(scores), _ptr(num_hyps), _ptr(bad_frame)
+    out = (tokens, token_len, scores, num_hyps, bad_frame)
+    if hasattr(a, "lm_scores"):
+        lm_scores = torch.zeros((b, topk), dtype=torch.float64, device=dev)
+        a.lm_scores = _ptr(lm_scores)
+        out = out[:3] + (lm_scores,) + out[3:]
+    a.batch, a.lengths = b, _ptr(ln)
+    nws = int(workspace_bytes(ct.byref(a)))
+    ws = torch.empty((max(nws, 1),), dtype=torch.uint8, device=dev)
+    a.workspace, a.workspace_bytes, a.stream = _ptr(ws), nws, _stream()
+    return out, (ln, ws)
+
+
 def ctc_beam_search(log_probs, lengths, tok_class, tok_hash, tok_pow, hash_base, hash_sep, blank=0, beam_size=100, topk=1,
                     prune_history=False, beam_prune_logp=-10.0, token_prune_min_logp=-5.0, blank_skip_threshold=1.0):
     """LM-free CTC beam search (cm_ctc_beam_search).  log_probs (batch, T, V) fp32 / bf16, lengths (batch) frames to decode;
@@ -868,36 +927,12 @@ def ctc_beam_search(log_probs, lengths, tok_class, tok_hash, tok_pow, hash_base,
     -> (tokens (batch, topk, T) int32, token_len (batch, topk) int32, scores (batch, topk) fp64, num_hyps (batch) int32,
     bad_frame (batch) int32): hypothesis h < num_hyps[b] of utterance b is its text-changing tokens tokens[b, h, :token_len[b, h]]."""
     _dev_check(log_probs, lengths, tok_class, tok_hash, tok_pow)
-    if log_probs.dtype not in (torch.float32, torch.bfloat16):
-        log_probs = log_probs.float()
-    lp = log_probs.detach()
-    if lp.stride(2) != 1:
-        lp = lp.contiguous()
-    b, t, v = lp.shape
-    dev = lp.device
-    ln = lengths.detach().to(device=dev, dtype=torch.int32).contiguous()
-    tc = tok_class.detach().to(device=dev, dtype=torch.int32).contiguous()
-    th = tok_hash.detach().to(device=dev, dtype=torch.int64).contiguous()
-    tp = tok_pow.detach().to(device=dev, dtype=torch.int64).contiguous()
-    tokens = torch.empty((b, topk, t), dtype=torch.int32, device=dev)
-    token_len = torch.zeros((b, topk), dtype=torch.int32, device=dev)
-    scores = torch.zeros((b, topk), dtype=torch.float64, device=dev)
-    num_hyps = torch.empty((b,), dtype=torch.int32, device=dev)
-    bad_frame = torch.empty((b,), dtype=torch.int32, device=dev)
     a = N.CtcBeamArgs()
-    a.batch, a.T, a.V, a.dtype = b, t, v, _DT[lp.dtype]
-    a.lp_bs, a.lp_ts = lp.stride(0), lp.stride(1)
-    a.log_probs, a.lengths, a.tok_class, a.tok_hash, a.tok_pow = _ptr(lp), _ptr(ln), _ptr(tc), _ptr(th), _ptr(tp)
-    a.hash_base[0], a.hash_base[1], a.hash_sep = int(hash_base[0]), int(hash_base[1]), int(hash_sep)
-    a.blank, a.beam_size, a.topk, a.prune_history = int(blank), int(beam_size), int(topk), int(bool(prune_history))
-    a.beam_prune_logp, a.token_prune_min_logp = float(beam_prune_logp), float(token_prune_min_logp)
-    a.blank_skip_threshold = float(blank_skip_threshold)
-    nws = int(N.lib().cm_ctc_beam_workspace_bytes(ct.byref(a)))
-    ws = torch.empty((max(nws, 1),), dtype=torch.uint8, device=dev)
-    a.tokens, a.token_len, a.scores, a.num_hyps, a.bad_frame = _ptr(tokens), _ptr(token_len), _ptr(scores), _ptr(num_hyps), _ptr(bad_frame)
-    a.workspace, a.workspace_bytes, a.stream = _ptr(ws), nws, _stream()
-    _launch("cm_ctc_beam_search", N.lib().cm_ctc_beam_search, a, units=b * t)
-    return tokens, token_len, scores, num_hyps, bad_frame
+    lp, t, _, held = _ctc_beam_args("ctc_beam_search", a, log_probs, None, tok_class, tok_hash, tok_pow, None, hash_base, hash_sep, blank,
+                                    beam_size, topk, prune_history, beam_prune_logp, token_prune_min_logp, blank_skip_threshold)
+    out, held_whole = _ctc_beam_whole(a, N.lib().cm_ctc_beam_workspace_bytes, lp, lengths, topk)   # held: alive until the launch
+    _launch("cm_ctc_beam_search", N.lib().cm_ctc_beam_search, a, units=lp.shape[0] * t)
+    return out
 
 
 def ctc_beam_search_lm(log_probs, lengths, tok_class, tok_hash, tok_pow, tok_len, hash_base, hash_sep, lm, *, order, n_words,
@@ -920,47 +955,18 @@ def ctc_beam_search_lm(log_probs, lengths, tok_class, tok_hash, tok_pow, tok_len
     if lm["word_ids"].numel() != lm["word_keys"].shape[0] or lm["ngram_vals"].numel() != lm["ngram_keys"].numel() \
             or lm["backoff"].numel() != lm["prob"].numel():
         raise RuntimeError("ctc_beam_search_lm: keys / values of a table, or prob / backoff, differ in length")
-    if log_probs.dtype not in (torch.float32, torch.bfloat16):
-        log_probs = log_probs.float()
-    lp = log_probs.detach()
-    if lp.stride(2) != 1:
-        lp = lp.contiguous()
-    b, t, v = lp.shape
-    dev = lp.device
-    ln = lengths.detach().to(device=dev, dtype=torch.int32).contiguous()
-    tc = tok_class.detach().to(device=dev, dtype=torch.int32).contiguous()
-    th = tok_hash.detach().to(device=dev, dtype=torch.int64).contiguous()
-    tp = tok_pow.detach().to(device=dev, dtype=torch.int64).contiguous()
-    tl = tok_len.detach().to(device=dev, dtype=torch.int32).contiguous()
-    if tc.numel() != v or th.numel() != 2 * v or tp.numel() != 2 * v or tl.numel() != v:
-        raise RuntimeError(f"ctc_beam_search_lm: token tables must cover the {v} tokens of log_probs")
-    tokens = torch.empty((b, topk, t), dtype=torch.int32, device=dev)
-    token_len = torch.zeros((b, topk), dtype=torch.int32, device=dev)
-    scores = torch.zeros((b, topk), dtype=torch.float64, device=dev)
-    lm_scores = torch.zeros((b, topk), dtype=torch.float64, device=dev)
-    num_hyps = torch.empty((b,), dtype=torch.int32, device=dev)
-    bad_frame = torch.empty((b,), dtype=torch.int32, device=dev)
     a = N.CtcBeamLmArgs()
-    a.batch, a.T, a.V, a.dtype = b, t, v, _DT[lp.dtype]
-    a.lp_bs, a.lp_ts = lp.stride(0), lp.stride(1)
-    a.log_probs, a.lengths, a.tok_class, a.tok_hash, a.tok_pow, a.tok_len = _ptr(lp), _ptr(ln), _ptr(tc), _ptr(th), _ptr(tp), _ptr(tl)
-    a.hash_base[0], a.hash_base[1], a.hash_sep = int(hash_base[0]), int(hash_base[1]), int(hash_sep)
-    a.blank, a.beam_size, a.topk, a.prune_history = int(blank), int(beam_size), int(topk), int(bool(prune_history))
-    a.beam_prune_logp, a.token_prune_min_logp = float(beam_prune_logp), float(token_prune_min_logp)
-    a.blank_skip_threshold = float(blank_skip_threshold)
+    lp, t, _, held = _ctc_beam_args("ctc_beam_search_lm", a, log_probs, None, tok_class, tok_hash, tok_pow, tok_len, hash_base, hash_sep,
+                                    blank, beam_size, topk, prune_history, beam_prune_logp, token_prune_min_logp, blank_skip_threshold)
     a.order, a.n_words, a.lm_bos, a.lm_eos, a.lm_unk = int(order), int(n_words), int(lm_bos), int(lm_eos), int(lm_unk)
     a.n_entries, a.word_cap, a.prefix_cap, a.ngram_cap = (lm["prob"].numel(), lm["word_ids"].numel(), lm["prefix_keys"].shape[0],
                                                           lm["ngram_keys"].numel())
     a.word_keys, a.word_ids, a.prefix_keys = _ptr(lm["word_keys"]), _ptr(lm["word_ids"]), _ptr(lm["prefix_keys"])
     a.ngram_keys, a.ngram_vals, a.lm_prob, a.lm_backoff = _ptr(lm["ngram_keys"]), _ptr(lm["ngram_vals"]), _ptr(lm["prob"]), _ptr(lm["backoff"])
     a.alpha, a.beta, a.unk_score_offset = float(alpha), float(beta), float(unk_score_offset)
-    nws = int(N.lib().cm_ctc_beam_lm_workspace_bytes(ct.byref(a)))
-    ws = torch.empty((max(nws, 1),), dtype=torch.uint8, device=dev)
-    a.tokens, a.token_len, a.scores, a.lm_scores = _ptr(tokens), _ptr(token_len), _ptr(scores), _ptr(lm_scores)
-    a.num_hyps, a.bad_frame = _ptr(num_hyps), _ptr(bad_frame)
-    a.workspace, a.workspace_bytes, a.stream = _ptr(ws), nws, _stream()
-    _launch("cm_ctc_beam_lm_search", N.lib().cm_ctc_beam_lm_search, a, units=b * t)
-    return tokens, token_len, scores, lm_scores, num_hyps, bad_frame
+    out, held_whole = _ctc_beam_whole(a, N.lib().cm_ctc_beam_lm_workspace_bytes, lp, lengths, topk)   # held: alive until the launch
+    _launch("cm_ctc_beam_lm_search", N.lib().cm_ctc_beam_lm_search, a, units=lp.shape[0] * t)
+    return out
 
 
 def ctc_beam_stream_state(slots, beam_size, max_frames, device):
@@ -992,30 +998,12 @@ def ctc_beam_stream(log_probs, chunk_len, state, max_frames, tok_class, tok_hash
     for name, flag in (("chunk_len", chunk_len), ("reset", reset), ("emit", emit)):
         if flag is not None and (flag.dtype != torch.int32 or tuple(flag.shape) != (slots,) or not flag.is_contiguous() or flag.device != dev):
             raise RuntimeError(f"ctc_beam_stream: {name} must be a contiguous int32 tensor of shape ({slots},) on {dev}")
+    if log_probs is not None and (log_probs.dim() != 3 or log_probs.shape[0] != slots or log_probs.device != dev):
+        raise RuntimeError(f"ctc_beam_stream: log_probs must be ({slots}, t, V) on {dev}, got {tuple(log_probs.shape)} on {log_probs.device}")
     a = N.CtcBeamStreamArgs()
-    if log_probs is None:
-        t, v, lp = 0, int(tok_class.shape[0]), None
-        a.dtype = N.CM_F32
-    else:
-        if log_probs.dtype not in (torch.float32, torch.bfloat16):
-            log_probs = log_probs.float()
-        lp = log_probs.detach()
-        if lp.dim() != 3 or lp.shape[0] != slots or lp.device != dev:
-            raise RuntimeError(f"ctc_beam_stream: log_probs must be ({slots}, t, V) on {dev}, got {tuple(lp.shape)} on {lp.device}")
-        if lp.stride(2) != 1:
-            lp = lp.contiguous()
-        _, t, v = lp.shape
-        a.dtype, a.lp_bs, a.lp_ts = _DT[lp.dtype], lp.stride(0), lp.stride(1)
-    tc = tok_class.detach().to(device=dev, dtype=torch.int32).contiguous()
-    th = tok_hash.detach().to(device=dev, dtype=torch.int64).contiguous()
-    tp = tok_pow.detach().to(device=dev, dtype=torch.int64).contiguous()
-    a.batch, a.T, a.V = slots, t, v
-    a.log_probs, a.chunk_len, a.reset, a.emit = _ptr(lp), _ptr(chunk_len), _ptr(reset), _ptr(emit)
-    a.tok_class, a.tok_hash, a.tok_pow = _ptr(tc), _ptr(th), _ptr(tp)
-    a.hash_base[0], a.hash_base[1], a.hash_sep = int(hash_base[0]), int(hash_base[1]), int(hash_sep)
-    a.blank, a.beam_size, a.topk, a.prune_history = int(blank), int(beam_size), int(topk), int(bool(prune_history))
-    a.beam_prune_logp, a.token_prune_min_logp = float(beam_prune_logp), float(token_prune_min_logp)
-    a.blank_skip_threshold = float(blank_skip_threshold)
+    _, t, _, held = _ctc_beam_args("ctc_beam_stream", a, log_probs, dev, tok_class, tok_hash, tok_pow, None, hash_base, hash_sep, blank,
+                                   beam_size, topk, prune_history, beam_prune_logp, token_prune_min_logp, blank_skip_threshold)
+    a.batch, a.chunk_len, a.reset, a.emit = slots, _ptr(chunk_len), _ptr(reset), _ptr(emit)
     a.state, a.state_stride_bytes, a.max_frames = _ptr(state), state.stride(0), int(max_frames)
     nws = int(N.lib().cm_ctc_beam_stream_workspace_bytes(ct.byref(a)))
     take = _bufs(bufs, ("tokens", "token_len", "scores", "num_hyps", "status", "workspace"), "ctc_beam_stream")

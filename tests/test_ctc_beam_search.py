@@ -136,3 +136,24 @@ def test_abi_validates_without_gpu():
     assert lib.cm_ctc_beam_workspace_bytes(C.byref(a)) == 2 * (10 * 100 * 4)
     a.beam_size = 257
     assert lib.cm_ctc_beam_workspace_bytes(C.byref(a)) == 0
+
+
+def test_short_token_tables_are_refused_before_launch():
+    """The preparation all three beam search wrappers share refuses token tables that do not cover the V tokens of log_probs (the
+    kernels index them by token); host tensors, nothing is launched."""
+    import mamba_asr_amd._native as N
+    from mamba_asr_amd import ops
+    V = 5
+    lp = torch.zeros(2, 3, V)
+    tables = dict(tok_class=torch.zeros(V, dtype=torch.int32), tok_hash=torch.zeros(V, 2, dtype=torch.int64),
+                  tok_pow=torch.ones(V, 2, dtype=torch.int64))
+    settings = dict(tok_len=None, hash_base=(3, 5), hash_sep=1, blank=0, beam_size=4, topk=1, prune_history=False, beam_prune_logp=-10.0,
+                    token_prune_min_logp=-5.0, blank_skip_threshold=1.0)
+    for what, args in (("ctc_beam_search", N.CtcBeamArgs), ("ctc_beam_stream", N.CtcBeamStreamArgs), ("ctc_beam_search_lm", N.CtcBeamLmArgs)):
+        a = args()
+        ops._ctc_beam_args(what, a, lp, None, **tables, **settings)
+        assert (a.T, a.V, a.beam_size) == (3, V, 4)
+        for name in tables:
+            short = dict(tables, **{name: tables[name][:V - 1]})
+            with pytest.raises(RuntimeError, match=f"{what}: token tables must cover the {V} tokens"):
+                ops._ctc_beam_args(what, args(), lp, None, **short, **settings)
