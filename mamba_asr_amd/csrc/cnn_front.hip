@@ -17,6 +17,7 @@
 //     step does LayerNorm over 20 x 32 values + LeakyReLU and writes the bf16 row.
 // HBM traffic: the features once (each input row is read by the 1-2 waves that need it) and the output once.
 #include "cm_common.h"
+#include "front_plan.h"
 
 #include <type_traits>
 
@@ -57,8 +58,7 @@ struct front_lds {
     bf16x8 wfrag[2][18][64];              // block-2 weights as MFMA A-operand fragment images (36 KB; in registers they
 };                                        // cost 144 VGPRs and pushed the block-1 row computation into scratch)
 
-constexpr int FH = 8;                     // cm_cnn_front_stream: feature rows of history per stream
-constexpr int T_OPEN = 1 << 29;           // ... and its T / T1 while the utterance's end is unknown: no index reflects against it
+constexpr int T_OPEN = 1 << 29;           // cm_cnn_front_stream: T / T1 while the utterance's end is unknown: no index reflects against it
 
 // STREAM (cm_cnn_front_stream; ARGS = cm_cnn_front_stream_args): the launch produces rows [r0, r0 + nr) of utterances whose feature
 // frames arrive in chunks; T2 is then r0 + nr, T / T1 are T_OPEN unless the call ends the utterance, and the tile walk starts at
@@ -67,7 +67,7 @@ constexpr int T_OPEN = 1 << 29;           // ... and its T / T1 while the uttera
 // statements for both instantiations, so a row has the same bits.
 //
 // Per slot (cm_cnn_front_stream_slots; ARGS = cf_slot_args): f0, nf, r0, nr and T_total of stream b come from row b of the (batch, 8)
-// int32 plan table of the front end's per-slot entry points (columns 3 .. 7); the struct's nf and nr are then the maxima over the
+// int32 plan table of the front end's per-slot entry points (front_plan.h: PL_F0 .. PL_TTOTAL); the struct's nf and nr are then the maxima over the
 // slots, the row strides of feats and out, and the launch's T / T1 / T2 / tiles_per_utt are replaced per stream.  Chunks of tiles
 // past a stream's own rows are skipped.
 struct cf_slot_args : cm_cnn_front_stream_args {
@@ -198,9 +198,9 @@ __global__ __launch_bounds__(512) void cnn_front_kernel(const ARGS p, int T, int
         const int b = ch / chunks_per_utt, tile0 = (ch % chunks_per_utt) * chunk;
         [[maybe_unused]] int out_rows = 0;                        // SLOT / LENS: rows of out per stream (the widest one's)
         if constexpr (SLOT) {
-            const int32_t *s = p.plan + (int64_t)b * 8;
-            const int nr = s[6], Tt = s[7];
-            f0s = s[3], nfs = max(s[4], 1), rbase = s[5];
+            const int32_t *s = p.plan + (int64_t)b * PL_W;
+            const int nr = s[PL_NR], Tt = s[PL_TTOTAL];
+            f0s = s[PL_F0], nfs = max(s[PL_NF], 1), rbase = s[PL_R0];
             T = Tt >= 0 ? Tt : T_OPEN, T1 = Tt >= 0 ? (Tt + 1) / 2 : T_OPEN, T2 = rbase + nr, tp_last = 2 * T2;
             tiles_per_utt = (nr + TT - 1) / TT;
             out_rows = p.nr;
@@ -296,38 +296,81 @@ __global__ __launch_bounds__(512) void cnn_front_kernel(const ARGS p, int T, int
     }
 }
 
-}  // namespace
+// ---- host side.  The four entry points keep their own pointer checks and say what the kernel gets; the rest is written once.  `sym` is
+// an entry point's symbol, `who` = sym + 3 the name its messages begin with (no "cm_").
 
-extern "C" int cm_cnn_front(const cm_cnn_front_args *args) {
-    CM_REQUIRE(args != nullptr, CM_EINVAL, "cnn_front: args is NULL");
-    const cm_cnn_front_args &a = *args;
-    CM_REQUIRE(a.batch > 0 && a.T >= 5 && a.feats && a.w1 && a.ln1_g && a.ln1_b && a.w2 && a.ln2_g && a.ln2_b && a.out, CM_EINVAL,
-               "cnn_front: bad sizes or NULL tensor");
-    CM_REQUIRE(a.F == F0 && a.C1 == C1 && a.C2 == C2, CM_EUNSUPPORTED, "cnn_front: only 80 bins, channels (64, 32) (got F %d, C %d, %d)", a.F,
+// What cm_cnn_front_args and cm_cnn_front_stream_args have in common, in one order for every entry: NULL / sizes (`counts`: the entry's
+// own condition on its counts), then the shape, then the alignment.
+template <typename A>
+int cnn_front_check(const A &a, bool counts, const char *who) {
+    CM_REQUIRE(a.batch > 0 && counts && a.feats && a.w1 && a.ln1_g && a.ln1_b && a.w2 && a.ln2_g && a.ln2_b && a.out, CM_EINVAL,
+               "%s: bad sizes or NULL tensor", who);
+    CM_REQUIRE(a.F == F0 && a.C1 == C1 && a.C2 == C2, CM_EUNSUPPORTED, "%s: only 80 bins, channels (64, 32) (got F %d, C %d, %d)", who, a.F,
                a.C1, a.C2);
     CM_REQUIRE(cm_aligned(a.w2, 16) && cm_aligned(a.out, 4) && cm_aligned(a.ln1_g, 8) && cm_aligned(a.ln1_b, 8) && cm_aligned(a.ln2_g, 8) &&
                    cm_aligned(a.ln2_b, 8) && (!a.b2 || cm_aligned(a.b2, 16)),
-               CM_EALIGN, "cnn_front: w2 / b2 must be 16-byte aligned, LayerNorm parameters 8-byte aligned");
-    const int T1 = (a.T + 1) / 2, T2 = (T1 + 2 - 3) / 2 + 1;
-    const int tiles_per_utt = (T2 + TT - 1) / TT;
+               CM_EALIGN, "%s: w2 / b2 must be 16-byte aligned, LayerNorm parameters 8-byte aligned", who);
+    return CM_OK;
+}
+
+// The grid and the chunks are those of `rows` output rows per utterance (the widest one's: a chunk past an utterance's own tiles is
+// skipped); T / T1 / T2 are the kernel's, replaced per utterance by the lens and per-slot instantiations.
+template <bool STREAM, typename ARGS>
+int cnn_front_launch(const ARGS &k, int rows, int T, int T1, int T2, const char *sym) {
+    const int tiles_per_utt = (rows + TT - 1) / TT;
     const int chunk = 16;
     const int chunks_per_utt = (tiles_per_utt + chunk - 1) / chunk;
-    const int64_t nchunks = (int64_t)a.batch * chunks_per_utt;
-    CM_REQUIRE(nchunks <= 2147483647, CM_EINVAL, "cnn_front: too many chunks");
-    static bool attr_done = false;
+    const int64_t nchunks = (int64_t)k.batch * chunks_per_utt;
+    CM_REQUIRE(nchunks <= 2147483647, CM_EINVAL, "%s: too many chunks", sym + 3);
+    static bool attr_done = false;                                // one per instantiation
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(cnn_front_kernel<false, cm_cnn_front_args>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(cnn_front_kernel<STREAM, ARGS>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         if (e != hipSuccess) {
-            cm_set_error("cnn_front: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+            cm_set_error("%s: hipFuncSetAttribute failed: %s", sym + 3, hipGetErrorString(e));
             return (int)e;
         }
         attr_done = true;
     }
     const int64_t grid = nchunks < 256 ? nchunks : 256;
-    hipLaunchKernelGGL((cnn_front_kernel<false, cm_cnn_front_args>), dim3((unsigned)grid), dim3(512), sizeof(front_lds),
-                       reinterpret_cast<hipStream_t>(a.stream), a, a.T, T1, T2, tiles_per_utt, chunk, chunks_per_utt, (int)nchunks);
-    return cm_launch_status("cm_cnn_front");
+    hipLaunchKernelGGL((cnn_front_kernel<STREAM, ARGS>), dim3((unsigned)grid), dim3(512), sizeof(front_lds),
+                       reinterpret_cast<hipStream_t>(k.stream), k, T, T1, T2, tiles_per_utt, chunk, chunks_per_utt, (int)nchunks);
+    return cm_launch_status(sym);
+}
+
+// ": slot b" behind the entry's name in a per-slot refusal, nothing for slot < 0; built where a message is, on the failing path only
+struct slot_tag {
+    char s[24];
+    explicit slot_tag(int slot) {
+        s[0] = 0;
+        if (slot >= 0) snprintf(s, sizeof s, ": slot %d", slot);
+    }
+};
+
+// The conditions of the streamed form on one stream's counts: cm_cnn_front_stream's own scalars (slot -1), or row `slot` of the per-slot
+// plan.
+int cnn_front_stream_check(int64_t f0, int64_t nf, int64_t r0, int64_t nr, int64_t Tt, bool hist, const char *who, int slot) {
+    const int64_t fend = f0 + nf, rend = r0 + nr;
+    if (Tt >= 0) {                                                // the call ends the utterance: rows up to T2 - 1, reflected at T and T1
+        CM_REQUIRE(Tt >= 5 && Tt == fend, CM_EINVAL, "%s%s: T_total must be f0 + nf and at least 5", who, slot_tag(slot).s);
+        CM_REQUIRE(rend <= ((Tt + 1) / 2 + 1) / 2, CM_EINVAL, "%s%s: row %d is past the utterance's last", who, slot_tag(slot).s, (int)rend - 1);
+    } else {
+        CM_REQUIRE(4 * (rend - 1) + 3 < fend, CM_EINVAL, "%s%s: row %d needs frames that have not arrived", who, slot_tag(slot).s, (int)rend - 1);
+    }
+    // the lowest frame a row of the launch names: 4 r0 - 3 (reflected at 0), or T - 5 through the reflections at the end
+    const int64_t lowest = std::min<int64_t>(std::max<int64_t>(4 * r0 - 3, 0), Tt >= 0 ? Tt - 5 : fend);
+    CM_REQUIRE(lowest >= (hist ? f0 - FH : f0), CM_EINVAL, "%s%s: row %d reaches behind the feature history", who, slot_tag(slot).s, (int)r0);
+    return CM_OK;
+}
+
+}  // namespace
+
+extern "C" int cm_cnn_front(const cm_cnn_front_args *args) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "cnn_front: args is NULL");
+    const cm_cnn_front_args &a = *args;
+    if (int rc = cnn_front_check(a, a.T >= 5, "cnn_front")) return rc;
+    const int T1 = (a.T + 1) / 2, T2 = (T1 + 2 - 3) / 2 + 1;
+    return cnn_front_launch<false>(a, T2, a.T, T1, T2, "cm_cnn_front");
 }
 
 extern "C" int cm_cnn_front_lens(const cm_cnn_front_args *args, const int32_t *frames) {
@@ -335,133 +378,42 @@ extern "C" int cm_cnn_front_lens(const cm_cnn_front_args *args, const int32_t *f
     CM_REQUIRE(frames != nullptr, CM_EINVAL, "cnn_front_lens: frames is NULL (cm_cnn_front is the form without lengths)");
     CM_REQUIRE(cm_aligned(frames, 4), CM_EALIGN, "cnn_front_lens: frames must be 4-byte aligned");
     const cm_cnn_front_args &a = *args;
-    CM_REQUIRE(a.batch > 0 && a.T >= 5 && a.feats && a.w1 && a.ln1_g && a.ln1_b && a.w2 && a.ln2_g && a.ln2_b && a.out, CM_EINVAL,
-               "cnn_front_lens: bad sizes or NULL tensor");
-    CM_REQUIRE(a.F == F0 && a.C1 == C1 && a.C2 == C2, CM_EUNSUPPORTED, "cnn_front_lens: only 80 bins, channels (64, 32) (got F %d, C %d, %d)", a.F,
-               a.C1, a.C2);
-    CM_REQUIRE(cm_aligned(a.w2, 16) && cm_aligned(a.out, 4) && cm_aligned(a.ln1_g, 8) && cm_aligned(a.ln1_b, 8) && cm_aligned(a.ln2_g, 8) &&
-                   cm_aligned(a.ln2_b, 8) && (!a.b2 || cm_aligned(a.b2, 16)),
-               CM_EALIGN, "cnn_front_lens: w2 / b2 must be 16-byte aligned, LayerNorm parameters 8-byte aligned");
-    // the grid and the chunks are those of the widest utterance; a chunk past an utterance's own tiles is skipped
-    const int T1 = (a.T + 1) / 2, T2 = (T1 + 2 - 3) / 2 + 1;
-    const int tiles_per_utt = (T2 + TT - 1) / TT;
-    const int chunk = 16;
-    const int chunks_per_utt = (tiles_per_utt + chunk - 1) / chunk;
-    const int64_t nchunks = (int64_t)a.batch * chunks_per_utt;
-    CM_REQUIRE(nchunks <= 2147483647, CM_EINVAL, "cnn_front_lens: too many chunks");
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(cnn_front_kernel<false, cf_lens_args>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e != hipSuccess) {
-            cm_set_error("cnn_front_lens: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        attr_done = true;
-    }
+    if (int rc = cnn_front_check(a, a.T >= 5, "cnn_front_lens")) return rc;
     cf_lens_args k{};
     static_cast<cm_cnn_front_args &>(k) = a;
     k.frames = frames;
-    const int64_t grid = nchunks < 256 ? nchunks : 256;
-    hipLaunchKernelGGL((cnn_front_kernel<false, cf_lens_args>), dim3((unsigned)grid), dim3(512), sizeof(front_lds),
-                       reinterpret_cast<hipStream_t>(a.stream), k, a.T, T1, T2, tiles_per_utt, chunk, chunks_per_utt, (int)nchunks);
-    return cm_launch_status("cm_cnn_front_lens");
+    const int T1 = (a.T + 1) / 2, T2 = (T1 + 2 - 3) / 2 + 1;       // of the widest utterance
+    return cnn_front_launch<false>(k, T2, a.T, T1, T2, "cm_cnn_front_lens");
 }
 
 extern "C" int cm_cnn_front_stream(const cm_cnn_front_stream_args *args) {
     CM_REQUIRE(args != nullptr, CM_EINVAL, "cnn_front_stream: args is NULL");
     const cm_cnn_front_stream_args &a = *args;
-    CM_REQUIRE(a.batch > 0 && a.nf > 0 && a.nr > 0 && a.f0 >= 0 && a.r0 >= 0 && a.feats && a.w1 && a.ln1_g && a.ln1_b && a.w2 && a.ln2_g && a.ln2_b &&
-                   a.out, CM_EINVAL, "cnn_front_stream: bad sizes or NULL tensor");
-    CM_REQUIRE(a.F == F0 && a.C1 == C1 && a.C2 == C2, CM_EUNSUPPORTED, "cnn_front_stream: only 80 bins, channels (64, 32) (got F %d, C %d, %d)", a.F,
-               a.C1, a.C2);
-    CM_REQUIRE(cm_aligned(a.w2, 16) && cm_aligned(a.out, 4) && cm_aligned(a.ln1_g, 8) && cm_aligned(a.ln1_b, 8) && cm_aligned(a.ln2_g, 8) &&
-                   cm_aligned(a.ln2_b, 8) && (!a.b2 || cm_aligned(a.b2, 16)),
-               CM_EALIGN, "cnn_front_stream: w2 / b2 must be 16-byte aligned, LayerNorm parameters 8-byte aligned");
-    const int64_t fend = (int64_t)a.f0 + a.nf, rend = (int64_t)a.r0 + a.nr;
-    CM_REQUIRE(fend < T_OPEN, CM_EUNSUPPORTED, "cnn_front_stream: frame index too large");
-    int T = T_OPEN, T1 = T_OPEN;
-    if (a.T_total >= 0) {                                         // the call ends the utterance: rows up to T2 - 1, reflected at T and T1
-        CM_REQUIRE(a.T_total >= 5 && a.T_total == fend, CM_EINVAL, "cnn_front_stream: T_total must be f0 + nf and at least 5");
-        T = a.T_total;
-        T1 = (T + 1) / 2;
-        CM_REQUIRE(rend <= (T1 + 1) / 2, CM_EINVAL, "cnn_front_stream: row %d is past the utterance's last", (int)rend - 1);
-    } else {
-        CM_REQUIRE(4 * (rend - 1) + 3 < fend, CM_EINVAL, "cnn_front_stream: row %d needs frames that have not arrived", (int)rend - 1);
-    }
-    // the lowest frame a row of the launch names: 4 r0 - 3 (reflected at 0), or T - 5 through the reflections at the end
-    const int64_t lowest = std::min<int64_t>(std::max<int64_t>(4 * (int64_t)a.r0 - 3, 0), a.T_total >= 0 ? (int64_t)a.T_total - 5 : fend);
-    CM_REQUIRE(lowest >= (a.feat_hist ? (int64_t)a.f0 - FH : (int64_t)a.f0), CM_EINVAL, "cnn_front_stream: row %d reaches behind the feature history", a.r0);
-    const int tiles_per_utt = (a.nr + TT - 1) / TT;
-    const int chunk = 16;
-    const int chunks_per_utt = (tiles_per_utt + chunk - 1) / chunk;
-    const int64_t nchunks = (int64_t)a.batch * chunks_per_utt;
-    CM_REQUIRE(nchunks <= 2147483647, CM_EINVAL, "cnn_front_stream: too many chunks");
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(cnn_front_kernel<true, cm_cnn_front_stream_args>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e != hipSuccess) {
-            cm_set_error("cnn_front_stream: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        attr_done = true;
-    }
-    const int64_t grid = nchunks < 256 ? nchunks : 256;
-    hipLaunchKernelGGL((cnn_front_kernel<true, cm_cnn_front_stream_args>), dim3((unsigned)grid), dim3(512), sizeof(front_lds),
-                       reinterpret_cast<hipStream_t>(a.stream), a, T, T1, (int)rend, tiles_per_utt, chunk, chunks_per_utt, (int)nchunks);
-    return cm_launch_status("cm_cnn_front_stream");
+    if (int rc = cnn_front_check(a, a.nf > 0 && a.nr > 0 && a.f0 >= 0 && a.r0 >= 0, "cnn_front_stream")) return rc;
+    CM_REQUIRE((int64_t)a.f0 + a.nf < T_OPEN, CM_EUNSUPPORTED, "cnn_front_stream: frame index too large");
+    if (int rc = cnn_front_stream_check(a.f0, a.nf, a.r0, a.nr, a.T_total, a.feat_hist != nullptr, "cnn_front_stream", -1)) return rc;
+    const int T = a.T_total >= 0 ? a.T_total : T_OPEN, T1 = a.T_total >= 0 ? (T + 1) / 2 : T_OPEN;
+    return cnn_front_launch<true>(a, a.nr, T, T1, a.r0 + a.nr, "cm_cnn_front_stream");
 }
 
+// The struct's nf and nr are the maxima over the slots; its f0 / r0 / T_total are not read.  A slot without rows is not checked further.
 extern "C" int cm_cnn_front_stream_slots(const cm_cnn_front_stream_args *args, const int32_t *plan_host, const int32_t *plan_dev) {
     CM_REQUIRE(args != nullptr, CM_EINVAL, "cnn_front_stream_slots: args is NULL");
     CM_REQUIRE(plan_host != nullptr && plan_dev != nullptr, CM_EINVAL, "cnn_front_stream_slots: plan is NULL (host copy and device copy)");
     CM_REQUIRE(cm_aligned(plan_host, 4) && cm_aligned(plan_dev, 4), CM_EALIGN, "cnn_front_stream_slots: plan must be 4-byte aligned");
     const cm_cnn_front_stream_args &a = *args;
-    CM_REQUIRE(a.batch > 0 && a.nf > 0 && a.nr > 0 && a.feats && a.w1 && a.ln1_g && a.ln1_b && a.w2 && a.ln2_g && a.ln2_b && a.out, CM_EINVAL,
-               "cnn_front_stream_slots: bad sizes or NULL tensor");
-    CM_REQUIRE(a.F == F0 && a.C1 == C1 && a.C2 == C2, CM_EUNSUPPORTED, "cnn_front_stream_slots: only 80 bins, channels (64, 32) (got F %d, C %d, %d)",
-               a.F, a.C1, a.C2);
-    CM_REQUIRE(cm_aligned(a.w2, 16) && cm_aligned(a.out, 4) && cm_aligned(a.ln1_g, 8) && cm_aligned(a.ln1_b, 8) && cm_aligned(a.ln2_g, 8) &&
-                   cm_aligned(a.ln2_b, 8) && (!a.b2 || cm_aligned(a.b2, 16)),
-               CM_EALIGN, "cnn_front_stream_slots: w2 / b2 must be 16-byte aligned, LayerNorm parameters 8-byte aligned");
-    for (int b = 0; b < a.batch; ++b) {                           // cm_cnn_front_stream's conditions on every slot that has a row
-        const int32_t *s = plan_host + (int64_t)b * 8;
-        const int64_t f0 = s[3], nf = s[4], r0 = s[5], nr = s[6], Tt = s[7];
+    if (int rc = cnn_front_check(a, a.nf > 0 && a.nr > 0, "cnn_front_stream_slots")) return rc;
+    for (int b = 0; b < a.batch; ++b) {
+        const int32_t *s = plan_host + (int64_t)b * PL_W;
+        const int64_t f0 = s[PL_F0], nf = s[PL_NF], r0 = s[PL_R0], nr = s[PL_NR];
         CM_REQUIRE(f0 >= 0 && nf >= 0 && r0 >= 0 && nr >= 0 && nf <= a.nf && nr <= a.nr, CM_EINVAL,
                    "cnn_front_stream_slots: slot %d: counts below 0 or above the maxima (nf %d of %d, nr %d of %d)", b, (int)nf, a.nf, (int)nr, a.nr);
         if (nr == 0) continue;
-        const int64_t fend = f0 + nf, rend = r0 + nr;
-        CM_REQUIRE(nf > 0 && fend < T_OPEN, CM_EINVAL, "cnn_front_stream_slots: slot %d has rows but no frames, or a frame index too large", b);
-        if (Tt >= 0) {
-            CM_REQUIRE(Tt >= 5 && Tt == fend, CM_EINVAL, "cnn_front_stream_slots: slot %d: T_total must be f0 + nf and at least 5", b);
-            CM_REQUIRE(rend <= ((Tt + 1) / 2 + 1) / 2, CM_EINVAL, "cnn_front_stream_slots: slot %d: row %d is past the utterance's last", b, (int)rend - 1);
-        } else {
-            CM_REQUIRE(4 * (rend - 1) + 3 < fend, CM_EINVAL, "cnn_front_stream_slots: slot %d: row %d needs frames that have not arrived", b, (int)rend - 1);
-        }
-        const int64_t lowest = std::min<int64_t>(std::max<int64_t>(4 * r0 - 3, 0), Tt >= 0 ? Tt - 5 : fend);
-        CM_REQUIRE(lowest >= (a.feat_hist ? f0 - FH : f0), CM_EINVAL, "cnn_front_stream_slots: slot %d: row %d reaches behind the feature history", b, (int)r0);
-    }
-    const int tiles_per_utt = (a.nr + TT - 1) / TT;
-    const int chunk = 16;
-    const int chunks_per_utt = (tiles_per_utt + chunk - 1) / chunk;
-    const int64_t nchunks = (int64_t)a.batch * chunks_per_utt;
-    CM_REQUIRE(nchunks <= 2147483647, CM_EINVAL, "cnn_front_stream_slots: too many chunks");
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(cnn_front_kernel<true, cf_slot_args>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e != hipSuccess) {
-            cm_set_error("cnn_front_stream_slots: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        attr_done = true;
+        CM_REQUIRE(nf > 0 && f0 + nf < T_OPEN, CM_EINVAL, "cnn_front_stream_slots: slot %d has rows but no frames, or a frame index too large", b);
+        if (int rc = cnn_front_stream_check(f0, nf, r0, nr, s[PL_TTOTAL], a.feat_hist != nullptr, "cnn_front_stream_slots", b)) return rc;
     }
     cf_slot_args k{};
     static_cast<cm_cnn_front_stream_args &>(k) = a;
     k.plan = plan_dev;
-    const int64_t grid = nchunks < 256 ? nchunks : 256;
-    hipLaunchKernelGGL((cnn_front_kernel<true, cf_slot_args>), dim3((unsigned)grid), dim3(512), sizeof(front_lds),
-                       reinterpret_cast<hipStream_t>(a.stream), k, T_OPEN, T_OPEN, 0, tiles_per_utt, chunk, chunks_per_utt, (int)nchunks);
-    return cm_launch_status("cm_cnn_front_stream_slots");
+    return cnn_front_launch<true>(k, a.nr, T_OPEN, T_OPEN, 0, "cm_cnn_front_stream_slots");
 }

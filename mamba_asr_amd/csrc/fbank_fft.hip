@@ -15,6 +15,7 @@
 //   * outputs land in base-4 digit-reversed order, so lane l finds Z[l + 64 i], i = 0..3, in 32 contiguous bytes;
 //   * |X[k]|^2 goes to the [bin][frame] power tile in LDS and the mel / dB stage of cm_fbank_mel_db runs unchanged.
 #include "cm_common.h"
+#include "front_plan.h"
 
 #include <type_traits>
 
@@ -25,7 +26,6 @@ constexpr int PWS = FT + 1;       // power-tile row stride (odd: conflict-free m
 constexpr int NF = 512;           // n_fft
 constexpr int NH = NF / 2;        // complex FFT length
 constexpr int HS = NF;            // cm_fbank_wav_stream: samples of history per stream (a frame reaches back fewer than n_fft)
-constexpr int FH = 8;             // cm_fbank_finish_stream: feature rows of history per stream (a row reaches back at most 6)
 constexpr int BWCAP = 1024;       // band weights staged in LDS (triangular filters: <= 2 per bin = 514 for 257 bins); a larger
                                   // table is read from global memory instead.  4 KB instead of the table's 16 KB bound: a
                                   // workgroup holds 32.5 KB of LDS and four of them (16 waves) share a CU
@@ -76,17 +76,18 @@ struct fb_slot_args : cm_fbank_stream_args {
 struct fb_lens_args : cm_fbank_args {
     const int32_t *nsamp;
 };
-enum { PL_N = 0, PL_CONSUMED = 1, PL_TOTAL = 2, PL_F0 = 3, PL_NF = 4, PL_R0 = 5, PL_NR = 6, PL_TTOTAL = 7, PL_W = 8 };
+// the arguments with the counts of row b of a plan table (front_plan.h) in place of the struct's own
+template <typename ARGS>
+__host__ __device__ __forceinline__ ARGS fb_row_view(const ARGS &pk, const int32_t *plan, int b) {
+    ARGS q = pk;
+    const int32_t *s = plan + (int64_t)b * PL_W;
+    q.n = s[PL_N], q.consumed = s[PL_CONSUMED], q.total = s[PL_TOTAL], q.f0 = s[PL_F0], q.nf = s[PL_NF];
+    return q;
+}
 template <typename ARGS>
 __device__ __forceinline__ ARGS fb_view(const ARGS &pk, int b) {      // the arguments as stream b sees them
-    if constexpr (std::is_same<ARGS, fb_slot_args>::value) {
-        ARGS q = pk;
-        const int32_t *s = pk.plan + (int64_t)b * PL_W;
-        q.n = s[PL_N], q.consumed = s[PL_CONSUMED], q.total = s[PL_TOTAL], q.f0 = s[PL_F0], q.nf = s[PL_NF];
-        return q;
-    } else {
-        return pk;
-    }
+    if constexpr (std::is_same<ARGS, fb_slot_args>::value) return fb_row_view(pk, pk.plan, b);
+    else return pk;
 }
 
 template <bool STREAM, typename ARGS>
@@ -295,23 +296,35 @@ __global__ __launch_bounds__(256) void fbank_wav_kernel(const ARGS pk, const flo
         if (tid == 0) p.umax_part[(int64_t)b * gridDim.x + blockIdx.x] = fmaxf(fmaxf(pw[0], pw[1]), fmaxf(pw[2], pw[3]));
 }
 
-// cm_fbank_finish_lens: cm_fbank_finish's kernel (frontend.hip) with the utterance's own frame count -- the maximum over the tiles
-// that hold its frames [0, T_b) (fbank_wav_kernel<false, fb_lens_args> kept the frames behind them out of the last one), the clamp
-// and the normalisation on those frames only.  grid (chunks, batch).
-__global__ __launch_bounds__(256) void fbank_finish_lens_kernel(const fb_lens_args p, int ntiles) {
+// cm_fbank_finish / cm_fbank_finish_lens, grid (chunks, batch): a workgroup first reduces its utterance's tile maxima (when umax_part is
+// given; cm_fbank_mel_db without it left the maximum in umax), then clamps and normalises its slice of the utterance.  ARGS =
+// fb_lens_args: the utterance's own frame count -- the maximum over the tiles that hold its frames [0, T_b) (fbank_wav_kernel<false,
+// fb_lens_args> kept the frames behind them out of the last one), the clamp and the normalisation on those frames only.
+template <typename ARGS>
+__global__ __launch_bounds__(256) void fbank_finish_kernel(const ARGS p, int ntiles) {
+    constexpr bool LENS = std::is_same<ARGS, fb_lens_args>::value;
     __shared__ float red[4];
     const int b = blockIdx.y;
-    const int nsv = min(max(p.nsamp[b], 0), p.samples), Tb = nsv > 0 ? 1 + nsv / p.hop : 0;
-    if (Tb == 0) return;
-    const int nt = (Tb + FT - 1) / FT;
-    float mx = -INFINITY;
-    for (int i = threadIdx.x; i < nt; i += blockDim.x) mx = fmaxf(mx, p.umax_part[(int64_t)b * ntiles + i]);
+    int Tb = p.frames, nt = ntiles;                               // the utterance's frames and the tiles that hold them
+    if constexpr (LENS) {
+        const int nsv = min(max(p.nsamp[b], 0), p.samples);
+        Tb = nsv > 0 ? 1 + nsv / p.hop : 0;
+        if (Tb == 0) return;
+        nt = (Tb + FT - 1) / FT;
+    }
+    float um;
+    if (LENS || p.umax_part) {
+        float mx = -INFINITY;
+        for (int i = threadIdx.x; i < nt; i += blockDim.x) mx = fmaxf(mx, p.umax_part[(int64_t)b * ntiles + i]);
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    const float um = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    if (blockIdx.x == 0 && threadIdx.x == 0) p.umax[b] = um;
+        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+        __syncthreads();
+        um = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        if (blockIdx.x == 0 && threadIdx.x == 0) p.umax[b] = um;
+    } else {
+        um = p.umax[b];
+    }
     const float floor_db = um - p.top_db;
     const int64_t per_utt = (int64_t)Tb * p.n_mels;
     float *db = p.db + (int64_t)b * p.frames * p.n_mels;
@@ -374,10 +387,23 @@ __global__ __launch_bounds__(256) void fbank_finish_slots_kernel(const fb_slot_a
     if (threadIdx.x == 0) p.umax[b] = run;
 }
 
-}  // namespace
+// ---- host side.  `sym` is an entry point's symbol, `who` = sym + 3 the name its messages begin with (no "cm_").
 
-// cm_fbank_wav (nsamp == NULL) and cm_fbank_wav_lens: one set of checks
-static int fbank_wav_entry(const cm_fbank_args &a, const int32_t *nsamp) {
+size_t fbank_wav_smem(int n_mels) {                               // power tile, band table, band weights, four FFT buffers
+    return (size_t)(NH + 1) * PWS * 4 + (size_t)(3 * n_mels + 1) * 4 + (size_t)BWCAP * 4 + (size_t)4 * ZN * 8 + 4;
+}
+float fbank_floor_db(float amin) { return (float)(10.0 * log10((double)amin)); }
+
+template <typename ARGS>
+int fbank_wav_launch(const ARGS &k, const char *sym) {
+    dim3 grid((k.frames + FT - 1) / FT, k.batch);
+    hipLaunchKernelGGL((fbank_wav_kernel<false, ARGS>), grid, dim3(256), fbank_wav_smem(k.n_mels), reinterpret_cast<hipStream_t>(k.stream), k,
+                       fbank_floor_db(k.amin));
+    return cm_launch_status(sym);
+}
+
+// cm_fbank_wav (nsamp == NULL) and cm_fbank_wav_lens: one set of checks, under the name of the form without lengths
+int fbank_wav_entry(const cm_fbank_args &a, const int32_t *nsamp) {
     CM_REQUIRE(a.batch > 0 && a.frames > 0 && a.n_mels > 0 && a.wav && a.window && a.twiddle && a.db && a.umax_part && a.band_lo &&
                    a.band_hi && a.band_off && a.band_w, CM_EINVAL, "fbank_wav: bad sizes or NULL tensor");
     CM_REQUIRE(a.n_fft == NF && a.n_freq == NH + 1, CM_EUNSUPPORTED, "fbank_wav: n_fft %d unsupported (512 only)", a.n_fft);
@@ -386,60 +412,44 @@ static int fbank_wav_entry(const cm_fbank_args &a, const int32_t *nsamp) {
                "fbank_wav: hop and the batch stride must be even, wav / window / twiddle 8-byte aligned");
     CM_REQUIRE(a.frames == 1 + a.samples / a.hop, CM_EINVAL, "fbank_wav: frames must be 1 + samples / hop (center=True)");
     CM_REQUIRE(a.batch <= 65535 && a.n_mels <= 128, CM_EUNSUPPORTED, "fbank_wav: batch / n_mels too large");
-    const size_t smem = (size_t)(NH + 1) * PWS * 4 + (size_t)(3 * a.n_mels + 1) * 4 + (size_t)BWCAP * 4 + (size_t)4 * ZN * 8 + 4;
-    dim3 grid((a.frames + FT - 1) / FT, a.batch);
+    if (!nsamp) return fbank_wav_launch(a, "cm_fbank_wav");
+    fb_lens_args k{};
+    static_cast<cm_fbank_args &>(k) = a;
+    k.nsamp = nsamp;
+    return fbank_wav_launch(k, "cm_fbank_wav_lens");
+}
+
+// cm_fbank_finish (nsamp == NULL; umax_part optional) and cm_fbank_finish_lens (umax_part required, and the frame count it is read by)
+int fbank_finish_entry(const cm_fbank_args &a, const int32_t *nsamp, const char *sym) {
+    const char *who = sym + 3;
+    CM_REQUIRE(a.batch > 0 && a.frames > 0 && a.n_mels > 0 && a.db && a.umax && (!nsamp || a.umax_part), CM_EINVAL, "%s: bad sizes or NULL tensor%s",
+               who, nsamp ? " (umax_part included)" : "");
+    CM_REQUIRE(!nsamp || (a.hop > 0 && a.samples > 0 && a.frames == 1 + a.samples / a.hop), CM_EINVAL, "%s: frames must be 1 + samples / hop", who);
+    CM_REQUIRE(!a.mean || a.std, CM_EINVAL, "%s: mean without std", who);
+    CM_REQUIRE(a.batch <= 65535, CM_EINVAL, "%s: batch %d exceeds the grid limit", who, a.batch);
+    const int64_t per_utt = (int64_t)a.frames * a.n_mels;
+    int64_t chunks = (per_utt + 256 * 8 - 1) / (256 * 8);
+    if (chunks > 256) chunks = 256;
+    const dim3 grid((unsigned)chunks, a.batch);
+    const int ntiles = (a.frames + FT - 1) / FT;
     if (nsamp) {
         fb_lens_args k{};
         static_cast<cm_fbank_args &>(k) = a;
         k.nsamp = nsamp;
-        hipLaunchKernelGGL((fbank_wav_kernel<false, fb_lens_args>), grid, dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), k,
-                           (float)(10.0 * log10((double)a.amin)));
-        return cm_launch_status("cm_fbank_wav_lens");
+        hipLaunchKernelGGL(fbank_finish_kernel<fb_lens_args>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(a.stream), k, ntiles);
+    } else {
+        hipLaunchKernelGGL(fbank_finish_kernel<cm_fbank_args>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(a.stream), a, ntiles);
     }
-    hipLaunchKernelGGL((fbank_wav_kernel<false, cm_fbank_args>), grid, dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), a,
-                       (float)(10.0 * log10((double)a.amin)));
-    return cm_launch_status("cm_fbank_wav");
+    return cm_launch_status(sym);
 }
 
-extern "C" int cm_fbank_wav(const cm_fbank_args *args) {
-    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_wav: args is NULL");
-    return fbank_wav_entry(*args, nullptr);
-}
-
-extern "C" int cm_fbank_wav_lens(const cm_fbank_args *args, const int32_t *n_samples) {
-    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_wav_lens: args is NULL");
-    CM_REQUIRE(n_samples != nullptr, CM_EINVAL, "fbank_wav_lens: n_samples is NULL (cm_fbank_wav is the form without lengths)");
-    CM_REQUIRE(cm_aligned(n_samples, 4), CM_EALIGN, "fbank_wav_lens: n_samples must be 4-byte aligned");
-    return fbank_wav_entry(*args, n_samples);
-}
-
-extern "C" int cm_fbank_finish_lens(const cm_fbank_args *args, const int32_t *n_samples) {
-    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_finish_lens: args is NULL");
-    CM_REQUIRE(n_samples != nullptr, CM_EINVAL, "fbank_finish_lens: n_samples is NULL (cm_fbank_finish is the form without lengths)");
-    CM_REQUIRE(cm_aligned(n_samples, 4), CM_EALIGN, "fbank_finish_lens: n_samples must be 4-byte aligned");
-    const cm_fbank_args &a = *args;
-    CM_REQUIRE(a.batch > 0 && a.frames > 0 && a.n_mels > 0 && a.db && a.umax && a.umax_part, CM_EINVAL, "fbank_finish_lens: bad sizes or NULL tensor (umax_part included)");
-    CM_REQUIRE(a.hop > 0 && a.samples > 0 && a.frames == 1 + a.samples / a.hop, CM_EINVAL, "fbank_finish_lens: frames must be 1 + samples / hop");
-    CM_REQUIRE(!a.mean || a.std, CM_EINVAL, "fbank_finish_lens: mean without std");
-    CM_REQUIRE(a.batch <= 65535, CM_EINVAL, "fbank_finish_lens: batch %d exceeds the grid limit", a.batch);
-    const int64_t per_utt = (int64_t)a.frames * a.n_mels;
-    int64_t chunks = (per_utt + 256 * 8 - 1) / (256 * 8);
-    if (chunks > 256) chunks = 256;
-    fb_lens_args k{};
-    static_cast<cm_fbank_args &>(k) = a;
-    k.nsamp = n_samples;
-    hipLaunchKernelGGL(fbank_finish_lens_kernel, dim3((unsigned)chunks, a.batch), dim3(256), 0, reinterpret_cast<hipStream_t>(a.stream), k,
-                       (a.frames + FT - 1) / FT);
-    return cm_launch_status("cm_fbank_finish_lens");
-}
-
-namespace {
 bool overlap(const void *a, const void *b, size_t bytes) {
     const char *x = static_cast<const char *>(a), *y = static_cast<const char *>(b);
     return x < y + bytes && y < x + bytes;
 }
-// the checks both stream entry points share (cm_fbank_finish_stream reads no sample: the sample counts are cm_fbank_wav_stream's);
-// nothing is launched before they pass
+
+// The checks on one stream's counts that the stream entry points share (cm_fbank_finish_stream reads no sample: the sample counts are
+// cm_fbank_wav_stream's): the struct's own scalars, or a row of the per-slot plan in their place.  Nothing is launched before they pass.
 int fbank_stream_check(const cm_fbank_stream_args &a, const char *who, bool samples) {
     CM_REQUIRE(a.batch > 0 && a.n_mels > 0 && a.nf >= 0 && a.f0 >= 0, CM_EINVAL, "%s: bad sizes", who);
     CM_REQUIRE(a.n_fft == NF, CM_EUNSUPPORTED, "%s: n_fft %d unsupported (512 only)", who, a.n_fft);
@@ -455,93 +465,108 @@ int fbank_stream_check(const cm_fbank_stream_args &a, const char *who, bool samp
     CM_REQUIRE(a.nf == 0 || (int64_t)a.hop * a.f0 - NH >= (int64_t)a.consumed - HS, CM_EINVAL, "%s: frame %d reaches behind the history", who, a.f0);
     return CM_OK;
 }
+
+// What the per-slot entry points ask first: the plan's two copies, then every slot's counts through fbank_stream_check and under the
+// struct's maxima
+int fbank_slots_check(const cm_fbank_stream_args *args, const int32_t *plan_host, const int32_t *plan_dev, const char *who, bool samples) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "%s: args is NULL", who);
+    CM_REQUIRE(plan_host != nullptr && plan_dev != nullptr, CM_EINVAL, "%s: plan is NULL (host copy and device copy)", who);
+    CM_REQUIRE(cm_aligned(plan_host, 4) && cm_aligned(plan_dev, 4), CM_EALIGN, "%s: plan must be 4-byte aligned", who);
+    const cm_fbank_stream_args &a = *args;
+    CM_REQUIRE(a.batch > 0 && (!samples || (a.n >= 0 && a.nf >= 0)), CM_EINVAL, "%s: bad sizes", who);
+    for (int b = 0; b < a.batch; ++b) {
+        const cm_fbank_stream_args q = fb_row_view(a, plan_host, b);
+        if (int rc = fbank_stream_check(q, who, samples)) return rc;
+        if (samples) CM_REQUIRE(q.n <= a.n && q.nf <= a.nf, CM_EINVAL, "%s: slot %d has n %d / nf %d above the maxima %d / %d", who, b, q.n, q.nf, a.n, a.nf);
+        else CM_REQUIRE(q.nf <= a.nf, CM_EINVAL, "%s: slot %d has nf %d above the maximum %d", who, b, q.nf, a.nf);
+    }
+    return CM_OK;
+}
+
+// cm_fbank_wav_stream and its per-slot form behind their own checks of the counts
+template <typename ARGS>
+int fbank_wav_stream_run(const ARGS &k, const char *sym) {
+    const cm_fbank_stream_args &a = k;
+    const char *who = sym + 3;
+    CM_REQUIRE(a.hist && a.hist_out && (a.n == 0 || a.chunk), CM_EINVAL, "%s: NULL chunk / hist / hist_out", who);
+    CM_REQUIRE(!overlap(a.hist, a.hist_out, (size_t)a.batch * HS * 4), CM_EINVAL, "%s: hist_out overlaps hist", who);
+    CM_REQUIRE(a.nf == 0 || (a.window && a.twiddle && a.db && a.fmax && a.band_lo && a.band_hi && a.band_off && a.band_w), CM_EINVAL,
+               "%s: NULL tensor", who);
+    CM_REQUIRE(a.nf == 0 || (cm_aligned(a.window, 8) && cm_aligned(a.twiddle, 8)), CM_EALIGN, "%s: window / twiddle must be 8-byte aligned", who);
+    dim3 grid(a.nf ? (a.nf + FT - 1) / FT : 1, a.batch);
+    hipLaunchKernelGGL((fbank_wav_kernel<true, ARGS>), grid, dim3(256), fbank_wav_smem(a.n_mels), reinterpret_cast<hipStream_t>(a.stream), k,
+                       fbank_floor_db(a.amin));
+    return cm_launch_status(sym);
+}
+
+// ... and cm_fbank_finish_stream and its per-slot form
+template <typename ARGS>
+int fbank_finish_stream_run(const ARGS &k, const char *sym) {
+    const cm_fbank_stream_args &a = k;
+    const char *who = sym + 3;
+    CM_REQUIRE(a.nf > 0 && a.db && a.fmax && a.umax, CM_EINVAL, "%s: no frames or NULL db / fmax / umax", who);
+    CM_REQUIRE(!a.mean == !a.std, CM_EINVAL, "%s: mean and std go together", who);
+    CM_REQUIRE(!a.feat_hist_out || !a.feat_hist || !overlap(a.feat_hist, a.feat_hist_out, (size_t)a.batch * FH * a.n_mels * 4), CM_EINVAL,
+               "%s: feat_hist_out overlaps feat_hist", who);
+    CM_REQUIRE(a.feat_hist_out || !a.feat_hist, CM_EINVAL, "%s: feat_hist without feat_hist_out", who);
+    if constexpr (std::is_same<ARGS, fb_slot_args>::value)
+        hipLaunchKernelGGL(fbank_finish_slots_kernel, dim3(a.batch), dim3(256), 0, reinterpret_cast<hipStream_t>(a.stream), k);
+    else
+        hipLaunchKernelGGL(fbank_finish_stream_kernel, dim3(a.batch), dim3(256), 0, reinterpret_cast<hipStream_t>(a.stream), k);
+    return cm_launch_status(sym);
+}
+
+fb_slot_args fb_with_plan(const cm_fbank_stream_args &a, const int32_t *plan_dev) {
+    fb_slot_args k{};
+    static_cast<cm_fbank_stream_args &>(k) = a;
+    k.plan = plan_dev;
+    return k;
+}
+
 }  // namespace
+
+extern "C" int cm_fbank_wav(const cm_fbank_args *args) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_wav: args is NULL");
+    return fbank_wav_entry(*args, nullptr);
+}
+
+extern "C" int cm_fbank_wav_lens(const cm_fbank_args *args, const int32_t *n_samples) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_wav_lens: args is NULL");
+    CM_REQUIRE(n_samples != nullptr, CM_EINVAL, "fbank_wav_lens: n_samples is NULL (cm_fbank_wav is the form without lengths)");
+    CM_REQUIRE(cm_aligned(n_samples, 4), CM_EALIGN, "fbank_wav_lens: n_samples must be 4-byte aligned");
+    return fbank_wav_entry(*args, n_samples);
+}
+
+extern "C" int cm_fbank_finish(const cm_fbank_args *args) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_finish: args is NULL");
+    return fbank_finish_entry(*args, nullptr, "cm_fbank_finish");
+}
+
+extern "C" int cm_fbank_finish_lens(const cm_fbank_args *args, const int32_t *n_samples) {
+    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_finish_lens: args is NULL");
+    CM_REQUIRE(n_samples != nullptr, CM_EINVAL, "fbank_finish_lens: n_samples is NULL (cm_fbank_finish is the form without lengths)");
+    CM_REQUIRE(cm_aligned(n_samples, 4), CM_EALIGN, "fbank_finish_lens: n_samples must be 4-byte aligned");
+    return fbank_finish_entry(*args, n_samples, "cm_fbank_finish_lens");
+}
 
 extern "C" int cm_fbank_wav_stream(const cm_fbank_stream_args *args) {
     CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_wav_stream: args is NULL");
-    const cm_fbank_stream_args &a = *args;
-    if (int rc = fbank_stream_check(a, "fbank_wav_stream", true)) return rc;
-    CM_REQUIRE(a.hist && a.hist_out && (a.n == 0 || a.chunk), CM_EINVAL, "fbank_wav_stream: NULL chunk / hist / hist_out");
-    CM_REQUIRE(!overlap(a.hist, a.hist_out, (size_t)a.batch * HS * 4), CM_EINVAL, "fbank_wav_stream: hist_out overlaps hist");
-    CM_REQUIRE(a.nf == 0 || (a.window && a.twiddle && a.db && a.fmax && a.band_lo && a.band_hi && a.band_off && a.band_w), CM_EINVAL,
-               "fbank_wav_stream: NULL tensor");
-    CM_REQUIRE(a.nf == 0 || (cm_aligned(a.window, 8) && cm_aligned(a.twiddle, 8)), CM_EALIGN, "fbank_wav_stream: window / twiddle must be 8-byte aligned");
-    const size_t smem = (size_t)(NH + 1) * PWS * 4 + (size_t)(3 * a.n_mels + 1) * 4 + (size_t)BWCAP * 4 + (size_t)4 * ZN * 8 + 4;
-    dim3 grid(a.nf ? (a.nf + FT - 1) / FT : 1, a.batch);
-    hipLaunchKernelGGL((fbank_wav_kernel<true, cm_fbank_stream_args>), grid, dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), a,
-                       (float)(10.0 * log10((double)a.amin)));
-    return cm_launch_status("cm_fbank_wav_stream");
+    if (int rc = fbank_stream_check(*args, "fbank_wav_stream", true)) return rc;
+    return fbank_wav_stream_run(*args, "cm_fbank_wav_stream");
 }
 
 extern "C" int cm_fbank_finish_stream(const cm_fbank_stream_args *args) {
     CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_finish_stream: args is NULL");
-    const cm_fbank_stream_args &a = *args;
-    if (int rc = fbank_stream_check(a, "fbank_finish_stream", false)) return rc;
-    CM_REQUIRE(a.nf > 0 && a.db && a.fmax && a.umax, CM_EINVAL, "fbank_finish_stream: no frames or NULL db / fmax / umax");
-    CM_REQUIRE(!a.mean == !a.std, CM_EINVAL, "fbank_finish_stream: mean and std go together");
-    CM_REQUIRE(!a.feat_hist_out || !a.feat_hist || !overlap(a.feat_hist, a.feat_hist_out, (size_t)a.batch * FH * a.n_mels * 4), CM_EINVAL,
-               "fbank_finish_stream: feat_hist_out overlaps feat_hist");
-    CM_REQUIRE(a.feat_hist_out || !a.feat_hist, CM_EINVAL, "fbank_finish_stream: feat_hist without feat_hist_out");
-    hipLaunchKernelGGL(fbank_finish_stream_kernel, dim3(a.batch), dim3(256), 0, reinterpret_cast<hipStream_t>(a.stream), a);
-    return cm_launch_status("cm_fbank_finish_stream");
+    if (int rc = fbank_stream_check(*args, "fbank_finish_stream", false)) return rc;
+    return fbank_finish_stream_run(*args, "cm_fbank_finish_stream");
 }
-
-
-namespace {
-// the per-slot entry points' view of slot b for the host checks: the lock-step struct with that slot's scalars
-cm_fbank_stream_args fb_host_view(const cm_fbank_stream_args &a, const int32_t *plan, int b) {
-    cm_fbank_stream_args q = a;
-    const int32_t *s = plan + (int64_t)b * PL_W;
-    q.n = s[PL_N], q.consumed = s[PL_CONSUMED], q.total = s[PL_TOTAL], q.f0 = s[PL_F0], q.nf = s[PL_NF];
-    return q;
-}
-}  // namespace
 
 extern "C" int cm_fbank_wav_stream_slots(const cm_fbank_stream_args *args, const int32_t *plan_host, const int32_t *plan_dev) {
-    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_wav_stream_slots: args is NULL");
-    CM_REQUIRE(plan_host != nullptr && plan_dev != nullptr, CM_EINVAL, "fbank_wav_stream_slots: plan is NULL (host copy and device copy)");
-    CM_REQUIRE(cm_aligned(plan_host, 4) && cm_aligned(plan_dev, 4), CM_EALIGN, "fbank_wav_stream_slots: plan must be 4-byte aligned");
-    const cm_fbank_stream_args &a = *args;
-    CM_REQUIRE(a.batch > 0 && a.n >= 0 && a.nf >= 0, CM_EINVAL, "fbank_wav_stream_slots: bad sizes");
-    for (int b = 0; b < a.batch; ++b) {                           // every slot passes the lock-step checks on its own counts
-        const cm_fbank_stream_args q = fb_host_view(a, plan_host, b);
-        if (int rc = fbank_stream_check(q, "fbank_wav_stream_slots", true)) return rc;
-        CM_REQUIRE(q.n <= a.n && q.nf <= a.nf, CM_EINVAL, "fbank_wav_stream_slots: slot %d has n %d / nf %d above the maxima %d / %d", b, q.n, q.nf, a.n, a.nf);
-    }
-    CM_REQUIRE(a.hist && a.hist_out && (a.n == 0 || a.chunk), CM_EINVAL, "fbank_wav_stream_slots: NULL chunk / hist / hist_out");
-    CM_REQUIRE(!overlap(a.hist, a.hist_out, (size_t)a.batch * HS * 4), CM_EINVAL, "fbank_wav_stream_slots: hist_out overlaps hist");
-    CM_REQUIRE(a.nf == 0 || (a.window && a.twiddle && a.db && a.fmax && a.band_lo && a.band_hi && a.band_off && a.band_w), CM_EINVAL,
-               "fbank_wav_stream_slots: NULL tensor");
-    CM_REQUIRE(a.nf == 0 || (cm_aligned(a.window, 8) && cm_aligned(a.twiddle, 8)), CM_EALIGN, "fbank_wav_stream_slots: window / twiddle must be 8-byte aligned");
-    fb_slot_args k{};
-    static_cast<cm_fbank_stream_args &>(k) = a;
-    k.plan = plan_dev;
-    const size_t smem = (size_t)(NH + 1) * PWS * 4 + (size_t)(3 * a.n_mels + 1) * 4 + (size_t)BWCAP * 4 + (size_t)4 * ZN * 8 + 4;
-    dim3 grid(a.nf ? (a.nf + FT - 1) / FT : 1, a.batch);
-    hipLaunchKernelGGL((fbank_wav_kernel<true, fb_slot_args>), grid, dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), k,
-                       (float)(10.0 * log10((double)a.amin)));
-    return cm_launch_status("cm_fbank_wav_stream_slots");
+    if (int rc = fbank_slots_check(args, plan_host, plan_dev, "fbank_wav_stream_slots", true)) return rc;
+    return fbank_wav_stream_run(fb_with_plan(*args, plan_dev), "cm_fbank_wav_stream_slots");
 }
 
 extern "C" int cm_fbank_finish_stream_slots(const cm_fbank_stream_args *args, const int32_t *plan_host, const int32_t *plan_dev) {
-    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_finish_stream_slots: args is NULL");
-    CM_REQUIRE(plan_host != nullptr && plan_dev != nullptr, CM_EINVAL, "fbank_finish_stream_slots: plan is NULL (host copy and device copy)");
-    CM_REQUIRE(cm_aligned(plan_host, 4) && cm_aligned(plan_dev, 4), CM_EALIGN, "fbank_finish_stream_slots: plan must be 4-byte aligned");
-    const cm_fbank_stream_args &a = *args;
-    CM_REQUIRE(a.batch > 0, CM_EINVAL, "fbank_finish_stream_slots: bad sizes");
-    for (int b = 0; b < a.batch; ++b) {
-        const cm_fbank_stream_args q = fb_host_view(a, plan_host, b);
-        if (int rc = fbank_stream_check(q, "fbank_finish_stream_slots", false)) return rc;
-        CM_REQUIRE(q.nf <= a.nf, CM_EINVAL, "fbank_finish_stream_slots: slot %d has nf %d above the maximum %d", b, q.nf, a.nf);
-    }
-    CM_REQUIRE(a.nf > 0 && a.db && a.fmax && a.umax, CM_EINVAL, "fbank_finish_stream_slots: no frames or NULL db / fmax / umax");
-    CM_REQUIRE(!a.mean == !a.std, CM_EINVAL, "fbank_finish_stream_slots: mean and std go together");
-    CM_REQUIRE(!a.feat_hist_out || !a.feat_hist || !overlap(a.feat_hist, a.feat_hist_out, (size_t)a.batch * FH * a.n_mels * 4), CM_EINVAL,
-               "fbank_finish_stream_slots: feat_hist_out overlaps feat_hist");
-    CM_REQUIRE(a.feat_hist_out || !a.feat_hist, CM_EINVAL, "fbank_finish_stream_slots: feat_hist without feat_hist_out");
-    fb_slot_args k{};
-    static_cast<cm_fbank_stream_args &>(k) = a;
-    k.plan = plan_dev;
-    hipLaunchKernelGGL(fbank_finish_slots_kernel, dim3(a.batch), dim3(256), 0, reinterpret_cast<hipStream_t>(a.stream), k);
-    return cm_launch_status("cm_fbank_finish_stream_slots");
+    if (int rc = fbank_slots_check(args, plan_host, plan_dev, "fbank_finish_stream_slots", false)) return rc;
+    return fbank_finish_stream_run(fb_with_plan(*args, plan_dev), "cm_fbank_finish_stream_slots");
 }

@@ -1,6 +1,7 @@
 // frontend.hip — Fbank back end and SpecAugment masking for gfx950 (contracts in include/conmamba_hip.h).
-// The STFT itself (framing, Hamming window, real FFT) stays on the vendor FFT; everything after it — power,
-// mel projection, dB, per-utterance top_db clamp, global normalisation, masking — is fused here.
+// The STFT itself (framing, Hamming window, real FFT) stays on the vendor FFT; what comes after it — power, mel
+// projection, dB — is fused here, and the masking.  The per-utterance top_db clamp and the global normalisation
+// (cm_fbank_finish) follow in fbank_fft.hip, next to the form with lengths.
 #include "cm_common.h"
 
 namespace {
@@ -79,34 +80,6 @@ __global__ __launch_bounds__(256) void fbank_mel_db_kernel(const cm_fbank_args p
     }
 }
 
-// grid (chunks, batch): a workgroup first reduces its utterance's tile maxima (when umax_part is given), then clamps and
-// normalises its slice of the utterance.
-__global__ __launch_bounds__(256) void fbank_finish_kernel(const cm_fbank_args p, int ntiles) {
-    __shared__ float red[4];
-    const int b = blockIdx.y;
-    float um;
-    if (p.umax_part) {
-        float mx = -INFINITY;
-        for (int i = threadIdx.x; i < ntiles; i += blockDim.x) mx = fmaxf(mx, p.umax_part[(int64_t)b * ntiles + i]);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-        __syncthreads();
-        um = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-        if (blockIdx.x == 0 && threadIdx.x == 0) p.umax[b] = um;
-    } else {
-        um = p.umax[b];
-    }
-    const float floor_db = um - p.top_db;
-    const int64_t per_utt = (int64_t)p.frames * p.n_mels;
-    float *db = p.db + (int64_t)b * per_utt;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_utt; i += (int64_t)gridDim.x * blockDim.x) {
-        float v = fmaxf(db[i], floor_db);
-        if (p.mean) { const int m = (int)(i % p.n_mels); v = (v - p.mean[m]) / p.std[m]; }
-        db[i] = v;
-    }
-}
-
 __global__ __launch_bounds__(256) void spec_drop_kernel(const cm_spec_drop_args p) {
     const int64_t n = (int64_t)p.batch * p.frames * p.n_mels;
     const float fill = *p.fill;
@@ -137,20 +110,6 @@ extern "C" int cm_fbank_mel_db(const cm_fbank_args *args) {
     hipLaunchKernelGGL(fbank_mel_db_kernel, grid, dim3(256), smem, reinterpret_cast<hipStream_t>(a.stream), a,
                        (float)(10.0 * log10((double)a.amin)));
     return cm_launch_status("cm_fbank_mel_db");
-}
-
-extern "C" int cm_fbank_finish(const cm_fbank_args *args) {
-    CM_REQUIRE(args != nullptr, CM_EINVAL, "fbank_finish: args is NULL");
-    const cm_fbank_args &a = *args;
-    CM_REQUIRE(a.batch > 0 && a.frames > 0 && a.n_mels > 0 && a.db && a.umax, CM_EINVAL, "fbank_finish: bad sizes or NULL tensor");
-    CM_REQUIRE(!a.mean || a.std, CM_EINVAL, "fbank_finish: mean without std");
-    CM_REQUIRE(a.batch <= 65535, CM_EINVAL, "fbank_finish: batch %d exceeds the grid limit", a.batch);
-    const int64_t per_utt = (int64_t)a.frames * a.n_mels;
-    int64_t chunks = (per_utt + 256 * 8 - 1) / (256 * 8);
-    if (chunks > 256) chunks = 256;
-    hipLaunchKernelGGL(fbank_finish_kernel, dim3((unsigned)chunks, a.batch), dim3(256), 0, reinterpret_cast<hipStream_t>(a.stream), a,
-                       (a.frames + FT - 1) / FT);
-    return cm_launch_status("cm_fbank_finish");
 }
 
 extern "C" int cm_spec_drop(const cm_spec_drop_args *args) {

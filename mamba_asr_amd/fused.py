@@ -787,6 +787,21 @@ def _frontend_cache(model, dtype):
     return _FRONTEND.lookup(model, _params_key(dtype, model.CNN, model.Transformer.custom_src_module), dtype)
 
 
+def _cnn_args(model, c):
+    """What ops.cnn_front and ops.cnn_front_stream take for the two CNN blocks: block 1 from the module (fp32), block 2 from the
+    front-end cache ``c``, and the LeakyReLU slope."""
+    b0 = model.CNN.blocks[0]
+    n0 = b0.norm.norm
+    return b0.conv.weight, b0.conv.bias, n0.weight, n0.bias, n0.eps, c["w2_ohwi"], c["b2f"], c["ln2"][0], c["ln2"][1], c["ln2"][2], 0.01
+
+
+def _recipes_front(model) -> bool:
+    """The recipes' Fbank and CNN, which the native front-end routes are built for: n_fft 512, 80 bins, channels (64, 32)."""
+    fb, b0 = model.compute_features, model.CNN.blocks[0]
+    return (ops.fbank_wav_supported(fb.n_fft, fb.hop, fb.n_mels) and fb.n_mels == 80 and tuple(b0.conv.weight.shape) == (64, 1, 3, 3)
+            and b0.norm.norm.weight.numel() == 40 * 64 and tuple(model.CNN.blocks[1].conv.weight.shape) == (32, 64, 3, 3))
+
+
 def ragged_sample_counts(wav_lens, n_total: int, hop: int):
     """Per-utterance sample counts of a padded (B, n_total) batch, on the host: relative lengths (a floating tensor, speechbrain's
     wav_lens) become round(rel * n_total), absolute counts (an integer tensor or a sequence of ints) are taken as they are; one
@@ -808,10 +823,7 @@ def ragged_sample_counts(wav_lens, n_total: int, hop: int):
 def frontend_ragged_native(model, wavs, dtype) -> bool:
     """The ragged front end runs on cm_fbank_wav_lens / cm_fbank_finish_lens / cm_cnn_front_lens: GPU, bf16, n_fft 512, the recipes' CNN."""
     from . import sb_compat
-    fb, b0 = model.compute_features, model.CNN.blocks[0]
-    return (wavs.is_cuda and dtype == torch.bfloat16 and USE_CNN_FRONT and sb_compat.USE_FBANK_WAV and ops.fbank_wav_supported(fb.n_fft, fb.hop, fb.n_mels)
-            and fb.n_mels == 80 and tuple(b0.conv.weight.shape) == (64, 1, 3, 3) and b0.norm.norm.weight.numel() == 40 * 64
-            and tuple(model.CNN.blocks[1].conv.weight.shape) == (32, 64, 3, 3))
+    return wavs.is_cuda and dtype == torch.bfloat16 and USE_CNN_FRONT and sb_compat.USE_FBANK_WAV and _recipes_front(model)
 
 
 @torch.no_grad()
@@ -827,11 +839,7 @@ def frontend_ragged(model, wavs, n_samples, dtype=torch.bfloat16):
     with torch.autocast("cuda", enabled=False):
         feats = ops.fbank_from_wav(wavs, fb.window, fb.n_fft, hop, fb.fbank, fb.amin, fb.top_db, model.normalize.glob_mean,
                                    model.normalize.glob_std, lens=counts[0])
-        c = _frontend_cache(model, dtype)
-        b0 = model.CNN.blocks[0]
-        n0 = b0.norm.norm
-        src = ops.cnn_front(feats, b0.conv.weight, b0.conv.bias, n0.weight, n0.bias, n0.eps,
-                            c["w2_ohwi"], c["b2f"], c["ln2"][0], c["ln2"][1], c["ln2"][2], 0.01, lens=counts[1])
+        src = ops.cnn_front(feats, *_cnn_args(model, _frontend_cache(model, dtype)), lens=counts[1])
     return src, RowLens(rows, counts[2]), counts[1]
 
 
@@ -881,8 +889,7 @@ def asr_encode(model, wavs, wav_lens, dtype: Optional[torch.dtype] = None, n_sam
         if (USE_CNN_FRONT and dtype == torch.bfloat16 and ops.cnn_front_supported(feats, b0.conv.weight, c["w2_ohwi"])
                 and n0.weight.numel() == 40 * 64):
             # both CNN blocks in one kernel: the (B, T/2 + 2, 42, 64) intermediate never reaches memory
-            src = ops.cnn_front(feats, b0.conv.weight, b0.conv.bias, n0.weight, n0.bias, n0.eps,
-                                c["w2_ohwi"], c["b2f"], c["ln2"][0], c["ln2"][1], c["ln2"][2], 0.01)            # (B, T2, 640)
+            src = ops.cnn_front(feats, *_cnn_args(model, c))                            # (B, T2, 640)
         else:
             y1 = ops.cnn_block1(feats, b0.conv.weight, b0.conv.bias, n0.weight, n0.bias, n0.eps, 0.01, out_dtype=dtype,
                                 pad_out=1)                                              # (B, T1+2, F1+2, 64) NHWC
@@ -1043,37 +1050,45 @@ def _front_generic(model, wav_chunk, ctx, last, plan):
     return out
 
 
-def _front_native(model, wav_chunk, ctx, last, plan):
-    n_fft, hop, f0, nf, r0, nr, T = plan
-    fb, B, n = model.compute_features, ctx.batch_size, wav_chunk.shape[1]
-    if n == 0 and nf == 0:
-        return torch.empty((B, 0, 640), dtype=torch.bfloat16, device=wav_chunk.device)
-    if wav_chunk.dtype != torch.float32 or (n and wav_chunk.stride(1) != 1):
+def _front_native(model, wav_chunk, ctx, last=False, plan=None, slots=None):
+    """The native route of one call -> out.  Lock step: ``plan`` is _front_plan's; no host-to-device copy and no pinned allocation, so
+    the call stays capturable.  Per slot: ``slots``, _slot_plan's table, stands in place of ``last`` and ``plan``; the kernels read it from
+    the device, the counts handed to them are the maxima over the slots, and -> (out, lens_dev)."""
+    fb, B, dev = model.compute_features, ctx.batch_size, wav_chunk.device
+    if slots is None:
+        n_fft, hop, f0, nf, r0, nr, T = plan
+        n, consumed, table, alloc = wav_chunk.shape[1], ctx.samples, None, torch.empty
+        total = consumed + n if last else -1
+    else:
+        n_fft, hop, f0, r0, T, consumed, total = fb.n_fft, fb.hop, 0, 0, -1, 0, -1
+        n, nf, nr = (max(p[k] for p in slots) for k in (0, 4, 6))
+        host = torch.tensor(slots, dtype=torch.int32).pin_memory()
+        table = (host, host.to(dev, non_blocking=True))
+        lens_dev = table[1][:, 6].contiguous()
+        alloc = torch.zeros                                # rows past a slot's own count stay zero
+    if n == 0 and nf == 0:                                 # nothing arrived and no utterance ends: no launch
+        out = alloc((B, 0, 640), dtype=torch.bfloat16, device=dev)
+        return out if slots is None else (out, lens_dev)
+    if wav_chunk.dtype != torch.float32 or (wav_chunk.shape[1] and wav_chunk.stride(1) != 1):
         wav_chunk = wav_chunk.float().contiguous()
-    db, fmax = ops.fbank_wav_stream(wav_chunk, ctx.samp_hist, ctx.samp_spare, ctx.samples, f0, nf, fb.window, n_fft, hop, fb.fbank, fb.amin,
-                                    total=ctx.samples + n if last else -1)
+    db, fmax = ops.fbank_wav_stream(wav_chunk, ctx.samp_hist, ctx.samp_spare, consumed, f0, nf, fb.window, n_fft, hop, fb.fbank, fb.amin,
+                                    total=total, plan=table)
     ctx.samp_hist, ctx.samp_spare = ctx.samp_spare, ctx.samp_hist
-    out = torch.empty((B, max(nr, 0), 640), dtype=torch.bfloat16, device=wav_chunk.device)
+    out = alloc((B, max(nr, 0), 640), dtype=torch.bfloat16, device=dev)
     if nf == 0:
-        return out
-    mean, std = _front_norm(model, fb.n_mels, wav_chunk.device)
-    ops.fbank_finish_stream(db, fmax, ctx.umax, f0, fb.top_db, mean, std, ctx.feat_hist, ctx.feat_spare, n_fft=n_fft)
+        return out if slots is None else (out, lens_dev)
+    mean, std = _front_norm(model, fb.n_mels, dev)
+    ops.fbank_finish_stream(db, fmax, ctx.umax, f0, fb.top_db, mean, std, ctx.feat_hist, ctx.feat_spare, n_fft=n_fft, plan=table)
     if nr > 0:
-        c = _frontend_cache(model, torch.bfloat16)
-        b0 = model.CNN.blocks[0]
-        n0 = b0.norm.norm
-        ops.cnn_front_stream(db, ctx.feat_hist, f0, r0, nr, b0.conv.weight, b0.conv.bias, n0.weight, n0.bias, n0.eps, c["w2_ohwi"], c["b2f"],
-                             c["ln2"][0], c["ln2"][1], c["ln2"][2], 0.01, t_total=T, out=out)
+        ops.cnn_front_stream(db, ctx.feat_hist, f0, r0, nr, *_cnn_args(model, _frontend_cache(model, torch.bfloat16)), t_total=T, out=out,
+                             plan=table)
     ctx.feat_hist, ctx.feat_spare = ctx.feat_spare, ctx.feat_hist
-    return out
+    return out if slots is None else (out, lens_dev)
 
 
 def frontend_streaming_native(model, ctx) -> bool:
     """Whether frontend_streaming takes the native route for this model and context."""
-    fb, b0 = model.compute_features, model.CNN.blocks[0]
-    return (USE_STREAM_FRONT_NATIVE and ctx.device.type == "cuda" and ctx.dtype == torch.bfloat16 and fb.n_mels == 80
-            and ops.fbank_wav_supported(fb.n_fft, fb.hop, fb.n_mels) and tuple(b0.conv.weight.shape) == (64, 1, 3, 3)
-            and tuple(model.CNN.blocks[1].conv.weight.shape) == (32, 64, 3, 3) and b0.norm.norm.weight.numel() == 40 * 64)
+    return USE_STREAM_FRONT_NATIVE and ctx.device.type == "cuda" and ctx.dtype == torch.bfloat16 and _recipes_front(model)
 
 
 @torch.no_grad()
@@ -1183,33 +1198,6 @@ def _slot_plan(model, ctx, wav_chunk, n_valid, last):
     return plan, ends
 
 
-def _front_native_slots(model, wav_chunk, ctx, plan):
-    fb, B, dev = model.compute_features, ctx.batch_size, wav_chunk.device
-    n_max, nf_max, nr_max = max(p[0] for p in plan), max(p[4] for p in plan), max(p[6] for p in plan)
-    host = torch.tensor(plan, dtype=torch.int32).pin_memory()
-    table = (host, host.to(dev, non_blocking=True))
-    lens_dev = table[1][:, 6].contiguous()
-    if n_max == 0 and nf_max == 0:                         # nothing arrived and no slot ends: no launch
-        return torch.zeros((B, 0, 640), dtype=torch.bfloat16, device=dev), lens_dev
-    if wav_chunk.dtype != torch.float32 or (wav_chunk.shape[1] and wav_chunk.stride(1) != 1):
-        wav_chunk = wav_chunk.float().contiguous()
-    db, fmax = ops.fbank_wav_stream(wav_chunk, ctx.samp_hist, ctx.samp_spare, 0, 0, nf_max, fb.window, fb.n_fft, fb.hop, fb.fbank, fb.amin, plan=table)
-    ctx.samp_hist, ctx.samp_spare = ctx.samp_spare, ctx.samp_hist
-    out = torch.zeros((B, nr_max, 640), dtype=torch.bfloat16, device=dev)          # rows past a slot's own count stay zero
-    if nf_max == 0:
-        return out, lens_dev
-    mean, std = _front_norm(model, fb.n_mels, dev)
-    ops.fbank_finish_stream(db, fmax, ctx.umax, 0, fb.top_db, mean, std, ctx.feat_hist, ctx.feat_spare, n_fft=fb.n_fft, plan=table)
-    if nr_max > 0:
-        c = _frontend_cache(model, torch.bfloat16)
-        b0 = model.CNN.blocks[0]
-        n0 = b0.norm.norm
-        ops.cnn_front_stream(db, ctx.feat_hist, 0, 0, nr_max, b0.conv.weight, b0.conv.bias, n0.weight, n0.bias, n0.eps, c["w2_ohwi"], c["b2f"],
-                             c["ln2"][0], c["ln2"][1], c["ln2"][2], 0.01, out=out, plan=table)
-    ctx.feat_hist, ctx.feat_spare = ctx.feat_spare, ctx.feat_hist
-    return out, lens_dev
-
-
 def _front_generic_slots(model, wav_chunk, ctx, plan, ends):
     """The lock-step generic route per slot, on one single-stream context each; the rows padded with zeros to the widest slot."""
     B, dev = ctx.batch_size, wav_chunk.device
@@ -1241,7 +1229,7 @@ def frontend_streaming_slots(model, wav_chunk, n_valid, ctx: SlotFrontEndStreami
     plan, ends = _slot_plan(model, ctx, wav_chunk, n_valid, last)
     with torch.autocast("cuda", enabled=False):
         if frontend_streaming_native(model, ctx) and wav_chunk.is_cuda:
-            out, lens_dev = _front_native_slots(model, wav_chunk, ctx, plan)
+            out, lens_dev = _front_native(model, wav_chunk, ctx, slots=plan)
         else:
             out, lens_dev = _front_generic_slots(model, wav_chunk, ctx, plan, ends)
     for b, p in enumerate(plan):
