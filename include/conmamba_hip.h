@@ -569,6 +569,63 @@ int64_t cm_ctc_beam_stream_state_bytes(int32_t beam_size, int32_t max_frames);
 int64_t cm_ctc_beam_stream_workspace_bytes(const cm_ctc_beam_stream_args *args);
 int cm_ctc_beam_stream(const cm_ctc_beam_stream_args *args);
 
+/* The LM-fused search carried across streaming chunks (csrc/ctc_beam_lm_stream.hip): cm_ctc_beam_stream's kernel
+ * with the LM switch of cm_ctc_beam_lm_search on, so after n frames in any chunking the hypotheses carry the bits
+ * cm_ctc_beam_lm_search returns for lengths = n: tokens, lengths, counts, scores (acoustic) and lm_scores (the total, which ranks).
+ * Everything cm_ctc_beam_stream takes, with the same meaning -- reset, consume, emit, idle slots, T == 0, status -1 / NaN frame /
+ * -2 as described there -- plus tok_len and the packed LM of cm_ctc_beam_lm_search with its constants.
+ * State: one slab of cm_ctc_beam_lm_stream_state_bytes(beam_size, max_frames) bytes per slot = (16 + 116 beam_size + 4 beam_size
+ * max_frames) rounded up to 16: the 16-byte header and the beam block of cm_ctc_beam_stream (80 bytes per beam), then the LM block
+ * -- lm beam_size f64, ps beam_size f64, ctx 4 x beam_size int32, plen beam_size int32 (LM(text), partial_score, the entries of the
+ * last 1 .. 4 words, the partial word's code points) -- then the history.  Plain memory without pointers, copying a slab copies a
+ * stream, an all-zero slab is a slot that was never reset; a reset stores the initial LM state (ctx[0] = lm_bos when order >= 2)
+ * beside the initial beam.  ctx holds entry numbers of the LM tables: a slab belongs to the tables (and lm_bos) it was advanced
+ * with, and continuing it with others gives wrong scores -- nothing detects that.  Whatever a slab holds, no load or store leaves
+ * it or the tables: on load every ctx outside [0, n_entries) reads as -1 and plen is clamped to >= 0.  The function returns 0
+ * outside the limits of cm_ctc_beam_stream_state_bytes.
+ * An emit of a reset slot without frames gives one hypothesis of no tokens, score 0 and lm_score = LM("") (the </s> term alone).
+ * workspace: cm_ctc_beam_lm_stream_workspace_bytes() bytes, the rule of cm_ctc_beam_stream_workspace_bytes.  Arguments are validated
+ * on the host before any launch: those of cm_ctc_beam_stream, the LM checks of cm_ctc_beam_lm_search, the state, the workspace. */
+typedef struct cm_ctc_beam_lm_stream_args {
+    int32_t batch, T, V, dtype;               /* batch: slots; T: rows per slot in this chunk; dtype CM_F32 or CM_BF16; V <= 4096 */
+    int64_t lp_bs, lp_ts;                     /* log_probs element strides of slot and time                     */
+    const void *log_probs;                    /* (batch, T, V)                                                  */
+    const int32_t *chunk_len;                 /* (batch) rows of this chunk to consume; 0: idle                 */
+    const int32_t *reset, *emit;              /* (batch) or NULL                                                */
+    const int32_t *tok_class;                 /* (V)                                                            */
+    const uint64_t *tok_hash, *tok_pow;       /* (V, 2)                                                         */
+    const int32_t *tok_len;                   /* (V) code points of the clean piece                             */
+    uint64_t hash_base[2], hash_sep;
+    int32_t blank, beam_size, topk, prune_history;   /* beam_size <= 256                                        */
+    double beam_prune_logp, token_prune_min_logp, blank_skip_threshold;
+    double blank_skip_log;                    /* set by the library                                             */
+    int32_t order, n_words;                   /* order in [1, 5]                                                */
+    int32_t lm_bos, lm_eos, lm_unk, reserved0;
+    int64_t n_entries, word_cap, prefix_cap, ngram_cap;
+    const uint64_t *word_keys;                /* (word_cap, 2)                                                  */
+    const int32_t *word_ids;                  /* (word_cap)                                                     */
+    const uint64_t *prefix_keys;              /* (prefix_cap, 2)                                                */
+    const uint64_t *ngram_keys;               /* (ngram_cap)                                                    */
+    const int32_t *ngram_vals;                /* (ngram_cap)                                                    */
+    const float *lm_prob, *lm_backoff;        /* (n_entries)                                                    */
+    double alpha, beta, unk_score_offset;     /* finite                                                         */
+    double alpha_ln10;                        /* set by the library                                             */
+    void *state;                              /* batch slabs                                                    */
+    int64_t state_stride_bytes;
+    int32_t max_frames, reserved1;            /* frames per utterance (between two resets)                      */
+    int32_t *tokens;                          /* (batch, topk, max_frames)                                      */
+    int32_t *token_len;                       /* (batch, topk)                                                  */
+    double *scores, *lm_scores;               /* (batch, topk)                                                  */
+    int32_t *num_hyps, *status;               /* (batch)                                                        */
+    void *workspace;
+    int64_t workspace_bytes;
+    void *stream;
+} cm_ctc_beam_lm_stream_args;
+
+int64_t cm_ctc_beam_lm_stream_state_bytes(int32_t beam_size, int32_t max_frames);
+int64_t cm_ctc_beam_lm_stream_workspace_bytes(const cm_ctc_beam_lm_stream_args *args);
+int cm_ctc_beam_lm_stream(const cm_ctc_beam_lm_stream_args *args);
+
 /* CTC prefix scores for joint CTC/attention S2S decoding (csrc/ctc_prefix.hip; what speechbrain's CTCScorer adds to the decoder's
  * log-probabilities, the reference S2S recipes' `ctc_weight_decode`; DESIGN.md §4d holds the contract).  logp (U, T, V) fp32
  * contiguous CTC log-posteriors; n_u[u] frames of utterance u to use (clamped to [0, T] in the kernels).  Hypothesis row r belongs

@@ -1,4 +1,4 @@
-// ctc_beam_finish.inc.h — the finish and backtrack of the CTC beam search as TEXT (see ctc_beam_frames.inc.h; the same three
+// ctc_beam_finish.inc.h — the finish and backtrack of the CTC beam search as TEXT (see ctc_beam_frames.inc.h; the same four
 // kernels include it): on the sort buffers only, beams and history stay as they are.  In scope at the include, behind a __syncthreads that covers beams and history: p, sh,
 // b, tid, K, nb, cur, steps, hist, lbuf, tok_stride (row stride of p.tokens), status_out / status (the word thread 0 writes beside
 // num_hyps) and the constant guard_history (the history is caller memory written by earlier launches: clamp each parent slot below

@@ -1,5 +1,5 @@
-// ctc_beam_frames.inc.h — the frame loop of the CTC beam search as TEXT: the three kernels (ctc_beam.hip, ctc_beam_stream.hip,
-// ctc_beam_lm.hip) include this file in the middle of their bodies, so they run the same statements and the whole-utterance kernel
+// ctc_beam_frames.inc.h — the frame loop of the CTC beam search as TEXT: the four kernels (ctc_beam.hip, ctc_beam_lm.hip and, through
+// ctc_beam_stream_impl.h, ctc_beam_stream.hip and ctc_beam_lm_stream.hip) include this file in the middle of their bodies, so they run the same statements and the whole-utterance kernel
 // compiles to the ISA it had when the loop stood in it (every function boundary tried around this register-starved loop moved its
 // time by 1 - 2 %).
 // In scope at the include: p (the argument struct), sh (Shared), b, tid, lane, wave, V, K, n (frames of log_probs[b] to consume;

@@ -1,6 +1,7 @@
 // ctc_beam_impl.h — what the whole-utterance CTC beam search (ctc_beam.hip, cm_ctc_beam_search), the streamed one
-// (ctc_beam_stream.hip, cm_ctc_beam_stream) and the LM-fused one (ctc_beam_lm.hip, cm_ctc_beam_lm_search) share: constants, the LDS
-// layout, hashing, merge_rank, the host-side argument check and slab layout and, as text all three kernels include in their
+// (ctc_beam_stream.hip, cm_ctc_beam_stream), the LM-fused one (ctc_beam_lm.hip, cm_ctc_beam_lm_search) and the streamed LM-fused one
+// (ctc_beam_lm_stream.hip, cm_ctc_beam_lm_stream; its kernel is the streamed one's template, ctc_beam_stream_impl.h) share: constants, the LDS
+// layout, hashing, merge_rank, the host-side argument check and slab layout and, as text all four kernels include in their
 // bodies, the frame loop (ctc_beam_frames.inc.h) and the finish with its backtrack (ctc_beam_finish.inc.h).  The kernels run
 // exactly these statements per frame, so a search fed chunk by chunk returns the bits of the search fed at once, and the LM search
 // differs from the LM-free one only in what the fragments say under their LM switch (NoLm below).  The
@@ -37,8 +38,8 @@ constexpr uint64_t KEY_MAX = ~0ull;
 constexpr int F_TEXT_EMPTY = 1, F_PART_EMPTY = 2;
 
 // The helpers that read search parameters (joined, extend, canonical, load_lp) are templates over the argument struct P,
-// cm_ctc_beam_args, cm_ctc_beam_stream_args or cm_ctc_beam_lm_args, and the two text fragments name it p: the fields they read
-// carry the same names in all three structs (log_probs, lp_bs, lp_ts, dtype, V, the token tables, the hash constants, blank, beam_size, topk, prune_history,
+// cm_ctc_beam_args, cm_ctc_beam_stream_args, cm_ctc_beam_lm_args or cm_ctc_beam_lm_stream_args, and the two text fragments name it p:
+// the fields they read carry the same names in all four structs (log_probs, lp_bs, lp_ts, dtype, V, the token tables, the hash constants, blank, beam_size, topk, prune_history,
 // beam_prune_logp, token_prune_min_logp, blank_skip_log; the finish also num_hyps, tokens, token_len, scores; under the LM switch
 // also tok_len, the LM tables and constants, lm_scores).
 
@@ -112,6 +113,7 @@ struct NoLm {
     static constexpr bool on = false;
     struct Lds {};
     struct State {};
+    static constexpr int STREAM_BYTES = 0;      // per beam in a stream slab (ctc_beam_stream_impl.h)
 };
 
 __device__ __forceinline__ State load_state(const Beams &bm, int buf, int r) {

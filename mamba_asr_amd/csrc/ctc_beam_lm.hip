@@ -3,7 +3,8 @@
 // LM-free one: this kernel is ctc_beam.hip's with the NgramLm policy, so it includes the same two text fragments and runs what
 // they say under `if constexpr (Lm::on)` -- every beam also holds an LM state (ctc_beam_lm_impl.h), the rank sort runs on
 // acoustic + LM(text) + partial_score(partial) (merge_rank's total functor) and the surviving beam fetches its folded acoustic
-// score from the position the sort carried along.  This file holds the kernel's setup and the LM table checks of the entry point.
+// score from the position the sort carried along.  This file holds the kernel's setup and the entry point (the LM table checks are
+// check_lm_args of ctc_beam_lm_impl.h).
 // One workgroup of 256 threads per utterance; LDS: Shared 115,888 B + LmBeams 18,432 B = 134,320 B of the 160 KB a workgroup may hold.
 #include "ctc_beam_lm_impl.h"
 
@@ -40,8 +41,6 @@ __global__ __launch_bounds__(NT) void ctc_beam_lm_kernel(const P p, int64_t slab
 #include "ctc_beam_finish.inc.h"
 }
 
-bool pow2(int64_t x) { return x > 0 && (x & (x - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int64_t cm_ctc_beam_lm_workspace_bytes(const cm_ctc_beam_lm_args *args) { return whole_workspace_bytes(args); }
@@ -52,18 +51,7 @@ extern "C" int cm_ctc_beam_lm_search(const cm_ctc_beam_lm_args *args) {
     const bool pointers = a.log_probs && a.lengths && a.tok_class && a.tok_hash && a.tok_pow && a.tok_len && a.tokens && a.token_len &&
                           a.scores && a.lm_scores && a.num_hyps && a.bad_frame && a.workspace;
     if (const int rc = check_beam_args(a, "ctc_beam_lm_search", nullptr, pointers)) return rc;
-    CM_REQUIRE(a.word_keys && a.word_ids && a.prefix_keys && a.ngram_keys && a.ngram_vals && a.lm_prob && a.lm_backoff, CM_EINVAL,
-               "ctc_beam_lm_search: NULL LM table pointer");
-    CM_REQUIRE(a.order >= 1 && a.order <= LM_ORDER_MAX, CM_EINVAL, "ctc_beam_lm_search: LM order %d not in [1, %d]", a.order, LM_ORDER_MAX);
-    CM_REQUIRE(pow2(a.word_cap) && pow2(a.prefix_cap) && pow2(a.ngram_cap), CM_EINVAL,
-               "ctc_beam_lm_search: table capacities must be powers of two (word %lld, prefix %lld, n-gram %lld)",
-               (long long)a.word_cap, (long long)a.prefix_cap, (long long)a.ngram_cap);
-    CM_REQUIRE(a.n_words >= 1 && a.n_entries >= a.n_words && a.n_entries < (1ll << 31), CM_EINVAL,
-               "ctc_beam_lm_search: need 1 <= n_words (%d) <= n_entries (%lld) < 2^31", a.n_words, (long long)a.n_entries);
-    CM_REQUIRE(a.lm_bos >= -1 && a.lm_bos < a.n_words && a.lm_eos >= -1 && a.lm_eos < a.n_words && a.lm_unk >= -1 && a.lm_unk < a.n_words,
-               CM_EINVAL, "ctc_beam_lm_search: lm_bos / lm_eos / lm_unk must be -1 or a word id below %d", a.n_words);
-    CM_REQUIRE(std::isfinite(a.alpha) && std::isfinite(a.beta) && std::isfinite(a.unk_score_offset), CM_EINVAL,
-               "ctc_beam_lm_search: alpha, beta and unk_score_offset must be finite");
+    if (const int rc = check_lm_args(a, "ctc_beam_lm_search")) return rc;
     CM_REQUIRE(a.workspace_bytes >= cm_ctc_beam_lm_workspace_bytes(&a), CM_EINVAL,
                "ctc_beam_lm_search: workspace smaller than cm_ctc_beam_lm_workspace_bytes()");
     a.blank_skip_log = std::log(a.blank_skip_threshold);

@@ -1,6 +1,8 @@
-// ctc_beam_lm_impl.h — what the LM-fused CTC beam search (ctc_beam_lm.hip, cm_ctc_beam_lm_search) adds to ctc_beam_impl.h: the
+// ctc_beam_lm_impl.h — what the LM-fused CTC beam searches (ctc_beam_lm.hip, cm_ctc_beam_lm_search; ctc_beam_lm_stream.hip,
+// cm_ctc_beam_lm_stream) add to ctc_beam_impl.h: the
 // per-beam LM state in LDS, the table probes, ARPA backoff, the word and partial-word scores, and NgramLm, the policy that turns on
-// the LM switch of the shared frame loop and finish, which call these functions.  Contract: DESIGN.md §4p.
+// the LM switch of the shared frame loop and finish, which call these functions; for the streamed search also the LM state's
+// place in a stream slab, and the entries' shared LM argument checks.  Contract: DESIGN.md §4p, §4q.
 // Probes read global memory from a few divergent lanes; each loop runs at most `capacity` steps and every id a table returns is
 // range-checked before it indexes anything.
 #pragma once
@@ -146,12 +148,61 @@ template <class P> __device__ __forceinline__ void lm_store_initial(const P &p, 
     lm_store(lb, buf, 0, s);
 }
 
+// The LM block of a stream slab (ctc_beam_stream_impl.h; `block` is 8-byte aligned), K beams: lm K f64 | ps K f64 | ctx LM_CTX x K
+// i32 | plen K i32.  The slab is caller memory and ctx indexes lm_backoff (lm_cond), so a load clamps every ctx to -1 unless it is
+// an entry of p's tables and plen to >= 0: a damaged slab gives wrong scores, no read outside the tables.
+constexpr int LM_STREAM_BYTES = 2 * 8 + LM_CTX * 4 + 4;
+
+template <class P> __device__ __forceinline__ LmState lm_slab_load(const P &p, const char *block, int K, int r) {
+    const double *d = reinterpret_cast<const double *>(block);
+    const int32_t *w = reinterpret_cast<const int32_t *>(d + 2 * K);
+    LmState s;
+    s.lm = d[r]; s.ps = d[K + r];
+#pragma unroll
+    for (int k = 0; k < LM_CTX; ++k) {
+        const int32_t e = w[k * K + r];
+        s.ctx[k] = (e >= 0 && (int64_t)e < p.n_entries) ? e : -1;
+    }
+    s.plen = max(w[LM_CTX * K + r], 0);
+    return s;
+}
+
+__device__ __forceinline__ void lm_slab_store(char *block, int K, int r, const LmState &s) {
+    double *d = reinterpret_cast<double *>(block);
+    int32_t *w = reinterpret_cast<int32_t *>(d + 2 * K);
+    d[r] = s.lm; d[K + r] = s.ps;
+#pragma unroll
+    for (int k = 0; k < LM_CTX; ++k) w[k * K + r] = s.ctx[k];
+    w[LM_CTX * K + r] = s.plen;
+}
+
 // the LM switch of the text fragments (ctc_beam_impl.h, NoLm) for this LM
 struct NgramLm {
     static constexpr bool on = true;
     using Lds = LmBeams;
     using State = LmState;
     static constexpr int CTX = LM_CTX;
+    static constexpr int STREAM_BYTES = LM_STREAM_BYTES;
 };
+
+inline bool lm_pow2(int64_t x) { return x > 0 && (x & (x - 1)) == 0; }
+
+// The LM argument checks cm_ctc_beam_lm_search and cm_ctc_beam_lm_stream share, behind check_beam_args and in the order the
+// first always made them; `who` prefixes the messages.
+template <class A> int check_lm_args(const A &a, const char *who) {
+    CM_REQUIRE(a.word_keys && a.word_ids && a.prefix_keys && a.ngram_keys && a.ngram_vals && a.lm_prob && a.lm_backoff, CM_EINVAL,
+               "%s: NULL LM table pointer", who);
+    CM_REQUIRE(a.order >= 1 && a.order <= LM_ORDER_MAX, CM_EINVAL, "%s: LM order %d not in [1, %d]", who, a.order, LM_ORDER_MAX);
+    CM_REQUIRE(lm_pow2(a.word_cap) && lm_pow2(a.prefix_cap) && lm_pow2(a.ngram_cap), CM_EINVAL,
+               "%s: table capacities must be powers of two (word %lld, prefix %lld, n-gram %lld)", who,
+               (long long)a.word_cap, (long long)a.prefix_cap, (long long)a.ngram_cap);
+    CM_REQUIRE(a.n_words >= 1 && a.n_entries >= a.n_words && a.n_entries < (1ll << 31), CM_EINVAL,
+               "%s: need 1 <= n_words (%d) <= n_entries (%lld) < 2^31", who, a.n_words, (long long)a.n_entries);
+    CM_REQUIRE(a.lm_bos >= -1 && a.lm_bos < a.n_words && a.lm_eos >= -1 && a.lm_eos < a.n_words && a.lm_unk >= -1 && a.lm_unk < a.n_words,
+               CM_EINVAL, "%s: lm_bos / lm_eos / lm_unk must be -1 or a word id below %d", who, a.n_words);
+    CM_REQUIRE(std::isfinite(a.alpha) && std::isfinite(a.beta) && std::isfinite(a.unk_score_offset), CM_EINVAL,
+               "%s: alpha, beta and unk_score_offset must be finite", who);
+    return CM_OK;
+}
 
 }  // namespace

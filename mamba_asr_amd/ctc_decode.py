@@ -64,7 +64,9 @@ Finish.  Commit the partial as a word, scored as above; merge by text, folding t
 plus alpha * ln(10) * log10 p(</s> | text) when score_boundary is set and the LM lists </s> (no beta for it); prune and rank by
 total; return CTCHypothesis(text, None, score=acoustic, lm_score=total, None).  n_b = 0 or T = 0 gives one hypothesis with
 text "", score 0.0 and lm_score = LM("") by the same rules (the </s> term alone).  Without kenlm_model_path the LM keywords are
-inert.  The streamed searcher does not carry LM state: it refuses a path.
+inert.  StreamingCTCBeamLMSearcher carries this search across chunks (ops.ctc_beam_lm_stream, csrc/ctc_beam_lm_stream.hip;
+DESIGN.md §4q): every beam's LM state lives in the stream's slab beside its identity, and hypotheses() after n frames is what the
+search above returns for n_b = n, lm_score bits included.  StreamingCTCBeamSearcher itself stays LM-free and refuses a path.
 """
 from __future__ import annotations
 
@@ -281,7 +283,8 @@ class CTCStreamState:
 class StreamingCTCBeamSearcher(CTCBeamSearcher):
     """CTCBeamSearcher carried across chunks (cm_ctc_beam_stream): the constructor keywords of CTCBeamSearcher plus
     max_frames, the frames one utterance (reset to reset) may hold -- 1500 is a minute of 40-ms encoder frames.  After n frames in
-    any chunking, hypotheses() returns what CTCBeamSearcher returns for those n frames, score bits included.
+    any chunking, hypotheses() returns what CTCBeamSearcher returns for those n frames, score bits included.  This class is the
+    LM-free search and refuses kenlm_model_path; StreamingCTCBeamLMSearcher below streams the LM-fused one.
 
         state = searcher.make_state(batch_size, device); state.reset()
         searcher.step(log_probs_chunk, state)           # per chunk: one launch, nothing read back
@@ -290,11 +293,14 @@ class StreamingCTCBeamSearcher(CTCBeamSearcher):
 
     def __init__(self, *args, max_frames: int = 1500, **kw):
         if kw.get("kenlm_model_path") is not None or (len(args) > 4 and args[4] is not None):
-            raise NotImplementedError("StreamingCTCBeamSearcher: streamed language-model fusion (kenlm_model_path) is not provided; "
-                                      "CTCBeamSearcher fuses an n-gram LM over whole utterances")
-        super().__init__(*args, **kw)
+            raise NotImplementedError("StreamingCTCBeamSearcher is LM-free: streamed language-model fusion (kenlm_model_path) is "
+                                      "StreamingCTCBeamLMSearcher's; CTCBeamSearcher fuses an n-gram LM over whole utterances")
+        self._init_searcher(args, kw, max_frames)
+
+    def _init_searcher(self, args, kw, max_frames):
+        CTCBeamSearcher.__init__(self, *args, **kw)
         if not 1 <= max_frames <= 0x7fff0000 // 256:
-            raise ValueError(f"StreamingCTCBeamSearcher: max_frames {max_frames} not in [1, {0x7fff0000 // 256}]")
+            raise ValueError(f"{type(self).__name__}: max_frames {max_frames} not in [1, {0x7fff0000 // 256}]")
         self.max_frames = int(max_frames)
         self._dev_lengths = {}
 
@@ -306,7 +312,7 @@ class StreamingCTCBeamSearcher(CTCBeamSearcher):
         rows = list(range(state.batch_size)) if rows is None else [int(u) for u in rows]
         for u in rows:
             if not 0 <= u < state.batch_size:
-                raise ValueError(f"StreamingCTCBeamSearcher: slot {u} outside a state of {state.batch_size} slots")
+                raise ValueError(f"{type(self).__name__}: slot {u} outside a state of {state.batch_size} slots")
         return rows
 
     def _flags(self, values: Sequence[int], device) -> torch.Tensor:
@@ -343,25 +349,25 @@ class StreamingCTCBeamSearcher(CTCBeamSearcher):
         its own, status -2).  Raises ValueError before launching when a slot was never reset or would pass max_frames."""
         n = state.batch_size
         if log_probs.dim() != 3 or log_probs.shape[0] != n or log_probs.shape[2] != len(self.vocab_list):
-            raise ValueError(f"StreamingCTCBeamSearcher: log_probs must be ({n}, t, {len(self.vocab_list)}), got {tuple(log_probs.shape)}")
+            raise ValueError(f"{type(self).__name__}: log_probs must be ({n}, t, {len(self.vocab_list)}), got {tuple(log_probs.shape)}")
         t = log_probs.shape[1]
         lengths = [t] * n if lengths is None else [int(x) for x in lengths]
         if len(lengths) != n or any(not 0 <= x <= t for x in lengths):
-            raise ValueError(f"StreamingCTCBeamSearcher: lengths must be {n} frame counts in [0, {t}], got {lengths}")
+            raise ValueError(f"{type(self).__name__}: lengths must be {n} frame counts in [0, {t}], got {lengths}")
         reset = self._rows(state, reset) if reset is not None else []
         fed = list(state.fed)
         for u in reset:
             fed[u] = 0
         for u, x in enumerate(lengths):
             if x and fed[u] is None:
-                raise ValueError(f"StreamingCTCBeamSearcher: slot {u} was never reset: pass reset=[{u}] with its first chunk, or call state.reset([{u}])")
+                raise ValueError(f"{type(self).__name__}: slot {u} was never reset: pass reset=[{u}] with its first chunk, or call state.reset([{u}])")
             if x and fed[u] + x > self.max_frames:
-                raise ValueError(f"StreamingCTCBeamSearcher: slot {u} would hold {fed[u] + x} frames, more than max_frames={self.max_frames}: "
+                raise ValueError(f"{type(self).__name__}: slot {u} would hold {fed[u] + x} frames, more than max_frames={self.max_frames}: "
                                  "end-point the utterance and reset the slot")
             if x:
                 fed[u] += x
         if not log_probs.is_cuda or not state.slab.is_cuda:
-            raise RuntimeError("StreamingCTCBeamSearcher runs on the GPU only (got a CPU tensor): move log_probs and the state to the GPU")
+            raise RuntimeError(f"{type(self).__name__} runs on the GPU only (got a CPU tensor): move log_probs and the state to the GPU")
         if t and (reset or any(lengths)):
             self._launch(state, log_probs, lengths, reset=reset)
         elif reset:
@@ -375,8 +381,56 @@ class StreamingCTCBeamSearcher(CTCBeamSearcher):
         reset, when the slot met a NaN."""
         rows = self._rows(state, rows)
         if not state.slab.is_cuda:
-            raise RuntimeError("StreamingCTCBeamSearcher runs on the GPU only (got a CPU state)")
+            raise RuntimeError(f"{type(self).__name__} runs on the GPU only (got a CPU state)")
         if not rows:
             return []
         tokens, token_len, scores, num_hyps, status = self._launch(state, None, [0] * state.batch_size, emit=rows)
         return self._hypotheses(tokens, token_len, scores, num_hyps, status, rows, "slot")
+
+
+class StreamingCTCBeamLMSearcher(StreamingCTCBeamSearcher):
+    """StreamingCTCBeamSearcher with the n-gram LM of CTCBeamSearcher(kenlm_model_path=...) fused into the streamed search
+    (cm_ctc_beam_lm_stream): the same constructor keywords, ``kenlm_model_path`` required and validated as
+    CTCBeamSearcher validates it, plus max_frames.  After n frames in any chunking, hypotheses() returns what
+    CTCBeamSearcher(kenlm_model_path=...) returns for those n frames -- CTCHypothesis(text, None, score=acoustic, lm_score=total,
+    None), score and lm_score bits included.  make_state, step (lengths=, reset=, hipGraph capture after one eager call),
+    state.reset and hypotheses are the base class's; a step uploads nothing, the LM tables being cached on the device.  A state
+    belongs to the searcher (the LM tables) that advanced it: its slabs hold entry numbers of those tables."""
+
+    def __init__(self, *args, max_frames: int = 1500, **kw):
+        if kw.get("kenlm_model_path") is None and not (len(args) > 4 and args[4] is not None):
+            raise ValueError("StreamingCTCBeamLMSearcher: kenlm_model_path is required (StreamingCTCBeamSearcher is the LM-free "
+                             "streamed search)")
+        self._init_searcher(args, kw, max_frames)
+
+    def make_state(self, batch_size: int, device) -> CTCStreamState:
+        """``batch_size`` slots that were never reset, their slabs sized for the LM state as well."""
+        return CTCStreamState(self, ops.ctc_beam_lm_stream_state(batch_size, self.beam_size, self.max_frames, device))
+
+    def _launch(self, state, log_probs, lengths, reset=None, emit=None):
+        dev, n = state.slab.device, state.batch_size
+        tc, th, tp = self._tables(dev)
+        lm = self.lm
+        same = len(set(lengths)) == 1
+        chunk_len = self._constant(lengths[0], n, dev) if same else self._flags(lengths, dev)
+
+        def mark(rows):
+            return self._flags([1 if u in rows else 0 for u in range(n)], dev) if rows else None
+        return ops.ctc_beam_lm_stream(
+            log_probs, chunk_len, state.slab, self.max_frames, tc, th, tp, self._tok_len(dev), HASH_BASE, HASH_SEP, lm.tables(dev),
+            order=lm.order, n_words=len(lm.words), lm_bos=lm.bos if self.score_boundary else -1,
+            lm_eos=lm.eos if self.score_boundary else -1, lm_unk=lm.unk, alpha=self.alpha, beta=self.beta,
+            unk_score_offset=self.unk_score_offset, reset=mark(reset), emit=mark(emit), blank=self.blank_index,
+            beam_size=self.beam_size, topk=self.topk, prune_history=self.prune_history, beam_prune_logp=self.beam_prune_logp,
+            token_prune_min_logp=self.token_prune_min_logp, blank_skip_threshold=self.blank_skip_threshold)
+
+    def hypotheses(self, state: CTCStreamState, rows: Optional[Sequence[int]] = None) -> List[List[CTCHypothesis]]:
+        """As StreamingCTCBeamSearcher.hypotheses; each hypothesis carries score = its acoustic score and lm_score = its total, by
+        which the list is ranked."""
+        rows = self._rows(state, rows)
+        if not state.slab.is_cuda:
+            raise RuntimeError(f"{type(self).__name__} runs on the GPU only (got a CPU state)")
+        if not rows:
+            return []
+        tokens, token_len, scores, lm_scores, num_hyps, status = self._launch(state, None, [0] * state.batch_size, emit=rows)
+        return self._hypotheses(tokens, token_len, scores, num_hyps, status, rows, "slot", lm_scores=lm_scores)

@@ -935,6 +935,29 @@ def ctc_beam_search(log_probs, lengths, tok_class, tok_hash, tok_pow, hash_base,
     return out
 
 
+_LM_TABLES = dict(word_keys=torch.int64, word_ids=torch.int32, prefix_keys=torch.int64, ngram_keys=torch.int64, ngram_vals=torch.int32,
+                  prob=torch.float32, backoff=torch.float32)
+
+
+def _ctc_lm_args(what, a, lm, order, n_words, lm_bos, lm_eos, lm_unk, alpha, beta, unk_score_offset):
+    """What the two LM-fused CTC beam searches prepare alike: the dict of device tensors of ngram_lm.NgramLM.tables() checked
+    (dtypes, contiguity, shapes) and, with the constants that describe it, filled into the argument struct ``a``."""
+    for n, dtype in _LM_TABLES.items():
+        if lm[n].dtype != dtype or not lm[n].is_contiguous():
+            raise RuntimeError(f"{what}: lm[{n!r}] must be a contiguous {dtype} tensor")
+    if lm["word_keys"].dim() != 2 or lm["word_keys"].shape[1] != 2 or lm["prefix_keys"].dim() != 2 or lm["prefix_keys"].shape[1] != 2:
+        raise RuntimeError(f"{what}: word_keys and prefix_keys must be (capacity, 2)")
+    if lm["word_ids"].numel() != lm["word_keys"].shape[0] or lm["ngram_vals"].numel() != lm["ngram_keys"].numel() \
+            or lm["backoff"].numel() != lm["prob"].numel():
+        raise RuntimeError(f"{what}: keys / values of a table, or prob / backoff, differ in length")
+    a.order, a.n_words, a.lm_bos, a.lm_eos, a.lm_unk = int(order), int(n_words), int(lm_bos), int(lm_eos), int(lm_unk)
+    a.n_entries, a.word_cap, a.prefix_cap, a.ngram_cap = (lm["prob"].numel(), lm["word_ids"].numel(), lm["prefix_keys"].shape[0],
+                                                          lm["ngram_keys"].numel())
+    a.word_keys, a.word_ids, a.prefix_keys = _ptr(lm["word_keys"]), _ptr(lm["word_ids"]), _ptr(lm["prefix_keys"])
+    a.ngram_keys, a.ngram_vals, a.lm_prob, a.lm_backoff = _ptr(lm["ngram_keys"]), _ptr(lm["ngram_vals"]), _ptr(lm["prob"]), _ptr(lm["backoff"])
+    a.alpha, a.beta, a.unk_score_offset = float(alpha), float(beta), float(unk_score_offset)
+
+
 def ctc_beam_search_lm(log_probs, lengths, tok_class, tok_hash, tok_pow, tok_len, hash_base, hash_sep, lm, *, order, n_words,
                        lm_bos=-1, lm_eos=-1, lm_unk=-1, alpha=0.5, beta=1.5, unk_score_offset=-10.0, blank=0, beam_size=100, topk=1,
                        prune_history=False, beam_prune_logp=-10.0, token_prune_min_logp=-5.0, blank_skip_threshold=1.0):
@@ -943,27 +966,11 @@ def ctc_beam_search_lm(log_probs, lengths, tok_class, tok_hash, tok_pow, tok_len
     (cap, 2) / prefix_keys (cap, 2) / ngram_keys (cap) int64 bit patterns, word_ids / ngram_vals int32, prob / backoff fp32; order,
     n_words and the word ids lm_bos / lm_eos / lm_unk (-1: not used) describe it.
     -> (tokens, token_len, scores (acoustic), lm_scores (total, the ranking score), num_hyps, bad_frame) as ctc_beam_search."""
-    names = ("word_keys", "word_ids", "prefix_keys", "ngram_keys", "ngram_vals", "prob", "backoff")
-    _dev_check(log_probs, lengths, tok_class, tok_hash, tok_pow, tok_len, *[lm[n] for n in names])
-    want = dict(word_keys=torch.int64, word_ids=torch.int32, prefix_keys=torch.int64, ngram_keys=torch.int64, ngram_vals=torch.int32,
-                prob=torch.float32, backoff=torch.float32)
-    for n in names:
-        if lm[n].dtype != want[n] or not lm[n].is_contiguous():
-            raise RuntimeError(f"ctc_beam_search_lm: lm[{n!r}] must be a contiguous {want[n]} tensor")
-    if lm["word_keys"].dim() != 2 or lm["word_keys"].shape[1] != 2 or lm["prefix_keys"].dim() != 2 or lm["prefix_keys"].shape[1] != 2:
-        raise RuntimeError("ctc_beam_search_lm: word_keys and prefix_keys must be (capacity, 2)")
-    if lm["word_ids"].numel() != lm["word_keys"].shape[0] or lm["ngram_vals"].numel() != lm["ngram_keys"].numel() \
-            or lm["backoff"].numel() != lm["prob"].numel():
-        raise RuntimeError("ctc_beam_search_lm: keys / values of a table, or prob / backoff, differ in length")
+    _dev_check(log_probs, lengths, tok_class, tok_hash, tok_pow, tok_len, *[lm[n] for n in _LM_TABLES])
     a = N.CtcBeamLmArgs()
+    _ctc_lm_args("ctc_beam_search_lm", a, lm, order, n_words, lm_bos, lm_eos, lm_unk, alpha, beta, unk_score_offset)
     lp, t, _, held = _ctc_beam_args("ctc_beam_search_lm", a, log_probs, None, tok_class, tok_hash, tok_pow, tok_len, hash_base, hash_sep,
                                     blank, beam_size, topk, prune_history, beam_prune_logp, token_prune_min_logp, blank_skip_threshold)
-    a.order, a.n_words, a.lm_bos, a.lm_eos, a.lm_unk = int(order), int(n_words), int(lm_bos), int(lm_eos), int(lm_unk)
-    a.n_entries, a.word_cap, a.prefix_cap, a.ngram_cap = (lm["prob"].numel(), lm["word_ids"].numel(), lm["prefix_keys"].shape[0],
-                                                          lm["ngram_keys"].numel())
-    a.word_keys, a.word_ids, a.prefix_keys = _ptr(lm["word_keys"]), _ptr(lm["word_ids"]), _ptr(lm["prefix_keys"])
-    a.ngram_keys, a.ngram_vals, a.lm_prob, a.lm_backoff = _ptr(lm["ngram_keys"]), _ptr(lm["ngram_vals"]), _ptr(lm["prob"]), _ptr(lm["backoff"])
-    a.alpha, a.beta, a.unk_score_offset = float(alpha), float(beta), float(unk_score_offset)
     out, held_whole = _ctc_beam_whole(a, N.lib().cm_ctc_beam_lm_workspace_bytes, lp, lengths, topk)   # held: alive until the launch
     _launch("cm_ctc_beam_lm_search", N.lib().cm_ctc_beam_lm_search, a, units=lp.shape[0] * t)
     return out
@@ -979,6 +986,44 @@ def ctc_beam_stream_state(slots, beam_size, max_frames, device):
     return torch.zeros((int(slots), nbytes), dtype=torch.uint8, device=device)
 
 
+def _ctc_beam_stream_run(what, a, sym, log_probs, chunk_len, state, max_frames, tok_class, tok_hash, tok_pow, tok_len, hash_base, hash_sep,
+                         reset, emit, blank, beam_size, topk, prune_history, beam_prune_logp, token_prune_min_logp, blank_skip_threshold,
+                         bufs):
+    """The body of ctc_beam_stream and ctc_beam_lm_stream: the checks, the argument struct ``a`` (of cm_<sym>; its LM fields, if
+    any, are filled already), the outputs (lm_scores where the struct has it) and the launch -> the outputs in the struct's order."""
+    dev = state.device
+    slots = state.shape[0]
+    if state.dim() != 2 or state.dtype != torch.uint8 or state.stride(1) != 1:
+        raise RuntimeError(f"{what}: state must be the (slots, bytes) uint8 tensor of {what}_state (or row slices of it)")
+    for name, flag in (("chunk_len", chunk_len), ("reset", reset), ("emit", emit)):
+        if flag is not None and (flag.dtype != torch.int32 or tuple(flag.shape) != (slots,) or not flag.is_contiguous() or flag.device != dev):
+            raise RuntimeError(f"{what}: {name} must be a contiguous int32 tensor of shape ({slots},) on {dev}")
+    if log_probs is not None and (log_probs.dim() != 3 or log_probs.shape[0] != slots or log_probs.device != dev):
+        raise RuntimeError(f"{what}: log_probs must be ({slots}, t, V) on {dev}, got {tuple(log_probs.shape)} on {log_probs.device}")
+    _, t, _, held = _ctc_beam_args(what, a, log_probs, dev, tok_class, tok_hash, tok_pow, tok_len, hash_base, hash_sep, blank,
+                                   beam_size, topk, prune_history, beam_prune_logp, token_prune_min_logp, blank_skip_threshold)
+    a.batch, a.chunk_len, a.reset, a.emit = slots, _ptr(chunk_len), _ptr(reset), _ptr(emit)
+    a.state, a.state_stride_bytes, a.max_frames = _ptr(state), state.stride(0), int(max_frames)
+    nws = int(getattr(N.lib(), f"cm_{sym}_workspace_bytes")(ct.byref(a)))
+    with_lm = hasattr(a, "lm_scores")
+    names = ("tokens", "token_len", "scores") + (("lm_scores",) if with_lm else ()) + ("num_hyps", "status")
+    take = _bufs(bufs, names + ("workspace",), what)
+    tokens = take("tokens", (slots, topk, int(max_frames)), torch.int32, dev)
+    token_len = take("token_len", (slots, topk), torch.int32, dev)
+    scores = take("scores", (slots, topk), torch.float64, dev)
+    out = (tokens, token_len, scores)
+    if with_lm:
+        lm_scores = take("lm_scores", (slots, topk), torch.float64, dev)
+        a.lm_scores = _ptr(lm_scores)
+        out += (lm_scores,)
+    num_hyps, status = take("num_hyps", (slots,), torch.int32, dev), take("status", (slots,), torch.int32, dev)
+    ws = take("workspace", (nws,), torch.uint8, dev) if nws else None
+    a.tokens, a.token_len, a.scores, a.num_hyps, a.status = _ptr(tokens), _ptr(token_len), _ptr(scores), _ptr(num_hyps), _ptr(status)
+    a.workspace, a.workspace_bytes, a.stream = _ptr(ws), nws, _stream()
+    _launch(f"cm_{sym}", getattr(N.lib(), f"cm_{sym}"), a, units=slots * t)
+    return out + (num_hyps, status)
+
+
 def ctc_beam_stream(log_probs, chunk_len, state, max_frames, tok_class, tok_hash, tok_pow, hash_base, hash_sep, reset=None, emit=None,
                     blank=0, beam_size=100, topk=1, prune_history=False, beam_prune_logp=-10.0, token_prune_min_logp=-5.0,
                     blank_skip_threshold=1.0, bufs=None):
@@ -991,31 +1036,37 @@ def ctc_beam_stream(log_probs, chunk_len, state, max_frames, tok_class, tok_hash
     (the rest); everything else is uninitialised memory.  bufs: caller-placed "tokens", "token_len", "scores", "num_hyps",
     "status" and "workspace" (uint8, cm_ctc_beam_stream_workspace_bytes)."""
     _dev_check(log_probs, chunk_len, state, reset, emit, tok_class, tok_hash, tok_pow)
-    dev = state.device
-    slots = state.shape[0]
-    if state.dim() != 2 or state.dtype != torch.uint8 or state.stride(1) != 1:
-        raise RuntimeError("ctc_beam_stream: state must be the (slots, bytes) uint8 tensor of ctc_beam_stream_state (or row slices of it)")
-    for name, flag in (("chunk_len", chunk_len), ("reset", reset), ("emit", emit)):
-        if flag is not None and (flag.dtype != torch.int32 or tuple(flag.shape) != (slots,) or not flag.is_contiguous() or flag.device != dev):
-            raise RuntimeError(f"ctc_beam_stream: {name} must be a contiguous int32 tensor of shape ({slots},) on {dev}")
-    if log_probs is not None and (log_probs.dim() != 3 or log_probs.shape[0] != slots or log_probs.device != dev):
-        raise RuntimeError(f"ctc_beam_stream: log_probs must be ({slots}, t, V) on {dev}, got {tuple(log_probs.shape)} on {log_probs.device}")
-    a = N.CtcBeamStreamArgs()
-    _, t, _, held = _ctc_beam_args("ctc_beam_stream", a, log_probs, dev, tok_class, tok_hash, tok_pow, None, hash_base, hash_sep, blank,
-                                   beam_size, topk, prune_history, beam_prune_logp, token_prune_min_logp, blank_skip_threshold)
-    a.batch, a.chunk_len, a.reset, a.emit = slots, _ptr(chunk_len), _ptr(reset), _ptr(emit)
-    a.state, a.state_stride_bytes, a.max_frames = _ptr(state), state.stride(0), int(max_frames)
-    nws = int(N.lib().cm_ctc_beam_stream_workspace_bytes(ct.byref(a)))
-    take = _bufs(bufs, ("tokens", "token_len", "scores", "num_hyps", "status", "workspace"), "ctc_beam_stream")
-    tokens = take("tokens", (slots, topk, int(max_frames)), torch.int32, dev)
-    token_len = take("token_len", (slots, topk), torch.int32, dev)
-    scores = take("scores", (slots, topk), torch.float64, dev)
-    num_hyps, status = take("num_hyps", (slots,), torch.int32, dev), take("status", (slots,), torch.int32, dev)
-    ws = take("workspace", (nws,), torch.uint8, dev) if nws else None
-    a.tokens, a.token_len, a.scores, a.num_hyps, a.status = _ptr(tokens), _ptr(token_len), _ptr(scores), _ptr(num_hyps), _ptr(status)
-    a.workspace, a.workspace_bytes, a.stream = _ptr(ws), nws, _stream()
-    _launch("cm_ctc_beam_stream", N.lib().cm_ctc_beam_stream, a, units=slots * t)
-    return tokens, token_len, scores, num_hyps, status
+    return _ctc_beam_stream_run("ctc_beam_stream", N.CtcBeamStreamArgs(), "ctc_beam_stream", log_probs, chunk_len, state, max_frames,
+                                tok_class, tok_hash, tok_pow, None, hash_base, hash_sep, reset, emit, blank, beam_size, topk, prune_history,
+                                beam_prune_logp, token_prune_min_logp, blank_skip_threshold, bufs)
+
+
+def ctc_beam_lm_stream_state(slots, beam_size, max_frames, device):
+    """The zeroed state of ``slots`` streamed LM-fused CTC beam searches: (slots, cm_ctc_beam_lm_stream_state_bytes(beam_size,
+    max_frames)) uint8 -- ctc_beam_stream_state's slab with 36 more bytes per beam, the LM state.  A slab belongs to the LM tables
+    it is advanced with."""
+    nbytes = int(N.lib().cm_ctc_beam_lm_stream_state_bytes(int(beam_size), int(max_frames)))
+    if nbytes <= 0 or slots < 1:
+        raise RuntimeError(f"ctc_beam_lm_stream_state: slots {slots} < 1, beam_size {beam_size} not in [1, 256] or max_frames "
+                           f"{max_frames} not in [1, {0x7fff0000 // 256}]")
+    return torch.zeros((int(slots), nbytes), dtype=torch.uint8, device=device)
+
+
+def ctc_beam_lm_stream(log_probs, chunk_len, state, max_frames, tok_class, tok_hash, tok_pow, tok_len, hash_base, hash_sep, lm, *, order,
+                       n_words, lm_bos=-1, lm_eos=-1, lm_unk=-1, alpha=0.5, beta=1.5, unk_score_offset=-10.0, reset=None, emit=None,
+                       blank=0, beam_size=100, topk=1, prune_history=False, beam_prune_logp=-10.0, token_prune_min_logp=-5.0,
+                       blank_skip_threshold=1.0, bufs=None):
+    """The next chunk of every stream through the LM-fused CTC beam search (cm_ctc_beam_lm_stream): ctc_beam_stream with the LM of
+    ctc_beam_search_lm (tok_len, the ``lm`` dict of device tensors and the constants that describe it); state from
+    ctc_beam_lm_stream_state.
+    -> (tokens, token_len, scores (acoustic), lm_scores (total, the ranking score), num_hyps, status), written as ctc_beam_stream
+    writes its outputs.  bufs: caller-placed "tokens", "token_len", "scores", "lm_scores", "num_hyps", "status" and "workspace"."""
+    _dev_check(log_probs, chunk_len, state, reset, emit, tok_class, tok_hash, tok_pow, tok_len, *[lm[n] for n in _LM_TABLES])
+    a = N.CtcBeamLmStreamArgs()
+    _ctc_lm_args("ctc_beam_lm_stream", a, lm, order, n_words, lm_bos, lm_eos, lm_unk, alpha, beta, unk_score_offset)
+    return _ctc_beam_stream_run("ctc_beam_lm_stream", a, "ctc_beam_lm_stream", log_probs, chunk_len, state, max_frames, tok_class,
+                                tok_hash, tok_pow, tok_len, hash_base, hash_sep, reset, emit, blank, beam_size, topk, prune_history,
+                                beam_prune_logp, token_prune_min_logp, blank_skip_threshold, bufs)
 
 
 def _ctc_prefix_args(what, logp, n_u, row_utt, last, r_n, r_b, psi_g, blank, eos, validated):
