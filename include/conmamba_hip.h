@@ -420,7 +420,8 @@ typedef struct cm_conv_cl_bwd_args {
  * train_CTC.py:405): log_probs (batch, T, V) fp32 contiguous (log-softmax outputs), targets (batch, S) int64 padded, lengths int32.
  * nll[b] = negative log-likelihood (0 where no alignment exists: zero_infinity); grad (batch, T, V) fp32 = exp(lp) - posteriors
  * for t < input_lengths[b], 0 elsewhere -- the gradient torch returns for a unit upstream gradient per utterance (the caller
- * scales by grad_out / batch).  S <= 511.  Deterministic (fixed summation order). */
+ * scales by grad_out / batch).  S <= 511; targets may be NULL exactly when S == 0 (every target empty: it is never read).
+ * Deterministic (fixed summation order). */
 typedef struct cm_ctc_args {
     int32_t batch, T, V, S, blank, Sx_max;   /* Sx_max: set by the library (2 S + 1)                          */
     const float   *log_probs;

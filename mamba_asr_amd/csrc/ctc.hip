@@ -234,7 +234,10 @@ extern "C" int cm_ctc_loss(const cm_ctc_args *args) {
     CM_REQUIRE(a.batch > 0 && a.T > 0 && a.V > 1 && a.S >= 0, CM_EINVAL, "ctc_loss: bad sizes batch=%d T=%d V=%d S=%d", a.batch, a.T, a.V, a.S);
     CM_REQUIRE(a.S <= 511, CM_EUNSUPPORTED, "ctc_loss: at most 511 labels per utterance (got %d)", a.S);
     CM_REQUIRE(a.blank >= 0 && a.blank < a.V, CM_EINVAL, "ctc_loss: blank %d out of range", a.blank);
-    CM_REQUIRE(a.log_probs && a.targets && a.input_lengths && a.target_lengths && a.nll && a.grad && a.workspace, CM_EINVAL, "ctc_loss: NULL tensor");
+    // S == 0 (every target empty): the extended sequence is the single blank, ext_label() reads targets at odd positions only --
+    // an empty tensor has no address, so NULL is what a caller holds
+    CM_REQUIRE(a.log_probs && (a.targets || a.S == 0) && a.input_lengths && a.target_lengths && a.nll && a.grad && a.workspace, CM_EINVAL,
+               "ctc_loss: NULL tensor");
     CM_REQUIRE(a.workspace_floats >= cm_ctc_workspace_floats(a.batch, a.T, a.S), CM_EINVAL, "ctc_loss: workspace smaller than cm_ctc_workspace_floats()");
     a.Sx_max = 2 * a.S + 1;
     a.alpha = a.workspace;

@@ -840,19 +840,22 @@ def ctc_supported(log_probs, targets) -> bool:
     return log_probs.is_cuda and log_probs.dim() == 3 and targets.dim() == 2 and targets.shape[1] <= 511 and log_probs.shape[2] > 1
 
 
-def ctc_loss_grad(log_probs, targets, input_lengths, target_lengths, blank=0):
+def ctc_loss_grad(log_probs, targets, input_lengths, target_lengths, blank=0, bufs=None):
     """log_probs (batch, T, V) -> (nll (batch) fp32, grad (batch, T, V) fp32) (cm_ctc_loss): per-utterance negative log-likelihood
-    (0 where no alignment exists) and its gradient w.r.t. log_probs; lengths are integer tensors."""
+    (0 where no alignment exists) and its gradient w.r.t. log_probs; lengths are integer tensors.  targets (batch, 0) -- every
+    target empty -- is passed as NULL (the library takes that exactly when S == 0).  bufs: caller-placed "nll", "grad" and
+    "workspace" (fp32, cm_ctc_workspace_floats)."""
     _dev_check(log_probs, targets, input_lengths, target_lengths)
     lp = log_probs.detach().float().contiguous()
     b, t, v = lp.shape
     tg = targets.detach().to(torch.int64).contiguous()
     il, tl = input_lengths.detach().to(torch.int32).contiguous(), target_lengths.detach().to(torch.int32).contiguous()
     s = tg.shape[1]
-    nll = torch.empty((b,), dtype=torch.float32, device=lp.device)
-    grad = torch.empty_like(lp)
+    take = _bufs(bufs, ("nll", "grad", "workspace"), "ctc_loss_grad")
+    nll = take("nll", (b,), torch.float32, lp.device)
+    grad = take("grad", (b, t, v), torch.float32, lp.device)
     nws = int(N.lib().cm_ctc_workspace_floats(b, t, s))
-    ws = torch.empty((nws,), dtype=torch.float32, device=lp.device)
+    ws = take("workspace", (nws,), torch.float32, lp.device)
     a = N.CtcArgs()
     a.batch, a.T, a.V, a.S, a.blank = b, t, v, s, int(blank)
     a.log_probs, a.targets, a.input_lengths, a.target_lengths, a.nll, a.grad = _ptr(lp), _ptr(tg), _ptr(il), _ptr(tl), _ptr(nll), _ptr(grad)
@@ -896,41 +899,50 @@ def _ctc_beam_args(what, a, log_probs, dev, tok_class, tok_hash, tok_pow, tok_le
     return lp, t, v, (lp, tc, th, tp, tl)
 
 
-def _ctc_beam_whole(a, workspace_bytes, lp, lengths, topk):
+def _ctc_beam_whole(what, a, workspace_bytes, lp, lengths, topk, bufs):
     """Lengths, outputs and workspace of a whole-utterance CTC beam search into its argument struct ``a`` (filled by
-    _ctc_beam_args; lm_scores where the struct has it) -> (the outputs in the struct's order, the tensors to keep until launch)."""
+    _ctc_beam_args; lm_scores where the struct has it) -> (the outputs in the struct's order, the tensors to keep until launch).
+    A caller-placed token_len / scores / lm_scores is not zeroed: rows past num_hyps keep what the buffer held."""
     b, t, _ = lp.shape
     dev = lp.device
     ln = lengths.detach().to(device=dev, dtype=torch.int32).contiguous()
-    tokens = torch.empty((b, topk, t), dtype=torch.int32, device=dev)
-    token_len = torch.zeros((b, topk), dtype=torch.int32, device=dev)
-    scores = torch.zeros((b, topk), dtype=torch.float64, device=dev)
-    num_hyps = torch.empty((b,), dtype=torch.int32, device=dev)
-    bad_frame = torch.empty((b,), dtype=torch.int32, device=dev)
+    with_lm = hasattr(a, "lm_scores")
+    take = _bufs(bufs, ("tokens", "token_len", "scores") + (("lm_scores",) if with_lm else ()) + ("num_hyps", "bad_frame", "workspace"), what)
+
+    def per_hyp(name, dtype):                   # (batch, topk): zero where the caller places none (rows past num_hyps are not written)
+        if bufs is None or bufs.get(name) is None:
+            return torch.zeros((b, topk), dtype=dtype, device=dev)
+        return take(name, (b, topk), dtype, dev)
+    tokens = take("tokens", (b, topk, t), torch.int32, dev)
+    token_len, scores = per_hyp("token_len", torch.int32), per_hyp("scores", torch.float64)
+    num_hyps = take("num_hyps", (b,), torch.int32, dev)
+    bad_frame = take("bad_frame", (b,), torch.int32, dev)
     a.tokens, a.token_len, a.scores, a.num_hyps, a.bad_frame = _ptr(tokens), _ptr(token_len), _ptr(scores), _ptr(num_hyps), _ptr(bad_frame)
     out = (tokens, token_len, scores, num_hyps, bad_frame)
-    if hasattr(a, "lm_scores"):
-        lm_scores = torch.zeros((b, topk), dtype=torch.float64, device=dev)
+    if with_lm:
+        lm_scores = per_hyp("lm_scores", torch.float64)
         a.lm_scores = _ptr(lm_scores)
         out = out[:3] + (lm_scores,) + out[3:]
     a.batch, a.lengths = b, _ptr(ln)
     nws = int(workspace_bytes(ct.byref(a)))
-    ws = torch.empty((max(nws, 1),), dtype=torch.uint8, device=dev)
+    ws = take("workspace", (max(nws, 1),), torch.uint8, dev)
     a.workspace, a.workspace_bytes, a.stream = _ptr(ws), nws, _stream()
     return out, (ln, ws)
 
 
 def ctc_beam_search(log_probs, lengths, tok_class, tok_hash, tok_pow, hash_base, hash_sep, blank=0, beam_size=100, topk=1,
-                    prune_history=False, beam_prune_logp=-10.0, token_prune_min_logp=-5.0, blank_skip_threshold=1.0):
+                    prune_history=False, beam_prune_logp=-10.0, token_prune_min_logp=-5.0, blank_skip_threshold=1.0, bufs=None):
     """LM-free CTC beam search (cm_ctc_beam_search).  log_probs (batch, T, V) fp32 / bf16, lengths (batch) frames to decode;
     tok_class (V) int32, tok_hash / tok_pow (V, 2) int64 holding the unsigned hash tables (mamba_asr_amd.ctc_decode builds them).
     -> (tokens (batch, topk, T) int32, token_len (batch, topk) int32, scores (batch, topk) fp64, num_hyps (batch) int32,
-    bad_frame (batch) int32): hypothesis h < num_hyps[b] of utterance b is its text-changing tokens tokens[b, h, :token_len[b, h]]."""
+    bad_frame (batch) int32): hypothesis h < num_hyps[b] of utterance b is its text-changing tokens tokens[b, h, :token_len[b, h]].
+    bufs: caller-placed "tokens", "token_len", "scores", "num_hyps", "bad_frame" and "workspace" (uint8,
+    cm_ctc_beam_workspace_bytes)."""
     _dev_check(log_probs, lengths, tok_class, tok_hash, tok_pow)
     a = N.CtcBeamArgs()
     lp, t, _, held = _ctc_beam_args("ctc_beam_search", a, log_probs, None, tok_class, tok_hash, tok_pow, None, hash_base, hash_sep, blank,
                                     beam_size, topk, prune_history, beam_prune_logp, token_prune_min_logp, blank_skip_threshold)
-    out, held_whole = _ctc_beam_whole(a, N.lib().cm_ctc_beam_workspace_bytes, lp, lengths, topk)   # held: alive until the launch
+    out, held_whole = _ctc_beam_whole("ctc_beam_search", a, N.lib().cm_ctc_beam_workspace_bytes, lp, lengths, topk, bufs)   # held: alive until the launch
     _launch("cm_ctc_beam_search", N.lib().cm_ctc_beam_search, a, units=lp.shape[0] * t)
     return out
 
@@ -960,18 +972,20 @@ def _ctc_lm_args(what, a, lm, order, n_words, lm_bos, lm_eos, lm_unk, alpha, bet
 
 def ctc_beam_search_lm(log_probs, lengths, tok_class, tok_hash, tok_pow, tok_len, hash_base, hash_sep, lm, *, order, n_words,
                        lm_bos=-1, lm_eos=-1, lm_unk=-1, alpha=0.5, beta=1.5, unk_score_offset=-10.0, blank=0, beam_size=100, topk=1,
-                       prune_history=False, beam_prune_logp=-10.0, token_prune_min_logp=-5.0, blank_skip_threshold=1.0):
+                       prune_history=False, beam_prune_logp=-10.0, token_prune_min_logp=-5.0, blank_skip_threshold=1.0, bufs=None):
     """CTC beam search with a fused backoff n-gram LM (cm_ctc_beam_lm_search).  The arguments of ctc_beam_search, plus tok_len
     (V) int32 (code points of each clean piece) and ``lm``, the dict of device tensors of ngram_lm.NgramLM.tables(): word_keys
     (cap, 2) / prefix_keys (cap, 2) / ngram_keys (cap) int64 bit patterns, word_ids / ngram_vals int32, prob / backoff fp32; order,
     n_words and the word ids lm_bos / lm_eos / lm_unk (-1: not used) describe it.
-    -> (tokens, token_len, scores (acoustic), lm_scores (total, the ranking score), num_hyps, bad_frame) as ctc_beam_search."""
+    -> (tokens, token_len, scores (acoustic), lm_scores (total, the ranking score), num_hyps, bad_frame) as ctc_beam_search.
+    bufs: caller-placed "tokens", "token_len", "scores", "lm_scores", "num_hyps", "bad_frame" and "workspace" (uint8,
+    cm_ctc_beam_lm_workspace_bytes)."""
     _dev_check(log_probs, lengths, tok_class, tok_hash, tok_pow, tok_len, *[lm[n] for n in _LM_TABLES])
     a = N.CtcBeamLmArgs()
     _ctc_lm_args("ctc_beam_search_lm", a, lm, order, n_words, lm_bos, lm_eos, lm_unk, alpha, beta, unk_score_offset)
     lp, t, _, held = _ctc_beam_args("ctc_beam_search_lm", a, log_probs, None, tok_class, tok_hash, tok_pow, tok_len, hash_base, hash_sep,
                                     blank, beam_size, topk, prune_history, beam_prune_logp, token_prune_min_logp, blank_skip_threshold)
-    out, held_whole = _ctc_beam_whole(a, N.lib().cm_ctc_beam_lm_workspace_bytes, lp, lengths, topk)   # held: alive until the launch
+    out, held_whole = _ctc_beam_whole("ctc_beam_search_lm", a, N.lib().cm_ctc_beam_lm_workspace_bytes, lp, lengths, topk, bufs)   # held: alive until the launch
     _launch("cm_ctc_beam_lm_search", N.lib().cm_ctc_beam_lm_search, a, units=lp.shape[0] * t)
     return out
 
@@ -1091,11 +1105,12 @@ def _ctc_prefix_args(what, logp, n_u, row_utt, last, r_n, r_b, psi_g, blank, eos
     return a
 
 
-def ctc_prefix_score(logp, n_u, row_utt, last, r_n, r_b, psi_g, blank, eos, candidates=None, validated=False):
+def ctc_prefix_score(logp, n_u, row_utt, last, r_n, r_b, psi_g, blank, eos, candidates=None, validated=False, bufs=None):
     """CTC prefix score deltas (cm_ctc_prefix_score).  logp (U, T, V) fp32 CTC log-posteriors, n_u (U) int32 frames per
     utterance; per hypothesis row: row_utt (rows) int32, last (rows) int32 (-1: empty prefix), r_n / r_b (rows, T) fp32,
     psi_g (rows) fp32.  -> (rows, V) fp32 psi(prefix + c) - psi_g, or (rows, K) for candidates (rows, K) int32 (-inf for a
-    candidate outside [0, V)); -inf for blank and for impossible extensions; column eos holds the prefix's CTC log-likelihood."""
+    candidate outside [0, V)); -inf for blank and for impossible extensions; column eos holds the prefix's CTC log-likelihood.
+    bufs: a caller-placed "out"."""
     a = _ctc_prefix_args("ctc_prefix_score", logp, n_u, row_utt, last, r_n, r_b, psi_g, blank, eos, validated)
     ncol = a.V
     if candidates is not None:
@@ -1105,31 +1120,36 @@ def ctc_prefix_score(logp, n_u, row_utt, last, r_n, r_b, psi_g, blank, eos, cand
             raise RuntimeError("ctc_prefix_score: candidates must be a contiguous int32 (rows, K >= 1) tensor")
         ncol = a.K = candidates.shape[1]
         a.candidates = _ptr(candidates)
-    out = torch.empty((a.rows, ncol), dtype=torch.float32, device=logp.device)
+    out = _bufs(bufs, ("out",), "ctc_prefix_score")("out", (a.rows, ncol), torch.float32, logp.device)
     a.out = _ptr(out)
     _launch("cm_ctc_prefix_score", N.lib().cm_ctc_prefix_score, a, units=a.rows * a.T)
     return out
 
 
-def ctc_prefix_advance(logp, n_u, row_utt, last, r_n, r_b, psi_g, tokens, blank, eos, validated=False):
+def ctc_prefix_advance(logp, n_u, row_utt, last, r_n, r_b, psi_g, tokens, blank, eos, validated=False, bufs=None):
     """Every row's prefix extended by tokens (rows) int32 (cm_ctc_prefix_advance; arguments as ctc_prefix_score) ->
-    new (r_n, r_b, psi_g, last) in fresh tensors.  A row whose token is eos keeps its state."""
+    new (r_n, r_b, psi_g, last) in fresh tensors.  A row whose token is eos keeps its state.  bufs: caller-placed "r_n_out",
+    "r_b_out", "psi_out" and "last_out"."""
     a = _ctc_prefix_args("ctc_prefix_advance", logp, n_u, row_utt, last, r_n, r_b, psi_g, blank, eos, validated)
     _dev_check(tokens)
     if tuple(tokens.shape) != (a.rows,) or tokens.dtype != torch.int32 or not tokens.is_contiguous():
         raise RuntimeError("ctc_prefix_advance: tokens must be a contiguous int32 (rows,) tensor")
-    r_n2, r_b2, psi2, last2 = torch.empty_like(r_n), torch.empty_like(r_b), torch.empty_like(psi_g), torch.empty_like(last)
+    take = _bufs(bufs, ("r_n_out", "r_b_out", "psi_out", "last_out"), "ctc_prefix_advance")
+    dev = logp.device
+    r_n2, r_b2 = take("r_n_out", (a.rows, a.T), torch.float32, dev), take("r_b_out", (a.rows, a.T), torch.float32, dev)
+    psi2, last2 = take("psi_out", (a.rows,), torch.float32, dev), take("last_out", (a.rows,), torch.int32, dev)
     a.tokens, a.r_n_out, a.r_b_out, a.psi_out, a.last_out = _ptr(tokens), _ptr(r_n2), _ptr(r_b2), _ptr(psi2), _ptr(last2)
     _launch("cm_ctc_prefix_advance", N.lib().cm_ctc_prefix_advance, a, units=a.rows * a.T)
     return r_n2, r_b2, psi2, last2
 
 
-def beam_select(att, alive, B, eos, delta=None, weight=0.0, eos_blocked=None):
+def beam_select(att, alive, B, eos, delta=None, weight=0.0, eos_blocked=None, bufs=None):
     """One token's selection of an S2S beam search (cm_beam_select).  att (U * B, V) fp32 decoder
     log-probabilities and alive (U * B) fp32 running scores (-inf: dead slot) of rows u * B + k; delta (U * B, V) fp32 CTC
     prefix scores added with ``weight``, or None; eos_blocked (U) int32, nonzero where <eos> may not be chosen, or None.
     -> (score, inc, parent, token), each (U, B): per utterance the B best candidates under (alive + inc descending, flat index
-    k * V + c ascending), inc = att [+ weight * delta] as separately rounded fp32 operations; parent / token int32."""
+    k * V + c ascending), inc = att [+ weight * delta] as separately rounded fp32 operations; parent / token int32.
+    bufs: caller-placed "score", "inc", "parent", "token" and "workspace" (uint8, cm_beam_select_workspace_bytes, 8-byte aligned)."""
     _dev_check(att, alive, delta, eos_blocked)
     B = int(B)
     if not 1 <= B <= N.CM_BEAM_SELECT_MAX_B:
@@ -1149,14 +1169,20 @@ def beam_select(att, alive, B, eos, delta=None, weight=0.0, eos_blocked=None):
     nws = lib.cm_beam_select_workspace_bytes(U, B, V)
     if nws <= 0:
         raise RuntimeError(f"beam_select: unsupported sizes U={U} B={B} V={V}")
-    ws = torch.empty((nws + 7) // 8, dtype=torch.int64, device=att.device)      # int64: the 8-byte alignment the library asks for
-    score, inc = (torch.empty((U, B), dtype=torch.float32, device=att.device) for _ in range(2))
-    parent, token = (torch.empty((U, B), dtype=torch.int32, device=att.device) for _ in range(2))
+    take = _bufs(bufs, ("score", "inc", "parent", "token", "workspace"), "beam_select")
+    if bufs is not None and bufs.get("workspace") is not None:
+        ws = take("workspace", (nws,), torch.uint8, att.device)
+        ws_bytes = nws
+    else:
+        ws = torch.empty((nws + 7) // 8, dtype=torch.int64, device=att.device)  # int64: the 8-byte alignment the library asks for
+        ws_bytes = ws.numel() * 8
+    score, inc = (take(n, (U, B), torch.float32, att.device) for n in ("score", "inc"))
+    parent, token = (take(n, (U, B), torch.int32, att.device) for n in ("parent", "token"))
     a = N.BeamSelectArgs()
     a.U, a.B, a.V, a.eos, a.weight = U, B, V, int(eos), float(weight)
     a.att, a.delta, a.alive, a.eos_blocked = _ptr(att), _ptr(delta), _ptr(alive), _ptr(eos_blocked)
     a.score, a.inc, a.parent, a.token = _ptr(score), _ptr(inc), _ptr(parent), _ptr(token)
-    a.workspace, a.workspace_bytes, a.stream = _ptr(ws), ws.numel() * 8, _stream()
+    a.workspace, a.workspace_bytes, a.stream = _ptr(ws), ws_bytes, _stream()
     _launch("cm_beam_select", lib.cm_beam_select, a, units=rows * V)
     return score, inc, parent, token
 
@@ -1185,17 +1211,17 @@ def _attn_step_shapes(qkv, kc, vc, anc, t, H):
     return R, D, Lcap
 
 
-def attn_step(qkv, kc, vc, anc, t, H):
+def attn_step(qkv, kc, vc, anc, t, H, bufs=None):
     """One decoding step of H-head self-attention over a KV cache addressed through a beam-ancestry table (cm_attn_step,
     DESIGN.md §4f).  qkv (R, 3 D) bf16 / fp32: this step's q | k | v; kc, vc (Lcap, R, D) caches of qkv's dtype, written in place
     at position t and nowhere else; anc (Lcap, R) int32: anc[s, r] is the row in which row r's prefix token of position s < t was
     cached (an entry outside [0, R) scores -inf); -> out (R, D) in qkv's dtype.  fp32 arithmetic; D / H in {32, 64}, H <= 32,
-    t < 4096."""
+    t < 4096.  bufs: a caller-placed "out"."""
     _dev_check(qkv, kc, vc, anc)
     if qkv.dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError(f"attn_step: unsupported dtype {qkv.dtype} (fp32 / bf16)")
     R, D, Lcap = _attn_step_shapes(qkv, kc, vc, anc, t, H)
-    out = torch.empty((R, D), dtype=qkv.dtype, device=qkv.device)
+    out = _bufs(bufs, ("out",), "attn_step")("out", (R, D), qkv.dtype, qkv.device)
     a = N.AttnStepArgs()
     a.R, a.D, a.H, a.t, a.Lcap, a.io_dtype = R, D, int(H), int(t), Lcap, _DT[qkv.dtype]
     a.kv_stride = kc.stride(0) if Lcap > 1 else R * D
@@ -1250,17 +1276,18 @@ def _xattn_step_shapes(q, k, v, row_utt, enc_len, H):
     return R, D, U, T
 
 
-def xattn_step(q, k, v, row_utt, enc_len, H):
+def xattn_step(q, k, v, row_utt, enc_len, H, bufs=None):
     """One decoding step of H-head cross-attention of R hypothesis rows over the encoder memory of their utterance
     (cm_xattn_step).  q (R, D) bf16 / fp32; k, v (U, T, D) views of q's dtype, projected once per utterance
     (any utterance / frame strides: the two halves of one (U, T, 2 D) GEMM result work); row_utt (R) int32: the utterance of
     each row; enc_len (U) int32: its valid frames -> out (R, D) in q's dtype, softmax over frames s < min(enc_len[u], T) only;
-    a row with row_utt outside [0, U) or no valid frame is zero.  fp32 arithmetic; D / H in {32, 36, 64}, H <= 32, T < 8192."""
+    a row with row_utt outside [0, U) or no valid frame is zero.  fp32 arithmetic; D / H in {32, 36, 64}, H <= 32, T < 8192.
+    bufs: a caller-placed "out"."""
     _dev_check(q, k, v, row_utt, enc_len)
     if q.dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError(f"xattn_step: unsupported dtype {q.dtype} (fp32 / bf16)")
     R, D, U, T = _xattn_step_shapes(q, k, v, row_utt, enc_len, H)
-    out = torch.empty((R, D), dtype=q.dtype, device=q.device)
+    out = _bufs(bufs, ("out",), "xattn_step")("out", (R, D), q.dtype, q.device)
     a = N.XattnStepArgs()
     a.R, a.U, a.T, a.D, a.H, a.io_dtype = R, U, T, D, int(H), _DT[q.dtype]
     for name, c in (("k", k), ("v", v)):
@@ -1649,15 +1676,15 @@ def add_layernorm(x, y=None, alpha=1.0, norm1=None, norm2=None, x_out=None, out_
     return x_out, out
 
 
-def causal_conv1d_update(x, conv_state, weight, bias=None, silu=True):
+def causal_conv1d_update(x, conv_state, weight, bias=None, silu=True, bufs=None):
     """Decode-time conv step (cm_causal_conv1d_update; reference bimamba.py:331-343): conv_state (batch, dim, width) fp32 is
-    shifted and gets x (batch, dim) appended IN PLACE; returns out (batch, dim) in x's dtype."""
+    shifted and gets x (batch, dim) appended IN PLACE; returns out (batch, dim) in x's dtype.  bufs: a caller-placed "out"."""
     _dev_check(x, conv_state, weight, bias)
     if conv_state.dtype != torch.float32 or not conv_state.is_contiguous():
         raise RuntimeError("causal_conv1d_update: conv_state must be a contiguous fp32 (batch, dim, width) tensor")
     x = x.contiguous()
     w, bs = _f32c(weight).reshape(conv_state.shape[1], -1), _f32c(bias)
-    out = torch.empty_like(x)
+    out = _bufs(bufs, ("out",), "causal_conv1d_update")("out", x.shape, x.dtype, x.device)
     a = N.ConvUpdateArgs()
     a.batch, a.dim, a.width, a.io_dtype, a.silu = x.shape[0], x.shape[1], conv_state.shape[2], _DT[x.dtype], int(bool(silu))
     a.x, a.conv_state, a.weight, a.bias, a.out, a.stream = _ptr(x), _ptr(conv_state), _ptr(w), _ptr(bs), _ptr(out), _stream()
@@ -1665,9 +1692,10 @@ def causal_conv1d_update(x, conv_state, weight, bias=None, silu=True):
     return out
 
 
-def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False):
+def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False, bufs=None):
     """Decode-time SSM step (cm_selective_state_update; reference bimamba.py:350-362): state (batch, dim, dstate) fp32 is
-    updated IN PLACE; x, dt, z (batch, dim), B, C (batch, dstate) share one dtype; returns y (batch, dim)."""
+    updated IN PLACE; x, dt, z (batch, dim), B, C (batch, dstate) share one dtype; returns y (batch, dim).  bufs: a
+    caller-placed "out"."""
     _dev_check(state, x, dt, A, B, C, D, z, dt_bias)
     if state.dtype != torch.float32 or not state.is_contiguous():
         raise RuntimeError("selective_state_update: state must be a contiguous fp32 (batch, dim, dstate) tensor")
@@ -1675,7 +1703,7 @@ def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, 
     dt, B, C = dt.to(x.dtype).contiguous(), B.to(x.dtype).contiguous(), C.to(x.dtype).contiguous()
     z = None if z is None else z.to(x.dtype).contiguous()
     A, D, dt_bias = _f32c(A), _f32c(D), _f32c(dt_bias)
-    out = torch.empty_like(x)
+    out = _bufs(bufs, ("out",), "selective_state_update")("out", x.shape, x.dtype, x.device)
     a = N.StateUpdateArgs()
     a.batch, a.dim, a.dstate, a.io_dtype, a.dt_softplus = x.shape[0], x.shape[1], state.shape[2], _DT[x.dtype], int(bool(dt_softplus))
     a.state, a.x, a.dt, a.A, a.B, a.C, a.D, a.z, a.dt_bias, a.out = (_ptr(state), _ptr(x), _ptr(dt), _ptr(A), _ptr(B), _ptr(C), _ptr(D),
@@ -1691,12 +1719,12 @@ def mamba_step_supported(d_inner: int, d_state: int, d_conv: int, dt_rank: int, 
             and dtype in (torch.float32, torch.bfloat16))
 
 
-def mamba_step(xz, conv_state, ssm_state, conv_weight, conv_bias, x_proj_weight, dt_proj_weight, dt_bias, A, D):
+def mamba_step(xz, conv_state, ssm_state, conv_weight, conv_bias, x_proj_weight, dt_proj_weight, dt_bias, A, D, bufs=None):
     """One mixer decoding step between in_proj and out_proj in one launch (cm_mamba_step; reference bimamba.py:331-362):
     xz (batch, 2 * dim) in fp32 / bf16; conv_state (batch, dim, 4) and ssm_state (batch, dim, 16), fp32, updated IN PLACE;
     conv_weight (dim, 4), x_proj_weight (dt_rank + 32, dim), dt_proj_weight (dim, dt_rank), A = -exp(A_log) (dim, 16), conv_bias,
     dt_bias, D (dim) or None -- all used in fp32.  Returns y (batch, dim) in xz's dtype.  A shape the kernel is not built
-    for raises (code -2): nothing is launched."""
+    for raises (code -2): nothing is launched.  bufs: a caller-placed "out"."""
     _dev_check(xz, conv_state, ssm_state, conv_weight, conv_bias, x_proj_weight, dt_proj_weight, dt_bias, A, D)
     if xz.dim() != 2 or xz.shape[1] % 2:
         raise RuntimeError("mamba_step: xz must be (batch, 2 * dim)")
@@ -1713,7 +1741,7 @@ def mamba_step(xz, conv_state, ssm_state, conv_weight, conv_bias, x_proj_weight,
     a.batch, a.dim, a.dstate, a.dconv, a.dt_rank, a.io_dtype = batch, dim, ssm_state.shape[2], conv_state.shape[2], wdt.shape[1], _DT[xz.dtype]
     if cw.shape != (dim, a.dconv) or wx.shape != (a.dt_rank + 2 * a.dstate, dim) or wdt.shape[0] != dim or A.shape != (dim, a.dstate):
         raise RuntimeError("mamba_step: weight shapes do not match the states")
-    out = torch.empty((batch, dim), dtype=xz.dtype, device=xz.device)
+    out = _bufs(bufs, ("out",), "mamba_step")("out", (batch, dim), xz.dtype, xz.device)
     a.xz, a.conv_state, a.ssm_state, a.out = _ptr(xz), _ptr(conv_state), _ptr(ssm_state), _ptr(out)
     a.conv_weight, a.conv_bias, a.x_proj_weight, a.dt_proj_weight = _ptr(cw), _ptr(cb), _ptr(wx), _ptr(wdt)
     a.dt_bias, a.A, a.D, a.stream = _ptr(dt_bias), _ptr(A), _ptr(D), _stream()

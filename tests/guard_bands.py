@@ -20,6 +20,12 @@ A workspace (Guards.scratch) is NaN inside and sentinel outside: nothing outside
 although no workgroup wrote it brings NaN into a result, where assert_finite / assert_same_bits report it -- a recycled
 allocation would still hold the previous launch's correct partials there.
 
+Integer inputs (int_poisoned; indices, lengths, labels) have no NaN: their guard elements hold a value the CASE chooses -- one that
+is valid as an address (a row, class or frame the test allocated) yet names poison (a NaN cache line, a class absent from every
+target), so that a kernel that reads the guard shows it in its result and never leaves the test's memory.
+Outputs that legitimately hold -inf, or integers that may equal the sentinel byte (free=True): the plain launch's non-finite pattern is
+part of its bits -- the guarded view must hold the same bits (NaN equals nothing), finite where the plain launch is.
+
 Launch / two_step: the two-launch protocol the GPU files share (plain tensors, then poisoned inputs / guarded outputs).
 
 Plain module (as tests/ctc_beam_ref.py), any torch.device.
@@ -85,6 +91,19 @@ def poisoned(t, rows=ROW_TILE, left=0, right=0, contiguous=False, align=16, tran
     return view
 
 
+def int_poisoned(t, guard, rows=ROW_TILE, unique=True):
+    """The integer tensor t (contiguous, any rank) with ``rows`` x its last axis elements of ``guard`` in front and behind: ``guard`` is
+    the case's choice of a value that is safe to use as an index and visible in the result when used.  unique=False: the value range
+    is too small for a guard that occurs nowhere in t (one row, two utterances); the guard still names poison."""
+    assert not t.is_floating_point() and not t.is_complex() and t.dim() >= 1 and t.numel() > 0 and rows > 0, (t.dtype, tuple(t.shape), rows)
+    assert not unique or not bool((t == guard).any()), f"the guard value {guard} occurs in the tensor: a read of the guard would not show"
+    n, pad = t.numel(), rows * t.shape[-1]
+    buf = torch.full((pad + n + pad,), guard, dtype=t.dtype, device=t.device)
+    view = buf[pad:pad + n].view(t.shape)
+    view.copy_(t)
+    return view
+
+
 def scratch(numel, dtype, device, pad=4096):
     """A workspace of ``numel`` elements: NaN inside, ``pad`` sentinel elements in front and behind (at least one partial row of the
     kernel under test).  -> (buffer, view, outside mask) as guarded()."""
@@ -141,7 +160,7 @@ class Guards:
     views hold their bits; nothing outside an output or a workspace is written (a workspace's content is the kernel's own)."""
 
     def __init__(self, device):
-        self.device, self.items, self.scratches = device, {}, set()
+        self.device, self.items, self.scratches, self.free = device, {}, set(), set()
 
     def scratch(self, name, numel, dtype, pad=4096):
         assert name not in self.items, name
@@ -149,9 +168,12 @@ class Guards:
         self.scratches.add(name)
         return self.items[name][1]
 
-    def out(self, name, shape, dtype, **kw):
+    def out(self, name, shape, dtype, free=False, **kw):
+        """free: the output may hold -inf (or, an integer one, the sentinel byte's value) in the plain launch."""
         assert name not in self.items, name
         self.items[name] = guarded(shape, dtype, self.device, **kw)
+        if free:
+            self.free.add(name)
         return self.items[name][1]
 
     def view(self, name):
@@ -163,10 +185,18 @@ class Guards:
             assert_untouched(self.items[name][0], self.items[name][2], name)
         for name, want in plain.items():
             buf, view, outside = self.items[name]
-            assert_far_from_sentinel(want, name)
             assert_untouched(buf, outside, name)
-            if view.dtype.is_floating_point:
-                assert_finite(view, name)
+            if name in self.free:
+                if view.dtype.is_floating_point:
+                    assert not bool(torch.isnan(want).any()), f"{name}: the plain launch holds NaN"
+                    fin = torch.isfinite(want)
+                    if bool(fin.any()):
+                        assert_far_from_sentinel(want[fin], name)
+                    assert_finite(view[fin], name)
+            else:
+                assert_far_from_sentinel(want, name)
+                if view.dtype.is_floating_point:
+                    assert_finite(view, name)
             assert_same_bits(view, want, name)
 
 
@@ -218,14 +248,24 @@ class Launch:
         v.copy_(t)
         return v
 
+    def ints(self, t, guard, rows=ROW_TILE, unique=True):
+        """A contiguous integer input with ``rows`` x its last axis elements of ``guard`` in front and behind (int_poisoned)."""
+        return None if t is None else (int_poisoned(t, guard, rows=rows, unique=unique) if self.guard else t.clone())
+
+    def around(self, t, rows=1):
+        """A contiguous input of any rank and any alignment with ``rows`` x its last axis of NaN in front and behind (a kernel that
+        needs more alignment than the element's says so itself)."""
+        return None if t is None else (poisoned(t, rows=rows, contiguous=True, align=t.element_size()) if self.guard else t.clone())
+
     def out(self, name, shape, dtype, fill=None, **kw):
         """An output: zeros (plain) or a sentinel-guarded view; ``fill``: initial content of both (an aliased input, or 0 where the
         kernel need not write every element)."""
         shift = kw.pop("shift", 0)                    # transposed outputs only: as chan()
         if kw.get("transposed"):
             kw.update(left=LEFT + shift, right=RIGHT - shift, align=self._chan_align(shape[-1], torch.empty((), dtype=dtype).element_size(), shift))
+        free = kw.pop("free", False)
         if self.guard:
-            t = self.g.out(name, shape, dtype, **kw)
+            t = self.g.out(name, shape, dtype, free=free, **kw)
         elif kw.get("transposed"):
             t = self._plain_chan(shape, dtype, shift)
         else:

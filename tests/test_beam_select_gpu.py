@@ -3,7 +3,8 @@ same device tensors.  The contract fixes every bit: the three fp32 operations ar
 parent and token are compared with torch.equal, and inc wherever the score is finite (a -inf slot's inc is not specified).
 
 Shapes (U, B, V): the smallest; a single beam; V < B; small and odd everywhere; the recipes' beam 66 on two 64-lane tiles plus 37;
-the largest beam; and once the recipes' own 66 x 5000."""
+the largest beam; and once the recipes' own 66 x 5000.  MULTI: more than one chunk of CM_BEAM_SELECT_CHUNK = 5120 tokens per row -- a last chunk of
+one token (K = 1 < B, the rest of its list zero-filled), a last chunk of exactly B tokens, three chunks."""
 import math
 import os
 import sys
@@ -19,6 +20,7 @@ DEV = torch.device("cuda:0")
 NEG = -math.inf
 SHAPES = [(1, 1, 1), (3, 1, 37), (2, 8, 5), (3, 5, 37), (2, 66, 165), (1, 128, 300)]
 BOTH = [(3, 5, 37), (2, 66, 165)]
+MULTI = [(2, 3, 5121), (1, 128, 5248), (2, 8, 10241)]
 
 
 def _check(att, alive, B, eos, **kw):
@@ -51,7 +53,7 @@ def _eos(V):
     return 2 if V > 2 else 0
 
 
-@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("shape", SHAPES + MULTI)
 def test_random_scores(shape):
     U, B, V = shape
     att, alive, delta = _inputs(U, B, V, 1)
@@ -67,7 +69,7 @@ def test_the_recipe_shape_once():
     _check(att, alive, B, 2, delta=delta, weight=0.4, eos_blocked=blocked)
 
 
-@pytest.mark.parametrize("shape", BOTH)
+@pytest.mark.parametrize("shape", BOTH + MULTI)
 def test_masses_of_ties(shape):
     U, B, V = shape
     att, alive, delta = _inputs(U, B, V, 3)
@@ -76,8 +78,9 @@ def test_masses_of_ties(shape):
     _check(q(att), q(alive), B, _eos(V), delta=q(delta), weight=0.5)
 
 
-@pytest.mark.parametrize("shape", BOTH + [(2, 8, 5), (1, 128, 300)])
+@pytest.mark.parametrize("shape", BOTH + [(2, 8, 5), (1, 128, 300)] + MULTI)
 def test_all_equal_scores_give_the_first_flat_indices(shape):
+    """MULTI: every chunk of every row hands the merge equal scores; the first B flat indices k * V + c win across chunk boundaries."""
     U, B, V = shape
     att, alive = torch.full((U * B, V), -1.5, device=DEV), torch.full((U * B,), -2.0, device=DEV)
     score, inc, parent, token = _check(att, alive, B, _eos(V))

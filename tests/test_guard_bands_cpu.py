@@ -2,6 +2,7 @@
 one that writes a column to the left, one that writes the first row behind an utterance, one that folds a row from outside its input
 view into a row sum -- are each flagged with the tensor's name, and a correct one passes.  The GPU tests
 (tests/test_forward_guards_gpu.py) make the same calls on real kernels; this file is why they are not vacuous."""
+import math
 import os
 import sys
 
@@ -371,3 +372,62 @@ def test_fp16_outputs_take_a_sentinel_fp16_holds():
     G.assert_far_from_sentinel(torch.full((2,), 16000.0, dtype=torch.float16), "y")
     with pytest.raises(AssertionError, match="too near the sentinel"):
         G.assert_far_from_sentinel(torch.full((2,), 17000.0, dtype=torch.float16), "y")
+
+
+# what the decoding kernels add: integer inputs (indices, lengths, labels) and outputs that hold -inf -----------------------------
+def k_gather_sum(table, idx, out, extra=0):
+    """out[r] = sum over j of table[idx[r, j]]: a kernel that addresses ``table`` through an index tensor.  ``extra``: the loop over a
+    row's indices runs that many elements too far (the next row's, or what lies behind the tensor)."""
+    r, k = idx.shape
+    wide = _reach(idx, (r, k + extra))
+    out.copy_(table[wide.long()].sum(1))
+
+
+def test_integer_guard_catches_an_index_over_read():
+    """NaN cannot stand in an index tensor.  Its guard elements hold a valid row that names a NaN line of the table: the over-read is
+    an address inside the test's memory, and it shows in the result."""
+    table = torch.randn(6, 8)
+    table[5] = float("nan")                                                   # the line no index names
+    idx = torch.randint(0, 5, (3, 4), generator=torch.Generator().manual_seed(0), dtype=torch.int32)
+    p = G.int_poisoned(idx, 5, rows=2)
+    assert torch.equal(p, idx) and p.is_contiguous() and p.dtype == torch.int32
+    assert bool((_reach(p, (2, 4), -8) == 5).all()) and bool((_reach(p, (5, 4))[3:] == 5).all())   # 2 x 4 guard elements either side
+    with pytest.raises(AssertionError, match="the guard value 3 occurs in the tensor"):
+        G.int_poisoned(torch.tensor([1, 3], dtype=torch.int32), 3)
+    dense = torch.empty(3, 8)
+    k_gather_sum(table, torch.cat([idx, idx])[:3], dense, extra=1)            # in a dense batch the over-read meets valid indices
+    assert bool(torch.isfinite(dense).all())
+
+    def make(extra):
+        def run(L):                                                           # (the plain tensor has nothing behind it to read)
+            k_gather_sum(table, L.ints(idx, 5, rows=2), L.out("y", (3, 8), torch.float32, rows=4), extra if L.guard else 0)
+        return run
+    outs = G.two_step(make(0), CPU)
+    assert torch.equal(outs["y"], table[idx.long()].sum(1))
+    with pytest.raises(AssertionError, match=r"y: 8 of 24 element\(s\) not finite"):
+        G.two_step(make(1), CPU)                                              # rows 0 and 1 read the next row's first index, row 2 the guard
+
+
+def test_free_outputs_keep_the_plain_launch_minus_infinity():
+    """An output that holds -inf by contract: the guarded view must hold the plain launch's bits, -inf included, be finite where the
+    plain launch is, and NaN nowhere."""
+    want = torch.tensor([[0.5, -math.inf], [-math.inf, 2.0]])
+    with pytest.raises(AssertionError, match="score: reference not finite"):
+        g = G.Guards(CPU)
+        g.out("score", (2, 2), torch.float32, rows=4).copy_(want)
+        g.check({"score": want})
+    g = G.Guards(CPU)
+    g.out("score", (2, 2), torch.float32, rows=4, free=True).copy_(want)
+    g.check({"score": want})
+    g = G.Guards(CPU)
+    g.out("score", (2, 2), torch.float32, rows=4, free=True).copy_(torch.tensor([[0.5, -math.inf], [-math.inf, float("nan")]]))
+    with pytest.raises(AssertionError, match=r"score: 1 of 2 element\(s\) not finite"):
+        g.check({"score": want})
+    g = G.Guards(CPU)
+    g.out("score", (2, 2), torch.float32, rows=4, free=True).copy_(torch.tensor([[0.5, 1.0], [-math.inf, 2.0]]))
+    with pytest.raises(AssertionError, match=r"score: 1 of 4 element\(s\) differ from the plain launch"):
+        g.check({"score": want})
+    token = torch.tensor([G.INT_SENTINEL, 3], dtype=torch.int32)             # a token id may equal the sentinel byte
+    g = G.Guards(CPU)
+    g.out("token", (2,), torch.int32, rows=4, free=True).copy_(token)
+    g.check({"token": token})

@@ -70,11 +70,12 @@ def _run(w, xz, conv0, ssm0):
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 @pytest.mark.parametrize("batch", [1, 3])
-@pytest.mark.parametrize("E,R", [(256, 8), (288, 9), (1024, 32)])
+@pytest.mark.parametrize("E,R", [(8, 1), (256, 8), (288, 9), (1024, 32), (4096, 32)])
 def test_mamba_step_vs_fp64(E, R, batch, dtype):
     """Four consecutive steps from random non-zero states: the conv-state shift and the in-place carry of both states are
     exercised; 288 is no multiple of the 256 channels a wave's x_proj pass covers, and leaves the last pass of the
-    512-thread channel loops partly empty; dt_rank 9 is no multiple of 4."""
+    512-thread channel loops partly empty; dt_rank 9 is no multiple of 4.  (8, 1): the smallest supported row, two lanes of one
+    wave in the x_proj pass; (4096, 32): the largest, x fills its LDS array."""
     w, xz, conv0, ssm0 = _case(batch, E, R, dtype)
     got = _run(w, xz, conv0, ssm0)
     wr = {k: v.double() for k, v in w.items()}
