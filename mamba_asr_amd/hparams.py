@@ -31,6 +31,7 @@ _SB_MAP = {
     "speechbrain.nnet.losses.ctc_loss": "mamba_asr_amd.sb_compat.ctc_loss",
     "speechbrain.nnet.schedulers.NoamScheduler": "mamba_asr_amd.sb_compat.NoamScheduler",
     "speechbrain.nnet.activations.Swish": "mamba_asr_amd.sb_compat.Swish",
+    "speechbrain.utils.epoch_loop.EpochCounter": "mamba_asr_amd.sb_compat.EpochCounter",
 }
 
 

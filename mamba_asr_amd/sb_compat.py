@@ -222,6 +222,10 @@ class Fbank(nn.Module):
         ``causal_top_db``: the floor of frame f is max(dB of frames 0..f) - top_db instead of the utterance's maximum - top_db: the
         clamp a streamed front end can apply (fused.frontend_streaming), which is the default one whenever no value of the utterance
         lies under its maximum - top_db.  Computed in torch on any device (the features a causal model is trained on)."""
+        if self.window.device != wav.device:
+            # a recipe keeps compute_features outside `modules` (hparams/CTC/*.yaml), so no Brain ever moves it: follow the input,
+            # as speechbrain's STFT / Filterbank do
+            self.to(wav.device)
         with torch.autocast(device_type=wav.device.type, enabled=False):          # speechbrain forces fp32 here
             if causal_top_db:
                 spec = torch.stft(wav.float(), self.n_fft, self.hop, self.win, self.window, center=True,
@@ -598,3 +602,28 @@ class NoamScheduler:
 
     def load_state_dict(self, sd):
         self.n_steps = sd["n_steps"]
+
+
+class EpochCounter:
+    """speechbrain.utils.epoch_loop.EpochCounter(limit): ``current`` starts at 0; iterating yields 1, 2, ... limit and sets
+    ``current`` BEFORE yielding, so the recipes read the running epoch from it inside the loop (train_CTC.py:287:
+    normalize(feats, wav_lens, epoch=self.hparams.epoch_counter.current)); a counter whose ``current`` was restored to k
+    (a recovered checkpoint) continues at k + 1."""
+
+    def __init__(self, limit):
+        self.current, self.limit = 0, int(limit)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self.current >= self.limit:
+            raise StopIteration
+        self.current += 1
+        return self.current
+
+    def state_dict(self):
+        return {"current": self.current}
+
+    def load_state_dict(self, sd):
+        self.current = int(sd["current"])

@@ -64,8 +64,10 @@ def _hook_torch_dropouts(model, store):
     return [mods[mod].register_forward_hook(lambda m, i, o, site=site: store.__setitem__(site, (o, m.p))) for site, mod in _site_names()]
 
 
-def _gpu_step(model, wavs, lens, tokens, tok_lens, autocast, monkeypatch):
-    """One forward + backward; -> (loss, grads, kernel names, seeds in draw order, CNN masks, (src dropout in, out, p))."""
+def _gpu_step(model, wavs, lens, tokens, tok_lens, autocast, monkeypatch, step=None):
+    """One forward + backward; -> (loss, grads, kernel names, seeds in draw order, CNN masks, (src dropout in, out, p)).
+    ``step``: a callable returning the loss instead of model.forward_ctc + model.ctc_objective (tests/test_recipe_surface_gpu.py
+    runs the recipe's own objects); ``model`` is then any module holding CNN / Transformer / ctc_lin under those names."""
     from mamba_asr_amd import ops
     seeds, cnn, src = [], [], []
     draw = ops.draw_seed
@@ -86,8 +88,11 @@ def _gpu_step(model, wavs, lens, tokens, tok_lens, autocast, monkeypatch):
     ops.LAUNCH_LOG = []
     try:
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
-            logp = model.forward_ctc(wavs, lens)
-            loss = model.ctc_objective(logp.float(), tokens.to(DEV), lens, tok_lens.to(DEV))
+            if step is not None:
+                loss = step()
+            else:
+                logp = model.forward_ctc(wavs, lens)
+                loss = model.ctc_objective(logp.float(), tokens.to(DEV), lens, tok_lens.to(DEV))
         loss.backward()
         torch.cuda.synchronize()
         names = {e[0] for e in ops.LAUNCH_LOG}
@@ -101,12 +106,12 @@ def _gpu_step(model, wavs, lens, tokens, tok_lens, autocast, monkeypatch):
     return loss.detach(), grads, names, seeds, cnn, src, tdrop
 
 
-def _masks(model, seeds, cnn, src, tdrop, rows, t, epochs=None):
+def _masks(model, seeds, cnn, src, tdrop, rows, t, epochs=None, cfg=None):
     """Every site's multiplier as an fp64 CPU tensor, keyed as the oracle expects: native sites (in forward order, one seed each)
     from the host restatement, module-tree sites from their recorded nn.Dropout output.  ``epochs`` {site: epoch} overrides the
-    epoch the host restatement uses for a site (the negative control)."""
+    epoch the host restatement uses for a site (the negative control).  ``cfg``: for a ``model`` that carries none."""
     from oracle import conmamba_oracle as O
-    cfg = model.cfg
+    cfg = model.cfg if cfg is None else cfg
     b = rows // t
     native = [name for name, _ in _site_names() if name not in tdrop]
     assert len(seeds) == len(native), (len(seeds), native)
@@ -126,20 +131,32 @@ def _masks(model, seeds, cnn, src, tdrop, rows, t, epochs=None):
     return m
 
 
-def _oracle(cfg, model, wavs, lens, tokens, tok_lens, masks):
-    """The step on the CPU in fp64 (Fbank fp32, as in the product), dropout = the given masks, torch autograd."""
+def _oracle_logp(cfg, model, wavs, masks, features=None):
+    """The forward on the CPU in fp64 (Fbank fp32, as in the product), dropout = the given masks (None: eval mode)
+    -> (fp64 parameters with requires_grad, log-probabilities).  ``features``: callable (the oracle's fp32 Fbank output) -> the
+    normalised, possibly augmented fp64 features; default: normalised with the model's own statistics."""
     from oracle import conmamba_oracle as O
     sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
     p = {k: (v.double().requires_grad_(True) if v.is_floating_point() else v) for k, v in sd.items()}
     feats = O.fbank(wavs.cpu(), n_fft=cfg.n_fft, win_ms=cfg.win_length)
-    feats = ((feats - sd["normalize.glob_mean"]) / sd["normalize.glob_std"]).double()
+    if features is not None:
+        feats = features(feats)
+    else:
+        feats = ((feats - sd["normalize.glob_mean"]) / sd["normalize.glob_std"]).double()
     src = O.cnn_frontend(p, feats, "CNN.", masks)
     src = O.src_projection(p, src, "Transformer.", masks)
     enc = O.encoder(p, src, LAYERS, "Transformer.encoder.", masks=masks)
-    logp = torch.log_softmax(F.linear(enc, p["ctc_lin.w.weight"], p["ctc_lin.w.bias"]), -1)
+    return p, torch.log_softmax(F.linear(enc, p["ctc_lin.w.weight"], p["ctc_lin.w.bias"]), -1)
+
+
+def _oracle(cfg, model, wavs, lens, tokens, tok_lens, masks, features=None, reduction="batchmean"):
+    """The step on the CPU in fp64 (Fbank fp32, as in the product), dropout = the given masks, torch autograd.  ``reduction``:
+    the recipe's loss_reduction (speechbrain's ctc_loss: 'batchmean' = sum / batch, 'mean' = sum / target tokens, 'sum')."""
+    p, logp = _oracle_logp(cfg, model, wavs, masks, features)
     b, t, _ = logp.shape
     il, tl = torch.round(lens.cpu() * t).int(), torch.round(tok_lens * tokens.shape[1]).int()
-    loss = F.ctc_loss(logp.transpose(0, 1), tokens, il, tl, 0, reduction="sum", zero_infinity=True) / b
+    loss = F.ctc_loss(logp.transpose(0, 1), tokens, il, tl, 0, reduction="sum", zero_infinity=True)
+    loss = {"batchmean": loss / b, "mean": loss / tl.sum(), "sum": loss}[reduction]
     names = [k for k, _ in model.named_parameters()]
     grads = torch.autograd.grad(loss, [p[k] for k in names], allow_unused=True)
     return loss.detach(), {k: g for k, g in zip(names, grads) if g is not None}
