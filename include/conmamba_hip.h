@@ -437,6 +437,40 @@ typedef struct cm_ctc_args {
 int64_t cm_ctc_workspace_floats(int32_t batch, int32_t T, int32_t S);
 int cm_ctc_loss(const cm_ctc_args *args);
 
+/* CTC forced alignment (csrc/ctc_align.hip; contract: mamba_asr_amd/ctc_decode.py): the Viterbi path of a known
+ * label sequence through the CTC trellis -- cm_ctc_loss's alpha recurrence with max for logsumexp, in float64 adds and strict
+ * compares only, plus a backtrace.  One workgroup per utterance; bit-reproducible and independent of batch composition.
+ * log_probs: lp_rows rows of (T, V) fp32 or bf16 with unit vocabulary stride, lp_bs / lp_ts elements apart; utterance b reads row
+ * rows[b] (rows NULL: row b, and lp_rows >= batch), so hypotheses of one utterance share its frames; a row outside [0, lp_rows)
+ * gives status 1.  targets (batch, S) int64 padded, NULL exactly when S == 0; ids at or past target_lengths[b] are never read; an
+ * id outside [0, V) scores -inf.  n = min(input_lengths[b], T) frames and L = min(target_lengths[b], S) labels are aligned (negative
+ * lengths count as 0).  S <= 1023.
+ * Outputs: status[b] 0 aligned / 1 no alignment (score -inf) / 2 NaN on the lattice (score NaN); score (batch) fp64; states
+ * (batch, T) int32 = the extended-sequence state of every frame < n, -1 elsewhere and wherever status != 0; starts / ends
+ * (batch, S) int32 = first frame and one past the last frame of label j in state 2 j + 1, -1 for j >= L or status != 0;
+ * label_logp (batch, S) fp64 = the left fold of the label's own frames' log-probabilities, 0 where starts is -1.
+ * workspace: cm_ctc_align_workspace_bytes() bytes, 16-byte aligned (the moves, 2 bits per trellis cell).  Arguments are validated
+ * on the host before any launch (CM_EINVAL / CM_EUNSUPPORTED / CM_EALIGN). */
+typedef struct cm_ctc_align_args {
+    int32_t batch, T, V, S, blank, dtype;     /* dtype: CM_F32 or CM_BF16                                       */
+    int64_t lp_rows, lp_bs, lp_ts;            /* rows of log_probs; element strides of row and time             */
+    const void *log_probs;
+    const int64_t *targets;                   /* (batch, S)                                                     */
+    const int32_t *input_lengths, *target_lengths;   /* (batch)                                                 */
+    const int32_t *rows;                      /* (batch) or NULL                                                */
+    double *score;                            /* (batch)                                                        */
+    int32_t *status;                          /* (batch)                                                        */
+    int32_t *states;                          /* (batch, T)                                                     */
+    int32_t *starts, *ends;                   /* (batch, S); may be NULL when S == 0                            */
+    double *label_logp;                       /* (batch, S); may be NULL when S == 0                            */
+    void *workspace;                          /* cm_ctc_align_workspace_bytes() bytes                           */
+    int64_t workspace_bytes;
+    void *stream;
+} cm_ctc_align_args;
+
+int64_t cm_ctc_align_workspace_bytes(const cm_ctc_align_args *args);
+int cm_ctc_align(const cm_ctc_align_args *args);
+
 /* LM-free CTC beam search (csrc/ctc_beam.hip; replaces speechbrain.decoders.ctc.CTCBeamSearcher, reference train_CTC.py:309-310,
  * 411-414 and 1155-1161).  The algorithm (mamba_asr_amd/ctc_decode.py): per processed frame select tokens, extend
  * every beam, merge equal (text, partial word, last token), prune by beam_prune_logp, rank, keep beam_size, optionally prune the

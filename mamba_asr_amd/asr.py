@@ -267,6 +267,38 @@ class ConMambaASR(nn.Module):
             return searcher(torch.where(own, enc, torch.zeros((), dtype=enc.dtype, device=enc.device)), rel)
         return searcher(self.encode(wavs, wav_lens), wav_lens)
 
+    @property
+    def row_seconds(self) -> float:
+        """Nominal duration of one encoder row: hop x (product of the CNN's time strides) / sample_rate (0.04 s in the recipe)."""
+        stride = 1
+        for blk in self.CNN.blocks:
+            stride *= int(blk.conv.stride[0])
+        return self.compute_features.hop * stride / float(self.cfg.sample_rate)
+
+    @torch.no_grad()
+    def align(self, wavs, wav_lens, targets, target_lens, aligner):
+        """CTC forced alignment of known transcripts: encode(..., ragged=True), the CTC head, then ``aligner`` (a
+        ctc_decode.CTCAligner) with lengths=row_lens -> List[CTCAlignment] with token_times / word_times filled, (start, end) in
+        seconds.  Runs in eval mode (the caller's mode is restored).  The times are NOMINAL row times, frame x row_seconds: row r is
+        taken to cover [r, r + 1) x row_seconds although the front end's receptive field is wider and centred frames start half a
+        window early; a span's end is clipped to the utterance's duration."""
+        from . import fused
+        was_training = self.training
+        self.eval()
+        try:
+            enc, row_lens = self.encode(wavs, wav_lens, ragged=True)
+            lp = torch.log_softmax(self.ctc_lin(enc), dim=-1)
+            out = aligner(lp, targets, target_lens, lengths=row_lens)
+        finally:
+            self.train(was_training)
+        n = fused.ragged_sample_counts(wav_lens, wavs.shape[1], self.compute_features.hop)
+        rs = self.row_seconds
+        for al, samples in zip(out, n):
+            dur = samples / float(self.cfg.sample_rate)
+            al.token_times = [(a * rs, min(z * rs, dur)) for a, z in al.token_frames]
+            al.word_times = [(a * rs, min(z * rs, dur)) for a, z in al.word_frames]
+        return out
+
     def s2s_objective(self, p_ctc, p_seq, tokens, tokens_lens, tokens_eos, tokens_eos_lens, wav_lens, ctc_weight=0.3,
                       label_smoothing=0.1, pad_idx=0):
         """train_S2S.py:518-529: ctc_weight * CTC(p_ctc, tokens) + (1 - ctc_weight) * label-smoothed KL(p_seq, tokens_eos)."""

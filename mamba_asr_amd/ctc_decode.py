@@ -67,6 +67,28 @@ text "", score 0.0 and lm_score = LM("") by the same rules (the </s> term alone)
 inert.  StreamingCTCBeamLMSearcher carries this search across chunks (ops.ctc_beam_lm_stream, csrc/ctc_beam_lm_stream.hip;
 DESIGN.md §4q): every beam's LM state lives in the stream's slab beside its identity, and hypotheses() after n frames is what the
 search above returns for n_b = n, lm_score bits included.  StreamingCTCBeamSearcher itself stays LM-free and refuses a path.
+
+Forced alignment (CTCAligner, CTCBeamSearcher.search(..., text_frames=True); ops.ctc_align, csrc/ctc_align.hip): the
+best path of a KNOWN label sequence through the CTC trellis, pinned bit for bit by tests/ctc_align_ref.py.  Per utterance
+n = min(input_lengths[b], T), L = min(target_lengths[b], S); the extended sequence e has E = 2 L + 1 entries, e[2j] = blank,
+e[2j+1] = y_j; x_t(s) = (double) lp[row, t, e[s]] (fp32 or bf16 in, the conversion is exact; a label outside [0, V) has x = -inf).
+  D_0(s) = x_0(s) for s in {0, 1} with s < E, else -inf.  For t >= 1 the candidates are c0 = D_{t-1}(s); c1 = D_{t-1}(s-1) when
+  s >= 1; c2 = D_{t-1}(s-2) when s is odd, s >= 3 and e[s] != e[s-2].  best = c0, move 0; if c1 > best: best = c1, move 1; if
+  c2 > best: best = c2, move 2 (strict: ties keep the smaller move).  D_t(s) = best + x_t(s) in float64.
+  End: sE = E-1; if E >= 2 and D_{n-1}(E-2) > D_{n-1}(E-1), sE = E-2.  score = D_{n-1}(sE); s_{n-1} = sE and
+  s_{t-1} = s_t - move_t(s_t).
+Every operation is a float64 add or compare, so the kernel's bits are the reference's by construction, ties included.
+status 0: aligned.  1: no alignment (score == -inf, or n == 0 with L > 0; a row index outside log_probs as well).  2: some x_t(s)
+with t < n, s < E is NaN (tracked by a flag, not through max; also a NaN score, which +inf inputs can make); NaN anywhere else in
+log_probs has no effect.  n == 0 and L == 0: status 0, score 0.0, an empty path.
+Outputs: score (B) fp64 (-inf under status 1, NaN under 2); status (B) int32; states (B, T) int32 = s_t for t < n, -1 elsewhere,
+all -1 when status != 0; starts / ends (B, S) int32 = label j's first frame and one past its last frame in state 2j+1, -1 for
+j >= L or status != 0; label_logp (B, S) fp64 = the left fold, in increasing t, of x_t(2j+1) over the label's frames, 0.0 where
+starts is -1.  At most 1023 labels per utterance.
+Words.  A word is the tokens between word-starts, by the rules of compose(): its span runs from its first token's start to its
+last token's end, its log-probability is the sum of its tokens'; a piece whose clean part is empty (the bare space piece, a bare
+spm_token) and blank belong to no word.  CTCBeamSearcher.search(text_frames=True) aligns each returned hypothesis' own tokens in one
+extra launch: those are the Viterbi frames of the hypothesis, not the frames at which the beam emitted its tokens.
 """
 from __future__ import annotations
 
@@ -111,6 +133,58 @@ def _join(a: str, b: str) -> str:
     return a if not b else (b if not a else a + " " + b)
 
 
+def classify_vocab(vocab: Sequence[str], blank_index: int, space_token: str, spm_token: str):
+    """The token classes of the module docstring -> (is_spm, classes, clean parts), one entry per piece."""
+    is_spm = any(p.startswith(spm_token) for p in vocab)
+    classes, cleans = [], []
+    for v, p in enumerate(vocab):
+        if v == blank_index:
+            cls, clean = BLANK, ""
+        elif is_spm and p.startswith(spm_token):
+            cls, clean = WORD_START, p[len(spm_token):]
+        elif not is_spm and p == space_token:
+            cls, clean = WORD_START, ""
+        else:
+            cls, clean = CHAR, p
+        classes.append(cls)
+        cleans.append(clean)
+    return is_spm, classes, cleans
+
+
+def group_words(tokens, starts, ends, logp, classes, clean):
+    """Aligned tokens -> (words, word_frames [(start, end)], word_logp), all host lists: ``tokens`` the label ids, ``starts`` /
+    ``ends`` / ``logp`` their frames and log-probabilities, ``classes`` / ``clean`` the vocabulary's (classify_vocab).  The words
+    are those of compose(tokens), in order; a token with an empty clean part and blank belong to no word."""
+    words, frames, lps = [], [], []
+    cur = None                                   # [text, start, end, logp] of the word being built
+
+    def commit():
+        if cur is not None and cur[0]:
+            words.append(cur[0])
+            frames.append((cur[1], cur[2]))
+            lps.append(cur[3])
+    for v, a, z, lp in zip(tokens, starts, ends, logp):
+        if classes[v] == BLANK:
+            continue
+        if classes[v] == WORD_START:
+            commit()
+            cur = None
+        if not clean[v]:
+            continue
+        if cur is None:
+            cur = [clean[v], int(a), int(z), float(lp)]
+        else:
+            cur[0], cur[2], cur[3] = cur[0] + clean[v], int(z), cur[3] + float(lp)
+    commit()
+    return words, frames, lps
+
+
+def _frame_counts(steps: int, wav_lens: Optional[torch.Tensor], batch: int) -> List[int]:
+    if wav_lens is None:
+        return [steps] * batch
+    return [min(max(int(round(rel * steps)), 0), steps) for rel in wav_lens.detach().cpu().tolist()]
+
+
 class CTCBeamSearcher:
     """CTC beam search without a language model, on the GPU (constructor keywords of speechbrain's CTCBeamSearcher).
 
@@ -140,19 +214,7 @@ class CTCBeamSearcher:
         self.beam_size, self.topk, self.prune_history = int(beam_size), int(topk), bool(prune_history)
         self.beam_prune_logp, self.token_prune_min_logp = float(beam_prune_logp), float(token_prune_min_logp)
         self.blank_skip_threshold = float(blank_skip_threshold)
-        self.is_spm = any(p.startswith(spm_token) for p in vocab)
-        self.classes, self.clean = [], []
-        for v, p in enumerate(vocab):
-            if v == self.blank_index:
-                cls, clean = BLANK, ""
-            elif self.is_spm and p.startswith(spm_token):
-                cls, clean = WORD_START, p[len(spm_token):]
-            elif not self.is_spm and p == space_token:
-                cls, clean = WORD_START, ""
-            else:
-                cls, clean = CHAR, p
-            self.classes.append(cls)
-            self.clean.append(clean)
+        self.is_spm, self.classes, self.clean = classify_vocab(vocab, self.blank_index, space_token, spm_token)
         hashes = [piece_hash(c) for c in self.clean]
         self.tok_class = torch.tensor([1 if c == WORD_START else 0 for c in self.classes], dtype=torch.int32)
         self.tok_hash = torch.tensor([h for h, _ in hashes], dtype=torch.int64)
@@ -196,14 +258,22 @@ class CTCBeamSearcher:
         return self._dev_tables[key]
 
     def frame_counts(self, steps: int, wav_lens: Optional[torch.Tensor], batch: int) -> List[int]:
-        if wav_lens is None:
-            return [steps] * batch
-        return [min(max(int(round(rel * steps)), 0), steps) for rel in wav_lens.detach().cpu().tolist()]
+        return _frame_counts(steps, wav_lens, batch)
 
     def __call__(self, log_probs: torch.Tensor, wav_lens: Optional[torch.Tensor] = None, lengths=None) -> List[List[CTCHypothesis]]:
         """``lengths``: absolute frame counts per utterance (a host sequence of ints, e.g. the fused.RowLens of
         ConMambaASR.encode(..., ragged=True)); it wins over ``wav_lens``, whose round(rel * T) can miss an utterance's own row count
-        by one."""
+        by one.  text_frames stays None: search(..., text_frames=True) is the call that fills it."""
+        return self.search(log_probs, wav_lens, lengths)
+
+    def search(self, log_probs: torch.Tensor, wav_lens: Optional[torch.Tensor] = None, lengths=None,
+               text_frames: bool = False) -> List[List[CTCHypothesis]]:
+        """__call__ with one more keyword (speechbrain's call signature is left as it is).  ``text_frames=True``: every returned
+        hypothesis gets text_frames = [(start_frame, end_frame), ...], one span per word of its text, from ONE extra cm_ctc_align
+        launch over all returned hypotheses' tokens (the topk hypotheses of an utterance share its frames through ``rows``).  These
+        are the Viterbi frames of the hypothesis' tokens, not the frames at which the beam emitted them.  A hypothesis of more
+        than 1023 tokens raises ValueError.  The default leaves text_frames None.  Whole-utterance searches only: the streaming
+        searchers do not take it."""
         if not log_probs.is_cuda:
             raise RuntimeError("CTCBeamSearcher runs on the GPU only (got a CPU tensor): move log_probs to the GPU")
         if log_probs.dim() != 3 or log_probs.shape[2] != len(self.vocab_list):
@@ -218,7 +288,7 @@ class CTCBeamSearcher:
         if steps == 0:
             empty = 0.0 if self.lm is None else self.lm.lm_of_text("", self.alpha, self.beta, self.unk_score_offset,
                                                                    self.score_boundary, finish=True)
-            return [[CTCHypothesis("", None, 0.0, empty, None)] for _ in range(b)]
+            return [[CTCHypothesis("", None, 0.0, empty, [] if text_frames else None)] for _ in range(b)]
         lengths = torch.tensor(counts, dtype=torch.int32).to(log_probs.device)
         tc, th, tp = self._tables(log_probs.device)
         if self.lm is not None:
@@ -229,12 +299,38 @@ class CTCBeamSearcher:
                 lm_unk=lm.unk, alpha=self.alpha, beta=self.beta, unk_score_offset=self.unk_score_offset, blank=self.blank_index,
                 beam_size=self.beam_size, topk=self.topk, prune_history=self.prune_history, beam_prune_logp=self.beam_prune_logp,
                 token_prune_min_logp=self.token_prune_min_logp, blank_skip_threshold=self.blank_skip_threshold)
-            return self._hypotheses(tokens, token_len, scores, num_hyps, bad, range(b), "utterance", lm_scores=lm_scores)
+            out = self._hypotheses(tokens, token_len, scores, num_hyps, bad, range(b), "utterance", lm_scores=lm_scores)
+            return self._text_frames(out, log_probs, lengths, tokens, token_len) if text_frames else out
         tokens, token_len, scores, num_hyps, bad = ops.ctc_beam_search(
             log_probs, lengths, tc, th, tp, HASH_BASE, HASH_SEP, blank=self.blank_index, beam_size=self.beam_size,
             topk=self.topk, prune_history=self.prune_history, beam_prune_logp=self.beam_prune_logp,
             token_prune_min_logp=self.token_prune_min_logp, blank_skip_threshold=self.blank_skip_threshold)
-        return self._hypotheses(tokens, token_len, scores, num_hyps, bad, range(b), "utterance")
+        out = self._hypotheses(tokens, token_len, scores, num_hyps, bad, range(b), "utterance")
+        return self._text_frames(out, log_probs, lengths, tokens, token_len) if text_frames else out
+
+    def _text_frames(self, hyps, log_probs, lengths, tokens, token_len):
+        """Word spans for the hypotheses of a whole-utterance search: one cm_ctc_align launch over the (batch x topk) token
+        sequences the kernel returned (rows past num_hyps hold no tokens and align as empty), then the word grouping."""
+        b, topk, _ = tokens.shape
+        lens = token_len.cpu().tolist()
+        lmax = max((lens[u][h] for u in range(b) for h in range(len(hyps[u]))), default=0)
+        if lmax > 1023:
+            raise ValueError(f"{type(self).__name__}: text_frames aligns at most 1023 tokens per hypothesis, got {lmax}")
+        dev = log_probs.device
+        tl = token_len.reshape(-1).clamp(max=lmax)
+        _, status, _, starts, ends, logp = ops.ctc_align(
+            log_probs, tokens.reshape(b * topk, -1)[:, :lmax], lengths.repeat_interleave(topk), tl, blank=self.blank_index,
+            rows=torch.arange(b, dtype=torch.int32, device=dev).repeat_interleave(topk))
+        status, starts, ends, logp = status.cpu().tolist(), starts.cpu().tolist(), ends.cpu().tolist(), logp.cpu().tolist()
+        tok = tokens[:, :, :lmax].cpu().tolist()
+        for u in range(b):
+            for h, hyp in enumerate(hyps[u]):
+                r, k = u * topk + h, lens[u][h]
+                if status[r] != 0:
+                    raise ValueError(f"{type(self).__name__}: the tokens of hypothesis {h} of utterance {u} have no alignment "
+                                     f"(status {status[r]})")
+                hyp.text_frames = group_words(tok[u][h][:k], starts[r][:k], ends[r][:k], logp[r][:k], self.classes, self.clean)[1]
+        return hyps
 
     def _hypotheses(self, tokens, token_len, scores, num_hyps, bad, rows, what, lm_scores=None) -> List[List[CTCHypothesis]]:
         """The kernel's outputs of the named rows, read to the host: NaN check, then one list of hypotheses per row."""
@@ -258,6 +354,95 @@ class CTCBeamSearcher:
     def decode_beams(self, log_probs, wav_lens=None, lm_start_state=None):
         """speechbrain's name for the same call."""
         return self(log_probs, wav_lens)
+
+
+@dataclass
+class CTCAlignment:
+    """One utterance's forced alignment.  status 0: aligned; 1: the labels do not fit the frames (the lists are empty, score is
+    -inf).  Frames are half-open spans [start, end) of log_probs rows; ConMambaASR.align adds token_times / word_times in seconds."""
+    status: int
+    score: float
+    tokens: List[int]
+    token_frames: List[tuple]
+    token_logp: List[float]
+    words: List[str]
+    word_frames: List[tuple]
+    word_logp: List[float]
+    token_times: Optional[List[tuple]] = None
+    word_times: Optional[List[tuple]] = None
+
+
+class CTCAligner:
+    """CTC forced alignment of known label sequences on the GPU (cm_ctc_align; the contract is in the module docstring).
+
+    __call__(log_probs (batch, T, V) on the GPU, targets: a padded (batch, S) integer tensor or a list of id lists, target_lens
+    (batch) label counts (None with a list of lists), wav_lens relative lengths or None, lengths=None: absolute frame counts, which
+    win when given) -> List[CTCAlignment].  Status 2 (NaN on the lattice) raises ValueError naming the utterance.  There is no host
+    implementation: CPU tensors raise."""
+
+    def __init__(self, blank_index: int, vocab_list: Sequence[str], space_token: str = " ", spm_token: str = "▁"):
+        vocab = list(vocab_list)
+        if not 0 <= blank_index < len(vocab):
+            raise ValueError(f"CTCAligner: blank_index {blank_index} outside a vocabulary of {len(vocab)}")
+        self.blank_index, self.vocab_list = int(blank_index), vocab
+        self.space_token, self.spm_token = space_token, spm_token
+        self.is_spm, self.classes, self.clean = classify_vocab(vocab, self.blank_index, space_token, spm_token)
+
+    def words(self, tokens, starts, ends, logp):
+        """group_words with this vocabulary's classes."""
+        return group_words(tokens, starts, ends, logp, self.classes, self.clean)
+
+    def __call__(self, log_probs: torch.Tensor, targets, target_lens=None, wav_lens: Optional[torch.Tensor] = None,
+                 lengths=None) -> List[CTCAlignment]:
+        if not log_probs.is_cuda:
+            raise RuntimeError("CTCAligner runs on the GPU only (got a CPU tensor): move log_probs to the GPU")
+        if log_probs.dim() != 3 or log_probs.shape[2] != len(self.vocab_list):
+            raise ValueError(f"CTCAligner: log_probs must be (batch, T, {len(self.vocab_list)}), got {tuple(log_probs.shape)}")
+        b, steps, v = log_probs.shape
+        dev = log_probs.device
+        if isinstance(targets, torch.Tensor):
+            if targets.dim() != 2 or targets.shape[0] != b or target_lens is None:
+                raise ValueError(f"CTCAligner: a targets tensor must be ({b}, S) and come with target_lens")
+            tl = [int(x) for x in (target_lens.detach().cpu().tolist() if isinstance(target_lens, torch.Tensor) else target_lens)]
+            ids = targets.detach().cpu().tolist()
+        else:
+            ids = [[int(x) for x in row] for row in targets]
+            tl = [len(row) for row in ids] if target_lens is None else [int(x) for x in target_lens]
+        if len(ids) != b or len(tl) != b or any(not 0 <= k <= len(row) for k, row in zip(tl, ids)):
+            raise ValueError(f"CTCAligner: need {b} label sequences and {b} target_lens within them, got lengths {tl}")
+        ids = [row[:k] for row, k in zip(ids, tl)]
+        for u, row in enumerate(ids):
+            if any(not 0 <= x < v for x in row):
+                raise ValueError(f"CTCAligner: utterance {u} has a label outside the vocabulary of {v}")
+        s = max(tl, default=0)
+        if s > 1023:
+            raise ValueError(f"CTCAligner: at most 1023 labels per utterance, got {s}")
+        if lengths is None:
+            counts = _frame_counts(steps, wav_lens, b)
+        else:
+            counts = [int(x) for x in lengths]
+            if len(counts) != b or any(not 0 <= x <= steps for x in counts):
+                raise ValueError(f"CTCAligner: lengths must be {b} frame counts in [0, {steps}], got {counts}")
+        if steps == 0:
+            return [CTCAlignment(0 if not row else 1, 0.0 if not row else -math.inf, [], [], [], [], [], []) for row in ids]
+        padded = torch.tensor([row + [0] * (s - len(row)) for row in ids], dtype=torch.int64).reshape(b, s).to(dev)
+        score, status, _, starts, ends, logp = ops.ctc_align(
+            log_probs, padded, torch.tensor(counts, dtype=torch.int32).to(dev), torch.tensor(tl, dtype=torch.int32).to(dev),
+            blank=self.blank_index)
+        score, status = score.cpu().tolist(), status.cpu().tolist()
+        starts, ends, logp = starts.cpu().tolist(), ends.cpu().tolist(), logp.cpu().tolist()
+        out = []
+        for u, row in enumerate(ids):
+            if status[u] == 2:
+                raise ValueError(f"CTCAligner: log_probs of utterance {u} hold NaN on its alignment lattice")
+            if status[u] != 0:
+                out.append(CTCAlignment(status[u], score[u], [], [], [], [], [], []))
+                continue
+            k = len(row)
+            a, z, lp = starts[u][:k], ends[u][:k], logp[u][:k]
+            words, frames, wlp = self.words(row, a, z, lp)
+            out.append(CTCAlignment(0, score[u], row, list(zip(a, z)), lp, words, frames, wlp))
+        return out
 
 
 class CTCStreamState:

@@ -864,6 +864,49 @@ def ctc_loss_grad(log_probs, targets, input_lengths, target_lengths, blank=0, bu
     return nll, grad
 
 
+def ctc_align(log_probs, targets, input_lengths, target_lengths, blank=0, rows=None, bufs=None):
+    """CTC forced alignment (cm_ctc_align; the contract is in mamba_asr_amd.ctc_decode's docstring).  log_probs (R, T, V) fp32 /
+    bf16 passed with its strides (unit vocabulary stride; other dtypes are cast to fp32), targets (batch, S) integer labels padded,
+    input_lengths / target_lengths (batch) integer tensors; rows (batch) or None: the log_probs row each utterance reads (None:
+    its own, and R = batch), so several label sequences can share one utterance's frames.
+    -> (score (batch) fp64, status (batch) int32, states (batch, T) int32, starts, ends (batch, S) int32, label_logp (batch, S)
+    fp64).  bufs: caller-placed "score", "status", "states", "starts", "ends", "label_logp" and "workspace" (uint8,
+    cm_ctc_align_workspace_bytes)."""
+    _dev_check(log_probs, targets, input_lengths, target_lengths, rows)
+    if log_probs.dim() != 3 or targets.dim() != 2:
+        raise RuntimeError(f"ctc_align: log_probs must be (rows, T, V) and targets (batch, S), got {tuple(log_probs.shape)} and {tuple(targets.shape)}")
+    if log_probs.dtype not in (torch.float32, torch.bfloat16):
+        log_probs = log_probs.float()
+    lp = log_probs.detach()
+    if lp.stride(2) != 1:
+        lp = lp.contiguous()
+    r, t, v = lp.shape
+    dev = lp.device
+    tg = targets.detach().to(torch.int64).contiguous()
+    b, s = tg.shape
+    il, tl = input_lengths.detach().to(torch.int32).contiguous(), target_lengths.detach().to(torch.int32).contiguous()
+    rw = None if rows is None else rows.detach().to(torch.int32).contiguous()
+    if il.numel() != b or tl.numel() != b or (rw is not None and rw.numel() != b) or (rw is None and r != b):
+        raise RuntimeError(f"ctc_align: {b} target rows need {b} input_lengths, target_lengths and rows (or, without rows, {b} rows of log_probs)")
+    take = _bufs(bufs, ("score", "status", "states", "starts", "ends", "label_logp", "workspace"), "ctc_align")
+    score, status = take("score", (b,), torch.float64, dev), take("status", (b,), torch.int32, dev)
+    states = take("states", (b, t), torch.int32, dev)
+    starts, ends = take("starts", (b, s), torch.int32, dev), take("ends", (b, s), torch.int32, dev)
+    label_logp = take("label_logp", (b, s), torch.float64, dev)
+    a = N.CtcAlignArgs()
+    a.batch, a.T, a.V, a.S, a.blank, a.dtype = b, t, v, s, int(blank), _DT[lp.dtype]
+    a.lp_rows, a.lp_bs, a.lp_ts = r, lp.stride(0), lp.stride(1)
+    a.log_probs, a.targets, a.input_lengths, a.target_lengths, a.rows = _ptr(lp), (_ptr(tg) if s else None), _ptr(il), _ptr(tl), _ptr(rw)
+    a.score, a.status, a.states = _ptr(score), _ptr(status), _ptr(states)
+    if s:
+        a.starts, a.ends, a.label_logp = _ptr(starts), _ptr(ends), _ptr(label_logp)
+    nws = int(N.lib().cm_ctc_align_workspace_bytes(ct.byref(a)))
+    ws = take("workspace", (max(nws, 1),), torch.uint8, dev)
+    a.workspace, a.workspace_bytes, a.stream = _ptr(ws), nws, _stream()
+    _launch("cm_ctc_align", N.lib().cm_ctc_align, a, units=b * t)
+    return score, status, states, starts, ends, label_logp
+
+
 def _ctc_beam_args(what, a, log_probs, dev, tok_class, tok_hash, tok_pow, tok_len, hash_base, hash_sep, blank, beam_size, topk,
                    prune_history, beam_prune_logp, token_prune_min_logp, blank_skip_threshold):
     """What the three CTC beam searches prepare alike, filled into their argument struct ``a``: log_probs as fp32 / bf16 with unit
