@@ -471,6 +471,67 @@ typedef struct cm_ctc_align_args {
 int64_t cm_ctc_align_workspace_bytes(const cm_ctc_align_args *args);
 int cm_ctc_align(const cm_ctc_align_args *args);
 
+/* Greedy CTC decode (csrc/ctc_greedy.hip; contract: mamba_asr_amd/ctc_decode.py): per frame the arg-max, repeats
+ * collapsed, blanks removed, with the frames and the log-probability of every kept token.  Two kernels behind this one entry: the
+ * arg-max of every frame < n on a grid over (utterance, frame tile), one wave per frame -- the only pass over log_probs -- and one
+ * workgroup per utterance for keep flags, prefix sum, compaction, ends and the per-token sums.
+ * log_probs: batch rows of (T, V) fp32 or bf16 with unit vocabulary stride, lp_bs / lp_ts elements apart, lp_ts >= V; any element
+ * alignment (16-byte loads wherever the row allows, scalar head and tail).  n = min(input_lengths[b], T), negative counts as 0;
+ * frames at and past n are never read.  No cap on T or V beyond one row spanning less than 2 GiB.
+ * best[t] = the lowest index attaining the frame's maximum (-inf is an ordinary value: an all -inf frame gives 0).  Frame t is kept
+ * when best[t] != blank and (t == 0 or best[t] != best[t-1]).  A NaN in any frame < n: status 2, token_len 0, every row entry -1 / 0.
+ * Outputs: tokens / starts / ends (batch, T) int32 = kept token k, its first frame and one past the last frame of its run, -1 past
+ * token_len[b]; token_logp (batch, T) fp64 = the left fold in increasing t of (double) lp[t][token] over the run, 0.0 past
+ * token_len[b]; status (batch) int32 0 / 2.  workspace: cm_ctc_greedy_workspace_bytes() bytes, 16-byte aligned (the arg-max of every
+ * frame).  Arguments are validated on the host before any launch (CM_EINVAL / CM_EUNSUPPORTED / CM_EALIGN). */
+typedef struct cm_ctc_greedy_args {
+    int32_t batch, T, V, blank, dtype;        /* dtype: CM_F32 or CM_BF16                                       */
+    int64_t lp_bs, lp_ts;                     /* element strides of row and time                                */
+    const void *log_probs;
+    const int32_t *input_lengths;             /* (batch)                                                        */
+    int32_t *tokens, *starts, *ends;          /* (batch, T)                                                     */
+    int32_t *token_len;                       /* (batch)                                                        */
+    double *token_logp;                       /* (batch, T)                                                     */
+    int32_t *status;                          /* (batch)                                                        */
+    void *workspace;                          /* cm_ctc_greedy_workspace_bytes() bytes                          */
+    int64_t workspace_bytes;
+    void *stream;
+} cm_ctc_greedy_args;
+
+int64_t cm_ctc_greedy_workspace_bytes(const cm_ctc_greedy_args *args);
+int cm_ctc_greedy(const cm_ctc_greedy_args *args);
+
+/* Edit distance with alignment counts (csrc/edit_distance.hip; contract: mamba_asr_amd/metrics.py).  Pair p is
+ * (refs[ref_index[p]][0 .. R), hyps[p][0 .. H)), R = ref_len[ref_index[p]] and H = hyp_len[p] clamped to [0, SR] / [0, SH]; ids at
+ * or past a length are never read; many hypotheses may share a reference.  ref_index[p] outside [0, NR): status 1, everything 0.
+ *   D[i][0] = i, D[0][j] = j; sub = D[i-1][j-1] + (a[i-1] != b[j-1]), del = D[i-1][j] + 1, ins = D[i][j-1] + 1;
+ *   move: diagonal if sub < ins && sub < del, else delete if del < ins, else insert; D[i][j] = the move's value.
+ * Backtrace from (R, H): diagonal -> (i-1, j-1), a hit when the tokens are equal, else a substitution; delete -> (i-1, j);
+ * insert -> (i, j-1); row 0 is all inserts, column 0 all deletes.  All arithmetic is int32.
+ * Outputs: counts (N, 4) int32 = [ins, del, sub, hits]; dist (N) int32 = D[R][H]; status (N) int32; with ops != NULL also ops
+ * (N, SR + SH) int8 = the path in forward order as the characters '=', 'I', 'D', 'S' (0 past n_ops[p]) and n_ops (N) int32.
+ * One workgroup per pair: thread j owns hypothesis column j + 1 and walks the anti-diagonals; moves at 2 bits per cell in the
+ * workspace; wave 0 backtraces.  Limits: 0 <= SR <= CM_EDIT_MAX_LEN and 0 <= SH <= CM_EDIT_MAX_LEN, anything longer is
+ * CM_EUNSUPPORTED.  workspace: cm_edit_distance_workspace_bytes() bytes, 16-byte aligned.  Arguments are validated on the host
+ * before any launch (CM_EINVAL / CM_EUNSUPPORTED / CM_EALIGN). */
+#define CM_EDIT_MAX_LEN 1024
+typedef struct cm_edit_distance_args {
+    int32_t N, NR, SR, SH;
+    const int32_t *refs, *ref_len;            /* (NR, SR), (NR); refs may be NULL when SR == 0                  */
+    const int32_t *hyps, *hyp_len;            /* (N, SH), (N); hyps may be NULL when SH == 0                    */
+    const int32_t *ref_index;                 /* (N)                                                            */
+    int32_t *counts;                          /* (N, 4)                                                         */
+    int32_t *dist, *status;                   /* (N)                                                            */
+    int8_t *ops;                              /* (N, SR + SH) or NULL                                           */
+    int32_t *n_ops;                           /* (N); required with ops                                         */
+    void *workspace;                          /* cm_edit_distance_workspace_bytes() bytes                       */
+    int64_t workspace_bytes;
+    void *stream;
+} cm_edit_distance_args;
+
+int64_t cm_edit_distance_workspace_bytes(const cm_edit_distance_args *args);
+int cm_edit_distance(const cm_edit_distance_args *args);
+
 /* LM-free CTC beam search (csrc/ctc_beam.hip; replaces speechbrain.decoders.ctc.CTCBeamSearcher, reference train_CTC.py:309-310,
  * 411-414 and 1155-1161).  The algorithm (mamba_asr_amd/ctc_decode.py): per processed frame select tokens, extend
  * every beam, merge equal (text, partial word, last token), prune by beam_prune_logp, rank, keep beam_size, optionally prune the

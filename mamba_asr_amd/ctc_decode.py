@@ -89,6 +89,11 @@ Words.  A word is the tokens between word-starts, by the rules of compose(): its
 last token's end, its log-probability is the sum of its tokens'; a piece whose clean part is empty (the bare space piece, a bare
 spm_token) and blank belong to no word.  CTCBeamSearcher.search(text_frames=True) aligns each returned hypothesis' own tokens in one
 extra launch: those are the Viterbi frames of the hypothesis, not the frames at which the beam emitted its tokens.
+
+Greedy decoding (CTCGreedyDecoder; ops.ctc_greedy, csrc/ctc_greedy.hip), pinned bit for bit by
+tests/ctc_score_ref.py: per frame the lowest index attaining the maximum (-inf an ordinary value), a frame kept when that index is
+not blank and differs from the previous frame's, each kept token with its run's frames and the float64 left fold of its own
+log-probabilities; a NaN in a frame below the length gives status 2.  The class docstring has the whole contract.
 """
 from __future__ import annotations
 
@@ -114,6 +119,7 @@ class CTCHypothesis:
     score: float = 0.0
     lm_score: float = 0.0
     text_frames: Optional[list] = None
+    tokens: Optional[list] = None            # CTCGreedyDecoder fills it; the beam searchers leave it None
 
 
 def piece_hash(s: str):
@@ -442,6 +448,106 @@ class CTCAligner:
             a, z, lp = starts[u][:k], ends[u][:k], logp[u][:k]
             words, frames, wlp = self.words(row, a, z, lp)
             out.append(CTCAlignment(0, score[u], row, list(zip(a, z)), lp, words, frames, wlp))
+        return out
+
+
+def greedy_host(log_probs: torch.Tensor, counts: Sequence[int], blank: int):
+    """The greedy contract of the module docstring on the host (CPU tensors; the GPU kernel's bits).
+    -> per utterance (status, tokens, starts, ends, token_logp) as host lists."""
+    out = []
+    for row, n in zip(log_probs.detach().cpu(), counts):
+        x = row[:n].double()                                         # exact from fp32 and bf16
+        if bool(torch.isnan(x).any()):
+            out.append((2, [], [], [], []))
+            continue
+        if n == 0:
+            out.append((0, [], [], [], []))
+            continue
+        top = x.max(dim=-1, keepdim=True).values                     # the lowest index attaining it, whatever argmax would pick
+        idx = torch.where(x == top, torch.arange(x.shape[1])[None, :], x.shape[1]).min(dim=-1).values
+        best, vals = idx.tolist(), x.gather(1, idx[:, None])[:, 0].tolist()
+        tokens, starts, ends, logp = [], [], [], []
+        for t, v in enumerate(best):
+            if v != blank and (t == 0 or v != best[t - 1]):
+                tokens.append(v), starts.append(t), ends.append(t + 1), logp.append(vals[t])
+            elif v != blank:
+                ends[-1], logp[-1] = t + 1, logp[-1] + vals[t]
+        out.append((0, tokens, starts, ends, logp))
+    return out
+
+
+class CTCGreedyDecoder:
+    """Greedy CTC decoding (the VALID stage's decode, reference train_CTC.py:305-310): per frame the arg-max, repeats collapsed,
+    blanks removed -- dataio.ctc_greedy_decode's tokens, plus each token's frames and log-probability, from cm_ctc_greedy on the
+    GPU (no host loop over frames) and from greedy_host on CPU tensors, with the same bits.
+
+    The contract (ops.ctc_greedy, csrc/ctc_greedy.hip; pinned by tests/ctc_score_ref.py).  n_b frames are decoded.
+    best[t] = the LOWEST index attaining frame t's maximum; -inf is an ordinary value (an all -inf frame gives index 0).  Frame t is
+    kept when best[t] != blank and (t == 0 or best[t] != best[t-1]): a run broken by blank starts a new token.  A kept token's span
+    is [first frame of its run, one past the last), its log-probability the float64 left fold, in increasing t, of
+    (double) lp[t][token] over the run.  A NaN in any frame < n_b gives that utterance status 2 (ValueError here, naming the
+    utterance); frames at and past n_b are never read.
+
+    __call__(log_probs (batch, T, V), wav_lens (batch) relative lengths or None, lengths=None: absolute frame counts, which win
+    when given) -> one CTCHypothesis per utterance: ``tokens`` the kept ids, ``text`` their composition by the class rules when a
+    vocabulary was given (else ""), ``text_frames`` the words' spans (group_words; None without a vocabulary), ``score`` the sum of
+    the tokens' log-probabilities.  .tokens(log_probs, wav_lens) -> List[List[int]]."""
+
+    def __init__(self, blank_index: int, vocab_list: Optional[Sequence[str]] = None, space_token: str = " ", spm_token: str = "▁"):
+        self.blank_index = int(blank_index)
+        self.vocab_list = None if vocab_list is None else list(vocab_list)
+        self.space_token, self.spm_token = space_token, spm_token
+        if self.blank_index < 0 or (self.vocab_list is not None and self.blank_index >= len(self.vocab_list)):
+            raise ValueError(f"CTCGreedyDecoder: blank_index {blank_index} outside the vocabulary")
+        if self.vocab_list is not None:
+            self.is_spm, self.classes, self.clean = classify_vocab(self.vocab_list, self.blank_index, space_token, spm_token)
+
+    def compose(self, tokens: Sequence[int]) -> str:
+        return CTCBeamSearcher.compose(self, tokens)
+
+    def _decode(self, log_probs, wav_lens, lengths, spans=True):
+        """-> per utterance (tokens, starts, ends, token_logp) as host lists; spans=False reads the tokens back alone (the other
+        three are None).  Status 2 raises."""
+        if log_probs.dim() != 3 or (self.vocab_list is not None and log_probs.shape[2] != len(self.vocab_list)):
+            raise ValueError(f"CTCGreedyDecoder: log_probs must be (batch, T, V) over the vocabulary, got {tuple(log_probs.shape)}")
+        b, steps, v = log_probs.shape
+        if not self.blank_index < v:
+            raise ValueError(f"CTCGreedyDecoder: blank_index {self.blank_index} outside the {v} classes of log_probs")
+        if lengths is None:
+            counts = _frame_counts(steps, wav_lens, b)
+        else:
+            counts = [int(x) for x in lengths]
+            if len(counts) != b or any(not 0 <= x <= steps for x in counts):
+                raise ValueError(f"CTCGreedyDecoder: lengths must be {b} frame counts in [0, {steps}], got {counts}")
+        if b == 0 or steps == 0:
+            return [([], [], [], []) for _ in range(b)]
+        if not log_probs.is_cuda:
+            rows = greedy_host(log_probs, counts, self.blank_index)
+            status, rows = [r[0] for r in rows], [r[1:] for r in rows]
+        else:
+            tokens, token_len, starts, ends, logp, status = ops.ctc_greedy(
+                log_probs, torch.tensor(counts, dtype=torch.int32).to(log_probs.device), blank=self.blank_index)
+            k, status = torch.stack((token_len, status)).cpu().tolist()          # one read-back for both
+            kmax = max(k)
+            cols = [x[:, :kmax].cpu().tolist() if (spans or x is tokens) else None for x in (tokens, starts, ends, logp)]
+            rows = [tuple(None if c is None else c[u][:k[u]] for c in cols) for u in range(b)]
+        for u, s in enumerate(status):
+            if s == 2:
+                raise ValueError(f"CTCGreedyDecoder: log_probs of utterance {u} hold NaN inside its length")
+        return rows
+
+    def tokens(self, log_probs: torch.Tensor, wav_lens: Optional[torch.Tensor] = None, lengths=None) -> List[List[int]]:
+        return [row[0] for row in self._decode(log_probs, wav_lens, lengths, spans=False)]
+
+    def __call__(self, log_probs: torch.Tensor, wav_lens: Optional[torch.Tensor] = None, lengths=None) -> List[CTCHypothesis]:
+        out = []
+        for tok, starts, ends, logp in self._decode(log_probs, wav_lens, lengths):
+            score = float(sum(logp))
+            hyp = CTCHypothesis("", None, score, score, None, tok)
+            if self.vocab_list is not None:
+                hyp.text = self.compose(tok)
+                hyp.text_frames = group_words(tok, starts, ends, logp, self.classes, self.clean)[1]
+            out.append(hyp)
         return out
 
 

@@ -32,6 +32,8 @@ _SB_MAP = {
     "speechbrain.nnet.schedulers.NoamScheduler": "mamba_asr_amd.sb_compat.NoamScheduler",
     "speechbrain.nnet.activations.Swish": "mamba_asr_amd.sb_compat.Swish",
     "speechbrain.utils.epoch_loop.EpochCounter": "mamba_asr_amd.sb_compat.EpochCounter",
+    "speechbrain.utils.metric_stats.ErrorRateStats": "mamba_asr_amd.metrics.ErrorRateStats",
+    "speechbrain.utils.Accuracy.AccuracyStats": "mamba_asr_amd.metrics.AccuracyStats",
 }
 
 

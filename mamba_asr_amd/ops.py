@@ -907,6 +907,86 @@ def ctc_align(log_probs, targets, input_lengths, target_lengths, blank=0, rows=N
     return score, status, states, starts, ends, label_logp
 
 
+def ctc_greedy(log_probs, input_lengths, blank=0, bufs=None):
+    """Greedy CTC decode (cm_ctc_greedy; the contract is in mamba_asr_amd.ctc_decode's docstring).  log_probs (batch, T, V) fp32 /
+    bf16 passed with its strides (unit vocabulary stride; other dtypes are cast to fp32), input_lengths (batch) integer tensor.
+    -> (tokens (batch, T) int32, token_len (batch) int32, starts, ends (batch, T) int32, token_logp (batch, T) fp64, status (batch)
+    int32).  bufs: caller-placed "tokens", "token_len", "starts", "ends", "token_logp", "status" and "workspace" (uint8,
+    cm_ctc_greedy_workspace_bytes)."""
+    _dev_check(log_probs, input_lengths)
+    if log_probs.dim() != 3 or 0 in log_probs.shape:
+        raise RuntimeError(f"ctc_greedy: log_probs must be a non-empty (batch, T, V) tensor, got {tuple(log_probs.shape)}")
+    if log_probs.dtype not in (torch.float32, torch.bfloat16):
+        log_probs = log_probs.float()
+    lp = log_probs.detach()
+    if lp.stride(2) != 1:
+        lp = lp.contiguous()
+    b, t, v = lp.shape
+    dev = lp.device
+    il = input_lengths.detach().to(torch.int32).contiguous()
+    if il.numel() != b:
+        raise RuntimeError(f"ctc_greedy: {b} rows of log_probs need {b} input_lengths, got {il.numel()}")
+    take = _bufs(bufs, ("tokens", "token_len", "starts", "ends", "token_logp", "status", "workspace"), "ctc_greedy")
+    tokens, token_len = take("tokens", (b, t), torch.int32, dev), take("token_len", (b,), torch.int32, dev)
+    starts, ends = take("starts", (b, t), torch.int32, dev), take("ends", (b, t), torch.int32, dev)
+    token_logp, status = take("token_logp", (b, t), torch.float64, dev), take("status", (b,), torch.int32, dev)
+    a = N.CtcGreedyArgs()
+    a.batch, a.T, a.V, a.blank, a.dtype = b, t, v, int(blank), _DT[lp.dtype]
+    a.lp_bs, a.lp_ts = lp.stride(0), lp.stride(1)
+    a.log_probs, a.input_lengths = _ptr(lp), _ptr(il)
+    a.tokens, a.token_len, a.starts, a.ends, a.token_logp, a.status = _ptr(tokens), _ptr(token_len), _ptr(starts), _ptr(ends), _ptr(token_logp), _ptr(status)
+    nws = int(N.lib().cm_ctc_greedy_workspace_bytes(ct.byref(a)))
+    ws = take("workspace", (max(nws, 1),), torch.uint8, dev)
+    a.workspace, a.workspace_bytes, a.stream = _ptr(ws), nws, _stream()
+    _launch("cm_ctc_greedy", N.lib().cm_ctc_greedy, a, units=b * t)
+    return tokens, token_len, starts, ends, token_logp, status
+
+
+def edit_distance(refs, ref_len, hyps, hyp_len, ref_index=None, want_ops=False, bufs=None):
+    """Edit distance with alignment counts (cm_edit_distance; the contract is in mamba_asr_amd.metrics' docstring).  refs (NR, SR)
+    and hyps (N, SH) integer ids padded, ref_len (NR) / hyp_len (N) integer tensors, ref_index (N) the reference of each hypothesis
+    (None: its own, and NR = N).  Sequences longer than CM_EDIT_MAX_LEN are refused by the library (CM_EUNSUPPORTED).
+    -> (counts (N, 4) int32 [ins, del, sub, hits], dist (N) int32, status (N) int32), and with want_ops also (ops (N, SR + SH) int8,
+    n_ops (N) int32).  bufs: caller-placed "counts", "dist", "status", "ops", "n_ops" and "workspace" (uint8,
+    cm_edit_distance_workspace_bytes)."""
+    _dev_check(refs, ref_len, hyps, hyp_len, ref_index)
+    if refs.dim() != 2 or hyps.dim() != 2 or refs.shape[0] == 0 or hyps.shape[0] == 0:
+        raise RuntimeError(f"edit_distance: refs must be (NR, SR) and hyps (N, SH) with NR, N >= 1, got {tuple(refs.shape)} and {tuple(hyps.shape)}")
+    rf, hy = refs.detach().to(torch.int32).contiguous(), hyps.detach().to(torch.int32).contiguous()
+    (nr, sr), (n, sh) = rf.shape, hy.shape
+    dev = hy.device
+    rl, hl = ref_len.detach().to(torch.int32).contiguous(), hyp_len.detach().to(torch.int32).contiguous()
+    if ref_index is None:
+        if nr != n:
+            raise RuntimeError(f"edit_distance: without ref_index every hypothesis has its own reference, got {nr} references for {n} hypotheses")
+        ri = torch.arange(n, dtype=torch.int32, device=dev)
+    else:
+        ri = ref_index.detach().to(torch.int32).contiguous()
+    if rl.numel() != nr or hl.numel() != n or ri.numel() != n:
+        raise RuntimeError(f"edit_distance: need {nr} ref_len and {n} hyp_len / ref_index, got {rl.numel()}, {hl.numel()}, {ri.numel()}")
+    take = _bufs(bufs, ("counts", "dist", "status", "ops", "n_ops", "workspace"), "edit_distance")
+    counts = take("counts", (n, 4), torch.int32, dev)
+    dist, status = take("dist", (n,), torch.int32, dev), take("status", (n,), torch.int32, dev)
+    a = N.EditDistanceArgs()
+    a.N, a.NR, a.SR, a.SH = n, nr, sr, sh
+    a.refs, a.ref_len, a.hyps, a.hyp_len, a.ref_index = (_ptr(rf) if sr else None), _ptr(rl), (_ptr(hy) if sh else None), _ptr(hl), _ptr(ri)
+    a.counts, a.dist, a.status = _ptr(counts), _ptr(dist), _ptr(status)
+    ops_out = n_ops = None
+    if want_ops:
+        n_ops = take("n_ops", (n,), torch.int32, dev)
+        if sr + sh:
+            ops_out = take("ops", (n, sr + sh), torch.int8, dev)
+            a.ops, a.n_ops = _ptr(ops_out), _ptr(n_ops)
+        else:                                                        # every sequence empty: no path, and an empty tensor has no address
+            ops_out = torch.empty((n, 0), dtype=torch.int8, device=dev)
+            n_ops.zero_()
+    nws = int(N.lib().cm_edit_distance_workspace_bytes(ct.byref(a)))
+    ws = take("workspace", (max(nws, 16),), torch.uint8, dev)
+    a.workspace, a.workspace_bytes, a.stream = _ptr(ws), nws, _stream()
+    _launch("cm_edit_distance", N.lib().cm_edit_distance, a, units=n)
+    return (counts, dist, status, ops_out, n_ops) if want_ops else (counts, dist, status)
+
+
 def _ctc_beam_args(what, a, log_probs, dev, tok_class, tok_hash, tok_pow, tok_len, hash_base, hash_sep, blank, beam_size, topk,
                    prune_history, beam_prune_logp, token_prune_min_logp, blank_skip_threshold):
     """What the three CTC beam searches prepare alike, filled into their argument struct ``a``: log_probs as fp32 / bf16 with unit
